@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json): U-Net denoise steps/sec for a 4-item outfit at 64x64x4 latents.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   N > 1: either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...: RANK /
   WORLD_SIZE come from the environment) or plainly as `python bench.py --gpus N`: the process then starts N ranks of itself
   (launch_ranks), one per GPU, and relays rank 0's line.
@@ -13,13 +13,15 @@ in_channels 8) + guidance combine + DDIM update.  Inputs are resident in HBM bef
 Multi-GPU: one process per GPU, each denoising its own outfit (outfits are independent; no data-path
 collective) -> weak scaling; value = N*K / max-over-ranks(elapsed).
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit/..., plus
+A plain run does set-up, W warm-up steps and the K timed steps, writes (--dump-outputs DIR) the latents the last timed step
+returned as DIR/latents.npy (float32, rank 0's outfits) and prints ONE JSON line on rank 0: metric/value/unit/ms_per_step/...
+--full adds, after the timed steps (every --mode):
   "roofline"     : dominant kernel (gemm_bf16_kernel: every conv3x3 / 1x1 / linear) -- ALGORITHMIC flops
                    per launch / average launch duration from HIP events recorded on the launch stream
                    (a second, profiled pass of the same K steps; the timed pass carries no events);
   "cpu_baseline" : the fp32 oracle (stand-in for the reference diffusers path) timed on
                    this box's host cores on a bounded sample;
-  "secondary_configs" (default invocation, one GPU): short legs of the OTHER BASELINE configurations run after the headline's timed
+  "secondary_configs" (--full, one GPU, default mode / shape / dtype): short legs of the OTHER BASELINE configurations run after the headline's timed
                    region, so that one driver-run record witnesses them -- configs[4] (the same sampler with enable_fp8()), the
                    reference's real inference batch (4 outfits per call = U-Net batch 64, inf4eval.py:521-524) and configs[2] (the
                    training step); the headline fields and its timed region are untouched by them (--no-secondary skips them).
@@ -68,9 +70,9 @@ def build_models(dev, cfg_name):
             else:
                 p.zero_()
     enc = da.MutualEncoder(cate_num=50, cate_emb_size=64, latent_channels=4, latent_size=64, hid_dim=256).to(dev).eval()
-    with torch.no_grad():
+    with torch.no_grad():                      # from the seeded generator too: the default ones are seeded at random per process
         for i in (0, 3):
-            torch.nn.init.xavier_normal_(enc.mlp[i].weight)
+            torch.nn.init.xavier_normal_(enc.mlp[i].weight, generator=g)
             enc.mlp[i].bias.zero_()
     unet.pack()
     torch.cuda.synchronize()
@@ -432,28 +434,32 @@ def run_clip(args, da, _lib, ddist, rank, world, dev):
     M = B * T
     gemm_flops = 2.0 * M * L * (4 * D * D + 2 * D * I)                       # q / k / v / out projections + the two MLP linears
     attn_flops = 2.0 * B * H * L * 2 * (T * (T + 1) / 2) * (D // H)          # causal scores + PV (VALU fp32)
-    # HIP events on the launch stream around the K timed encodes of a second pass (the whole encoder is one stream of launches)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(K):
-        m(ids)
-    e1.record()
-    torch.cuda.synchronize()
-    ev_ms = e0.elapsed_time(e1) / K
+    ev_ms = None
+    if not args.no_profile:
+        # HIP events on the launch stream around the K timed encodes of a second pass (the whole encoder is one stream of launches)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(K):
+            m(ids)
+        e1.record()
+        torch.cuda.synchronize()
+        ev_ms = e0.elapsed_time(e1) / K
     if rank != 0:
         return
     FP32_MFMA_PEAK = 157.3
-    ach = (gemm_flops + attn_flops) / (ev_ms * 1e-3) / 1e12
     rec = {"metric": "CLIP text encoder, prompt tables/sec (51 prompts x 77 tokens)", "value": round(world * K / el, 3), "unit": "tables/s",
            "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(el * 1e3 / K, 3), "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": f"SURVEY 8f-2: {('OpenCLIP ViT-H/14, 23 layers x 1024' if args.config == 'sd2base' else 'CLIP ViT-L/14, 12 layers x 768')} text tower, "
                                   "the dataset's closed prompt set (50 category prompts + the empty prompt) = 51 x 77 tokens per step: what a run pays once "
                                   "(PromptTable.build)", "prompts": B, "tokens": T, "prompts_per_s": round(world * K * B / el, 1)},
-           "roofline": {"bound": "mfma", "kernel": "clip_gemm_f32_kernel (v_mfma_f32_16x16x4_f32) + clip_attention_kernel", "achieved": round(ach, 2),
-                        "peak": FP32_MFMA_PEAK, "unit": "TFLOP/s", "frac": round(ach / FP32_MFMA_PEAK, 4), "traffic": None,
-                        "algorithmic_tflop_per_step": round((gemm_flops + attn_flops) / 1e12, 4), "event_ms_per_step": round(ev_ms, 3),
-                        "note": "HIP events on the launch stream around the K encodes; fp32 matrix peak 256 FLOP/clk/CU x 256 CUs x 2.4 GHz"}}
+           "roofline": None}
+    if ev_ms is not None:
+        ach = (gemm_flops + attn_flops) / (ev_ms * 1e-3) / 1e12
+        rec["roofline"] = {"bound": "mfma", "kernel": "clip_gemm_f32_kernel (v_mfma_f32_16x16x4_f32) + clip_attention_kernel", "achieved": round(ach, 2),
+                           "peak": FP32_MFMA_PEAK, "unit": "TFLOP/s", "frac": round(ach / FP32_MFMA_PEAK, 4), "traffic": None,
+                           "algorithmic_tflop_per_step": round((gemm_flops + attn_flops) / 1e12, 4), "event_ms_per_step": round(ev_ms, 3),
+                           "note": "HIP events on the launch stream around the K encodes; fp32 matrix peak 256 FLOP/clk/CU x 256 CUs x 2.4 GHz"}
     if not args.no_cpu_baseline and world == 1:
         torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
         p = clip_ref.init_params(cfg, 0)
@@ -682,7 +688,9 @@ def measure_sampling(da, _lib, ddist, unet, enc, dev, rank, K, W, outfits=1, dty
     elapsed = ddist.max_over_ranks(time.perf_counter() - t0)
     own_max, own_min = ddist.max_over_ranks(own), min_over_ranks(ddist, own)
     assert torch.isfinite(sampler.latents).all(), "non-finite latents"
-    res = dict(elapsed=elapsed, own_min=own_min, own_max=own_max, roofline=None, classes=None, bound={}, prof_ms=None)
+    # what the last timed step returned (--dump-outputs), copied before the profiled pass steps the sampler on
+    res = dict(elapsed=elapsed, own_min=own_min, own_max=own_max, roofline=None, classes=None, bound={}, prof_ms=None,
+               latents=sampler.latents.clone())
     if profile and rank == 0:
         torch.cuda.synchronize()
         _lib.prof_begin()
@@ -778,11 +786,22 @@ def main():
                          "cross q, cross to_out, the GEGLU pair, proj_out) in e4m3 on the block-scaled MFMA; 3x3 convs stay bf16")
     ap.add_argument("--fp8-attention", action="store_true",
                     help="with --dtype fp8: also the self-attention products QK^T / PV on the e4m3 MFMA (opt-in: measured slower, profiles/r04)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, after its timed steps: the profiled pass (roofline, kernel classes), "
+                         "the CPU baseline and, on one GPU, the secondary_configs legs (--no-profile / --no-cpu-baseline / --no-secondary drop "
+                         "one of them again).  Off: a plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="--mode sample: after the timed steps, write what the last timed step returned (the latents of rank 0's outfits) "
+                         "as DIR/latents.npy, float32; the inputs depend on the arguments only")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU-only check of the --gpus N launcher flow (tests/test_host_logic_cpu.py, world 8): every rank joins a gloo group "
                          "from the RANK / WORLD_SIZE / MASTER_* environment launch_ranks gives it, one all-reduce counts the ranks, rank 0 prints "
                          "one JSON line.  Touches no GPU and measures nothing")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "sample":
+        ap.error("--dump-outputs is implemented for --mode sample")
+    if not args.full:
+        args.no_profile = args.no_cpu_baseline = args.no_secondary = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher.  Nothing here has touched the GPU yet (no HIP call, no
@@ -845,6 +864,10 @@ def main():
         ddist.barrier()
     if rank != 0:
         return
+    if args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy"), r["latents"].float().cpu().numpy())
     value = world * nout * K / elapsed
     if nout == 1:
         workload = ("BASELINE configs[1]" if args.dtype == "bf16" else "BASELINE configs[4] on one GPU (fp8 transformer linears"
