@@ -11,8 +11,22 @@ import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
+# The 16-bit storage format of activations and packed weights is a property of the PROCESS: each format is a build of its own
+# of the kernel library (csrc/Makefile), chosen before the library is first loaded -- DFH_STORAGE=fp16 in the environment or
+# set_storage("fp16"); unset means bf16.  The fp16 library is inference only (training and the fp8 legs refuse there).
+_LIB_NAMES = {"bf16": "libdifashion_hip.so", "fp16": "libdifashion_hip_f16.so"}
+
+
+def _env_storage() -> str:
+    v = (os.environ.get("DFH_STORAGE") or "bf16").strip().lower()
+    if v not in _LIB_NAMES:
+        raise ValueError(f"DFH_STORAGE={v!r}: the storage format is 'bf16' (default) or 'fp16'")
+    return v
+
+
+_STORAGE = _env_storage()
 # DFH_LIB=<path>: load another build of the library (same-box A/B probes); the product path never sets it
-LIB_PATH = os.environ.get("DFH_LIB") or os.path.join(CSRC, "libdifashion_hip.so")
+LIB_PATH = os.environ.get("DFH_LIB") or os.path.join(CSRC, _LIB_NAMES[_STORAGE])
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "difashion_hip.h")
 
 DFH_MAX_BLOCKS = 4
@@ -240,14 +254,61 @@ _UNBOUND = set()
 ABI_VERSION = 7          # == DFH_ABI_VERSION of include/difashion_hip.h (checked when the library is loaded)
 
 
+def storage() -> str:
+    """'bf16' or 'fp16': the 16-bit storage format of this process's kernel library."""
+    return _STORAGE
+
+
+def set_storage(name: str) -> None:
+    """Choose the storage format before the library is first used.  Raises once the library is loaded with the other format."""
+    global _STORAGE, LIB_PATH
+    name = str(name).strip().lower()
+    if name not in _LIB_NAMES:
+        raise ValueError(f"set_storage({name!r}): the storage format is 'bf16' or 'fp16'")
+    if name == _STORAGE:
+        return
+    if _lib is not None:
+        raise DfhError(f"set_storage({name!r}): the {_STORAGE} library is already loaded ({LIB_PATH}); the storage format is fixed "
+                       "per process -- set DFH_STORAGE or call set_storage() before the first use")
+    _STORAGE = name
+    if not os.environ.get("DFH_LIB"):
+        LIB_PATH = os.path.join(CSRC, _LIB_NAMES[name])
+
+
+def storage_dtype():
+    """The torch dtype that tensor dtype code 1 of the C ABI means in this process."""
+    import torch
+    return torch.float16 if _STORAGE == "fp16" else torch.bfloat16
+
+
+def dtype_code(t, what: str = "tensor") -> int:
+    """C-ABI dtype code of a tensor: 0 = float32, 1 = the library's storage type.  The other 16-bit type is refused."""
+    import torch
+    if t.dtype == torch.float32:
+        return 0
+    if t.dtype == storage_dtype():
+        return 1
+    if t.dtype in (torch.float16, torch.bfloat16):
+        raise TypeError(f"{what} is {t.dtype}, but this process runs the {_STORAGE}-storage library: pass float32 or "
+                        f"{storage_dtype()} (DFH_STORAGE / set_storage() select the other library)")
+    raise TypeError(f"{what} must be float32 or {storage_dtype()}, got {t.dtype}")
+
+
+def require_bf16(what: str) -> None:
+    """Training and the fp8 legs exist in the bf16 library only."""
+    if _STORAGE != "bf16":
+        raise DfhError(f"{what} is refused under DFH_STORAGE=fp16: the fp16-storage library is inference only (training has no loss "
+                       "scaling; the fp8 epilogues are calibrated against bf16 producers) -- run it with the default bf16 storage")
+
+
 def build(force: bool = False) -> str:
-    """Compile the HIP sources for gfx950 (hipcc cross-compiles without a GPU)."""
+    """Compile the HIP sources for gfx950 (hipcc cross-compiles without a GPU): both storage builds of the library."""
     args = ["make", "-C", CSRC, "-j", str(min(8, os.cpu_count() or 1))]
     if force:
         subprocess.run(["make", "-C", CSRC, "clean"], check=True, capture_output=True)
     r = subprocess.run(args, capture_output=True, text=True)
     if r.returncode != 0:
-        raise DfhError("building libdifashion_hip.so failed:\n" + r.stdout[-4000:] + r.stderr[-4000:])
+        raise DfhError("building libdifashion_hip.so / libdifashion_hip_f16.so failed:\n" + r.stdout[-4000:] + r.stderr[-4000:])
     return LIB_PATH
 
 
@@ -277,6 +338,10 @@ def raw():
             raise DfhError(f"{LIB_PATH} reports ABI {got}, this Python side binds ABI {ABI_VERSION} (include/difashion_hip.h "
                            "DFH_ABI_VERSION): rebuild the library (`python -c 'import __graft_entry__ as g; g.build()'`)"
                            + ("; DFH_LIB_ALLOW_ABI_MISMATCH=1 loads it anyway for an A/B probe" if os.environ.get("DFH_LIB") else ""))
+        info = lib.dfh_build_info().decode()
+        built = info.split("storage=")[1].split()[0] if "storage=" in info else "bf16"      # older builds (DFH_LIB probes): bf16
+        if built != _STORAGE:
+            raise DfhError(f"{LIB_PATH} is a {built}-storage build, this process selected {_STORAGE} (DFH_STORAGE / set_storage())")
         global _UNBOUND
         _UNBOUND = unbound
         _lib = lib

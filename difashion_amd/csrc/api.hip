@@ -120,7 +120,12 @@ long dfh_census_get(int i) { return (i >= 0 && i < dfh::CK_COUNT) ? dfh::g_censu
 const char* dfh_last_error(void) { return dfh::g_err.c_str(); }
 #define DFH_STR2(x) #x
 #define DFH_STR(x) DFH_STR2(x)
-const char* dfh_build_info(void) { return "libdifashion_hip gfx950 (CDNA4) bf16/fp8-MFMA abi=" DFH_STR(DFH_ABI_VERSION); }
+#ifdef DFH_F16
+#define DFH_MFMA_DESC "fp16-MFMA"
+#else
+#define DFH_MFMA_DESC "bf16/fp8-MFMA"
+#endif
+const char* dfh_build_info(void) { return "libdifashion_hip gfx950 (CDNA4) " DFH_MFMA_DESC " abi=" DFH_STR(DFH_ABI_VERSION) " storage=" DFH_STORAGE_NAME; }
 
 size_t dfh_gemm_partial_floats(const dfh_gemm_desc* d) {
   GemmArgs g;
@@ -169,6 +174,7 @@ static int fill_wgrad(const dfh_gemm_desc* d, const void* dY, int ldy, float* dW
 }
 
 int dfh_gemm_wgrad(const dfh_gemm_desc* d, const void* dY, int ldy, float* dW, int ldw, int msplit, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(d && dY && dW, "null argument");
   WgradArgs w;
   if (int rc = fill_wgrad(d, dY, ldy, dW, ldw, msplit, w)) return rc;
@@ -176,12 +182,14 @@ int dfh_gemm_wgrad(const dfh_gemm_desc* d, const void* dY, int ldy, float* dW, i
 }
 
 size_t dfh_gemm_wgrad_partial_floats(const dfh_gemm_desc* d, int msplit) {
+  DFH_BF16_ONLY_TRAINING_SIZE;
   WgradArgs w;
   if (!d || fill_wgrad(d, nullptr, 8, nullptr, 8, msplit, w)) return 0;
   return dfh::wgrad_partial_floats(w);
 }
 
 int dfh_gemm_wgrad_plan(const dfh_gemm_desc* d, int msplit, int* tiles, int* whole_tiles, int* slices) {
+  DFH_BF16_ONLY_TRAINING;
   WgradArgs w;
   DFH_REQUIRE(d && tiles && whole_tiles && slices, "null argument");
   if (int rc = fill_wgrad(d, nullptr, 8, nullptr, 8, msplit, w)) return rc;
@@ -191,6 +199,7 @@ int dfh_gemm_wgrad_plan(const dfh_gemm_desc* d, int msplit, int* tiles, int* who
 }
 
 int dfh_colsum(const void* Y, int ldy, int N, int groups, int rows_per_group, float* out, int ld_out, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(Y && out, "null argument");
   return dfh::colsum_launch((const bf16_t*)Y, ldy, N, groups, rows_per_group, out, ld_out, (hipStream_t)stream);
 }
@@ -223,6 +232,7 @@ int dfh_groupnorm_stats(const void* src0, int c0, const void* src1, int c1, int 
 int dfh_groupnorm_bwd(const void* src0, int c0, const void* src1, int c1, const void* dy, int batch, int hw, int groups,
                       const float* gamma, const float* beta, const float* stats, int silu, void* dx0, int acc0, void* dx1,
                       int acc1, float* dgamma, float* dbeta, float* partial, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   GnBwdArgs a; std::memset(&a, 0, sizeof(a));
   a.src0 = (const bf16_t*)src0; a.C0 = c0; a.src1 = (const bf16_t*)src1; a.C1 = src1 ? c1 : 0; a.dy = (const bf16_t*)dy;
   a.B = batch; a.HW = hw; a.G = groups; a.gamma = gamma; a.beta = beta; a.stats = stats; a.silu = silu;
@@ -237,11 +247,13 @@ int dfh_attention_lse(const void* Q, int ldq, const void* K, int ldk, const void
   return dfh::attention_launch(a, (hipStream_t)stream);
 }
 int dfh_attention_delta(const void* O, const void* dO, int ld, float* delta, int batch, int heads, int head_dim, int Nq, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::attention_delta_launch((const bf16_t*)O, (const bf16_t*)dO, ld, delta, batch, heads, head_dim, Nq, (hipStream_t)stream);
 }
 int dfh_attention_bwd(const void* Q, int ldq, const void* K, int ldk, const void* V, int ldv, const void* dO, int ldo,
                       const float* lse, const float* delta, void* dQ, int lddq, void* dK, int lddk, void* dV, int lddv, int batch,
                       int heads, int head_dim, int Nq, int Nk, float scale, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   AttnBwdArgs a; std::memset(&a, 0, sizeof(a));
   a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.V = (const bf16_t*)V; a.ldv = ldv;
   a.dO = (const bf16_t*)dO; a.ldo = ldo; a.lse = lse; a.delta = delta;
@@ -251,22 +263,28 @@ int dfh_attention_bwd(const void* Q, int ldq, const void* K, int ldk, const void
 }
 int dfh_layernorm_bwd(const void* x, const void* dy, const float* gamma, void* dx, int accumulate, float* dgamma, float* dbeta,
                       int M, int C, float eps, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::layernorm_bwd_launch((const bf16_t*)x, (const bf16_t*)dy, gamma, (bf16_t*)dx, accumulate, dgamma, dbeta, M, C, eps,
                                    (hipStream_t)stream);
 }
 int dfh_pack_matrix_t(const float* w, void* out, int N, int K, int ldt, int t_row_off, int t_col_off, int geglu, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::pack_matrix_t_launch(w, (bf16_t*)out, N, K, ldt, t_row_off, t_col_off, geglu, (hipStream_t)stream);
 }
 int dfh_pack_conv3x3_t(const float* w, void* out, int Cout, int Cin, int ldt, int t_col_off, int o_pad, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::pack_conv3x3_t_launch(w, (bf16_t*)out, Cout, Cin, ldt, t_col_off, o_pad, (hipStream_t)stream);
 }
 int dfh_unpack_matrix(const float* g, float* grad, int N, int K, int ldw, int row_off, int col_off, int geglu, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::unpack_matrix_launch(g, grad, N, K, ldw, row_off, col_off, geglu, (hipStream_t)stream);
 }
 int dfh_unpack_conv3x3(const float* g, float* grad, int Cout, int Cin, int ldw, int col_off, int cin_pad, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::unpack_conv3x3_launch(g, grad, Cout, Cin, ldw, col_off, cin_pad, (hipStream_t)stream);
 }
 int dfh_unpack_vector(const float* g, float* grad, int N, int off, int geglu, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::unpack_vector_launch(g, grad, N, off, geglu, (hipStream_t)stream);
 }
 int dfh_pool2x2_sum(const void* in, void* out, int batch, int H, int W, int C, void* stream) {
@@ -279,6 +297,7 @@ int dfh_geglu_fwd(const void* pre, void* y, size_t M, int N2, void* stream) {
   return dfh::geglu_fwd_launch((const bf16_t*)pre, (bf16_t*)y, (long)M, N2, (hipStream_t)stream);
 }
 int dfh_geglu_bwd(const void* pre, const void* dy, void* dpre, size_t M, int N2, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::geglu_bwd_launch((const bf16_t*)pre, (const bf16_t*)dy, (bf16_t*)dpre, (long)M, N2, (hipStream_t)stream);
 }
 int dfh_act_fwd(const void* pre, void* y, size_t n, int kind, void* stream) {
@@ -286,6 +305,7 @@ int dfh_act_fwd(const void* pre, void* y, size_t n, int kind, void* stream) {
 }
 int dfh_act_bwd(const void* ref_bf16, const float* ref_f32, const void* dy_bf16, const float* dy_f32, void* dpre, size_t n, int kind,
                 float scale, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::act_bwd_launch((const bf16_t*)ref_bf16, ref_f32, (const bf16_t*)dy_bf16, dy_f32, (bf16_t*)dpre, (long)n, kind, scale,
                              (hipStream_t)stream);
 }
@@ -299,33 +319,41 @@ int dfh_transpose_bf16(const void* in, void* out, int batch, int R, int C, int l
 }
 int dfh_mse_bwd(const float* pred, const float* target, const float* w, float* dpred, int rows, int L, float loss_scale,
                 const float* scale_dev, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::mse_bwd_launch(pred, target, w, dpred, rows, L, loss_scale, scale_dev, (hipStream_t)stream);
 }
 int dfh_assemble_bwd(const float* dx, const uint8_t* mutual_real, float* dmutual, int rows, int CL, float eta, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::assemble_bwd_launch(dx, mutual_real, dmutual, rows, CL, eta, (hipStream_t)stream);
 }
-int dfh_sumsq(const float* g, size_t n, float* out, void* stream) { return dfh::sumsq_launch(g, (long)n, out, (hipStream_t)stream); }
+int dfh_sumsq(const float* g, size_t n, float* out, void* stream) { DFH_BF16_ONLY_TRAINING; return dfh::sumsq_launch(g, (long)n, out, (hipStream_t)stream); }
 int dfh_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
               float weight_decay, int step, const float* sumsq, float max_norm, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::adamw_launch(p, g, m, v, (long)n, lr, beta1, beta2, eps, weight_decay, step, sumsq, max_norm, (hipStream_t)stream);
 }
 int dfh_adamw_ema(float* p, const float* g, float* m, float* v, float* shadow, size_t n, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int step, const float* sumsq, float max_norm, float ema_decay, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(shadow != nullptr, "null shadow");
   return dfh::adamw_launch(p, g, m, v, (long)n, lr, beta1, beta2, eps, weight_decay, step, sumsq, max_norm, (hipStream_t)stream, shadow,
                            ema_decay);
 }
 int dfh_ema(float* shadow, const float* p, size_t n, float decay, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::ema_launch(shadow, p, (long)n, decay, (hipStream_t)stream);
 }
 
 int dfh_wire_pack(const float* g, void* wire, size_t n, size_t n_pad, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::wire_pack_launch(g, (bf16_t*)wire, (long)n, (long)n_pad, (hipStream_t)stream);
 }
 int dfh_wire_shard_mean(const void* recv, void* shard, int world, size_t per, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::wire_shard_mean_launch((const bf16_t*)recv, (bf16_t*)shard, world, (long)per, (hipStream_t)stream);
 }
 int dfh_wire_unpack(const void* wire, float* g, size_t n, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::wire_unpack_launch((const bf16_t*)wire, g, (long)n, (hipStream_t)stream);
 }
 
@@ -444,6 +472,7 @@ int dfh_gemm_batched(const dfh_gemm_desc* d, int nbatch, long a_bs, long w_bs, l
 }
 
 int dfh_gemm_fp8(const dfh_gemm_fp8_desc* d, void* stream) {
+  DFH_BF16_ONLY_FP8;
   DFH_REQUIRE(d != nullptr, "null descriptor");
   Fp8GemmArgs g; std::memset(&g, 0, sizeof(g));
   g.A = (const uint8_t*)d->A; g.lda = d->lda; g.sA = d->sA; g.sa_div = d->sa_div; g.sa_mul = d->sa_mul; g.sx = (const uint8_t*)d->sx;
@@ -477,6 +506,7 @@ int dfh_mlp_fused(const void* x, const void* resid, const void* img, const float
   return dfh::mlp2_fused_launch(a, (hipStream_t)stream);
 }
 int dfh_groupnorm_fp8(const void* src, int batch, int HW, int C, int groups, float eps, float q_mul, void* q, float* partial, void* stream) {
+  DFH_BF16_ONLY_FP8;
   GnArgs a; std::memset(&a, 0, sizeof(a));
   a.src0 = (const bf16_t*)src; a.C0 = C; a.B = batch; a.HW = HW; a.G = groups; a.eps = eps; a.out8 = (uint8_t*)q; a.q_mul = q_mul;
   a.partial = partial;
@@ -484,6 +514,7 @@ int dfh_groupnorm_fp8(const void* src, int batch, int HW, int C, int groups, flo
 }
 int dfh_attention_fp8out(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O8, int ldo, const float* v_amax,
                          int batch, int heads, int head_dim, int Nq, int Nk, float scale, void* stream) {
+  DFH_BF16_ONLY_FP8;
   AttnArgs a; std::memset(&a, 0, sizeof(a));
   a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.Vt = (const bf16_t*)Vt; a.ldvt = ldvt;
   a.O8 = (uint8_t*)O8; a.ldo = ldo; a.o_amax = v_amax; a.B = batch; a.H = heads; a.D = head_dim; a.Nq = Nq; a.Nk = Nk; a.scale = scale;
@@ -493,6 +524,7 @@ int dfh_attention_fp8out(const void* Q, int ldq, const void* K, int ldk, const v
 int dfh_attention_fp8(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O, int ldo, const float* rq,
                       const float* rk, const float* rv, const float* hs, int batch, int heads, int head_dim, int Nq, int Nk, float scale,
                       void* stream) {
+  DFH_BF16_ONLY_FP8;
   AttnArgs a; std::memset(&a, 0, sizeof(a));
   a.Q = (const bf16_t*)Q; a.ldq = ldq; a.K = (const bf16_t*)K; a.ldk = ldk; a.Vt = (const bf16_t*)Vt; a.ldvt = ldvt;
   a.O = (bf16_t*)O; a.ldo = ldo; a.B = batch; a.H = heads; a.D = head_dim; a.Nq = Nq; a.Nk = Nk; a.scale = scale;
@@ -502,16 +534,20 @@ int dfh_attention_fp8(const void* Q, int ldq, const void* K, int ldk, const void
   return dfh::attention_launch(a, (hipStream_t)stream);
 }
 int dfh_attn_scales(const void* wf, const float* bf, int C, int heads, float* rq, float* rk, float* rv, float* hs, void* stream) {
+  DFH_BF16_ONLY_FP8;
   return dfh::attn_scales_launch((const bf16_t*)wf, bf, C, heads, rq, rk, rv, hs, (hipStream_t)stream);
 }
 int dfh_amax_slabs(const void* x, long bstride, int ld, int cols, const int* row0, const int* nrows, float* out, int nslab, int batch,
                    void* stream) {
+  DFH_BF16_ONLY_FP8;
   return dfh::amax_slabs_launch((const bf16_t*)x, bstride, ld, cols, row0, nrows, out, nslab, batch, (hipStream_t)stream);
 }
 int dfh_quantize_rows_fp8(const void* x, int ldx, void* q, float* scale, int R, int K, void* stream) {
+  DFH_BF16_ONLY_FP8;
   return dfh::quant_rows_fp8_launch((const bf16_t*)x, ldx, (uint8_t*)q, scale, R, K, (hipStream_t)stream);
 }
 int dfh_layernorm_fp8(const void* x, const float* gamma, const float* beta, void* q, float* scale, int M, int C, float eps, void* stream) {
+  DFH_BF16_ONLY_FP8;
   return dfh::layernorm_fp8_launch((const bf16_t*)x, gamma, beta, (uint8_t*)q, scale, M, C, eps, (hipStream_t)stream);
 }
 
@@ -568,6 +604,7 @@ int dfh_noise_mix(const float* x0, const float* noise, const int64_t* t, const f
   return dfh::noise_mix_launch(x0, noise, (const long*)t, sqrt_acp, sqrt_1m_acp, noisy, velocity, rows, L, (hipStream_t)stream);
 }
 int dfh_mse_rows(const float* pred, const float* target, float* out, int rows, int L, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   return dfh::mse_rows_launch(pred, target, out, rows, L, (hipStream_t)stream);
 }
 

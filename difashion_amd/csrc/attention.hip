@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
   const bf16_t* Vb = a.Vt + (long)b * (a.vt_bstride ? a.vt_bstride : (long)a.H * D * a.ldvt) + (long)h * D * a.ldvt;
 
   // ---- Q fragments (B operand of S^T = K.Q^T): lane holds Q[q = fr][d = ks*32 + fg*8 ..+8]
-  bf16x8_t qf[2][KS];
+  h16x8_t qf[2][KS];
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = q0 + qt * 16 + fr;
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
       const int d0 = ks * 32 + fg * 8;
       uint4 v = uint4{0, 0, 0, 0};
       if (q < a.Nq && d0 < D) v = *(const uint4*)(Qb + (long)q * a.ldq + d0);
-      qf[qt][ks] = __builtin_bit_cast(bf16x8_t, v);
+      qf[qt][ks] = __builtin_bit_cast(h16x8_t, v);
     }
   }
 
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
       const int row = idx >> 3, slot = idx & 7;
       const int k0 = kv0 + slot * 8;
       uint4 v = uint4{0, 0, 0, 0};
-      if (ONES_ROW && row == D) v = uint4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};   // bf16 1.0 x8
+      if (ONES_ROW && row == D) v = uint4{DFH_H16_ONE2, DFH_H16_ONE2, DFH_H16_ONE2, DFH_H16_ONE2};   // 1.0 x8 in the storage type
       if (idx < DF * 128 && row < D && (FULL || k0 < a.Nk)) {
         v = *(const uint4*)(Vb + (long)row * a.ldvt + k0);
         if (!FULL && k0 + 8 > a.Nk) {   // ragged tail (cross-attention, Nk = 77): zero the padding keys
@@ -173,14 +173,14 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
       const int sw = (KSTR == 128) ? ((fr >> 1) & 7) : fr;
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
-        const bf16x8_t kf = *(const bf16x8_t*)(Ks + key * KSTR + (((ks * 4 + fg) ^ sw) << 4));
-        s[0][tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[0][ks], s[0][tt], 0, 0, 0);
-        s[1][tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[1][ks], s[1][tt], 0, 0, 0);
+        const h16x8_t kf = *(const h16x8_t*)(Ks + key * KSTR + (((ks * 4 + fg) ^ sw) << 4));
+        s[0][tt] = DFH_MFMA_16x16x32(kf, qf[0][ks], s[0][tt], 0, 0, 0);
+        s[1][tt] = DFH_MFMA_16x16x32(kf, qf[1][ks], s[1][tt], 0, 0, 0);
       }
     }
     // lane (fr = query, fg) holds for tile tt, reg r: key kv0 + (tt>>1)*32 + fg*8 + (tt&1)*4 + r
     const bool ragged = !FAST && kv0 + KV_TILE > a.Nk;
-    bf16x8_t pf[2][2];
+    h16x8_t pf[2][2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
       float sc[4][4];      // raw scores; the scale c is folded into the exp2 argument (one FMA per score)
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
         w.y = pack2bf(sc[2 * ch][2], sc[2 * ch][3]);
         w.z = pack2bf(sc[2 * ch + 1][0], sc[2 * ch + 1][1]);
         w.w = pack2bf(sc[2 * ch + 1][2], sc[2 * ch + 1][3]);
-        pf[qt][ch] = __builtin_bit_cast(bf16x8_t, w);
+        pf[qt][ch] = __builtin_bit_cast(h16x8_t, w);
       }
     }
     // ---- O^T += V^T . P^T
@@ -241,9 +241,9 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
       const int row = f * 16 + fr;
 #pragma unroll
       for (int ch = 0; ch < 2; ++ch) {
-        const bf16x8_t vf = *(const bf16x8_t*)(Vs + row * 128 + (((ch * 4 + fg) ^ ((row >> 1) & 7)) << 4));
-        oacc[0][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[0][ch], oacc[0][f], 0, 0, 0);
-        oacc[1][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[1][ch], oacc[1][f], 0, 0, 0);
+        const h16x8_t vf = *(const h16x8_t*)(Vs + row * 128 + (((ch * 4 + fg) ^ ((row >> 1) & 7)) << 4));
+        oacc[0][f] = DFH_MFMA_16x16x32(vf, pf[0][ch], oacc[0][f], 0, 0, 0);
+        oacc[1][f] = DFH_MFMA_16x16x32(vf, pf[1][ch], oacc[1][f], 0, 0, 0);
       }
     }
     if (more) store_tile((t + 1) & 1);   // the other buffer: last read one barrier ago

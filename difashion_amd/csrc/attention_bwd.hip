@@ -44,7 +44,7 @@ template <int STR> DFH_DEVICE int swz(int row) {
 
 // transposed fragment: 8 consecutive tile rows m0..m0+7 of head-dim column d0 + L (A operand rows = head dim)
 template <int STR>
-DFH_DEVICE bf16x8_t tr_frag(const unsigned char* tile, int m0, int d0, int L) {
+DFH_DEVICE h16x8_t tr_frag(const unsigned char* tile, int m0, int d0, int L) {
   const int col = d0 + (L & 3) * 4;
   const int r0 = m0 + (L >> 2), r1 = r0 + 4;
   const unsigned char* p0 = tile + r0 * STR + ((((col >> 3)) ^ swz<STR>(r0)) << 4) + (col & 7) * 2;
@@ -52,13 +52,13 @@ DFH_DEVICE bf16x8_t tr_frag(const unsigned char* tile, int m0, int d0, int L) {
   const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p0);
   const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p1);
   const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, v);
+  return __builtin_bit_cast(h16x8_t, v);
 }
 
 // X32 variant: rows m0 + {0..3} and m0 + 8 + {0..3} of head-dim column d0 + L (the k-slot order the swapped 32x32 C layout leaves in a lane
 // group), tile swizzled by (row >> 1) & 7
 template <int STR>
-DFH_DEVICE bf16x8_t tr_frag_x32(const unsigned char* tile, int m0, int d0, int L) {
+DFH_DEVICE h16x8_t tr_frag_x32(const unsigned char* tile, int m0, int d0, int L) {
   const int col = d0 + (L & 3) * 4;
   const int r0 = m0 + (L >> 2), r1 = r0 + 8;
   const unsigned char* p0 = tile + r0 * STR + ((((col >> 3)) ^ ((r0 >> 1) & 7)) << 4) + (col & 7) * 2;
@@ -66,7 +66,7 @@ DFH_DEVICE bf16x8_t tr_frag_x32(const unsigned char* tile, int m0, int d0, int L
   const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p0);
   const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)p1);
   const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, v);
+  return __builtin_bit_cast(h16x8_t, v);
 }
 
 // KV_SIDE = false: columns are queries (dQ pass); true: columns are keys (dK / dV pass)
@@ -116,7 +116,7 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
   };
   auto sw_of = [](int row) { return X32 ? ((row >> 1) & 7) : swz<STR>(row); };      // X32: 32 consecutive rows per fragment read
   // X32: column operands of the 32x32x16 MFMAs -- lane (column lane & 31, half hi = lane >> 5) holds d = 16 ks + 8 hi .. + 7
-  bf16x8_t yx1[X32 ? KS32 : 1], yx2[X32 ? KS32 : 1];
+  h16x8_t yx1[X32 ? KS32 : 1], yx2[X32 ? KS32 : 1];
   if (X32) {
     const int col = c0 + (lane & 31), hi = lane >> 5;
 #pragma unroll
@@ -135,11 +135,11 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
         if (KV_SIDE) { v1.x = pack2bf(1.0f, 1.0f); v2.x = v1.x; }
         else { v1.x = split2(-lse[col]); v1.y = pack2bf(MASKV, 0.f); v2.x = split2(-dlt[col]); }
       }
-      yx1[ks] = __builtin_bit_cast(bf16x8_t, v1);
-      yx2[ks] = __builtin_bit_cast(bf16x8_t, v2);
+      yx1[ks] = __builtin_bit_cast(h16x8_t, v1);
+      yx2[ks] = __builtin_bit_cast(h16x8_t, v2);
     }
   }
-  bf16x8_t y1[NT][KS], y2[NT][KS];
+  h16x8_t y1[NT][KS], y2[NT][KS];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     if (X32) break;
@@ -162,8 +162,8 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
         if (KV_SIDE) { v1.x = pack2bf(1.0f, 1.0f); v2.x = v1.x; }
         else { v1.x = split2(-lse[col]); v1.y = pack2bf(MASKV, 0.f); v2.x = split2(-dlt[col]); }
       }
-      y1[nt][ks] = __builtin_bit_cast(bf16x8_t, v1);
-      y2[nt][ks] = __builtin_bit_cast(bf16x8_t, v2);
+      y1[nt][ks] = __builtin_bit_cast(h16x8_t, v1);
+      y2[nt][ks] = __builtin_bit_cast(h16x8_t, v2);
     }
   }
   // per-column softmax statistics (dQ pass: the lane's own query)
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
     const unsigned char* T2 = T1 + G::TILE;
     const float* st = (const float*)(T2 + G::TILE);
 
-    bf16x8_t pf[NT][2], dsf[NT][2];
+    h16x8_t pf[NT][2], dsf[NT][2];
     if (X32) {
       typedef __attribute__((ext_vector_type(16))) float f32x16_t;
       typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
@@ -298,10 +298,10 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
         for (int e = 0; e < 16; ++e) { tS[e] = 0.f; tU[e] = 0.f; }
 #pragma unroll
         for (int ks = 0; ks < KS32; ++ks) {
-          const bf16x8_t x1 = *(const bf16x8_t*)(T1 + row * STR + (((ks * 2 + hi) ^ sw) << 4));
-          const bf16x8_t x2 = *(const bf16x8_t*)(T2 + row * STR + (((ks * 2 + hi) ^ sw) << 4));
-          tS = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x1, yx1[ks], tS, 0, 0, 0);
-          tU = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x2, yx2[ks], tU, 0, 0, 0);
+          const h16x8_t x1 = *(const h16x8_t*)(T1 + row * STR + (((ks * 2 + hi) ^ sw) << 4));
+          const h16x8_t x2 = *(const h16x8_t*)(T2 + row * STR + (((ks * 2 + hi) ^ sw) << 4));
+          tS = DFH_MFMA_32x32x16(x1, yx1[ks], tS, 0, 0, 0);
+          tU = DFH_MFMA_32x32x16(x2, yx2[ks], tU, 0, 0, 0);
         }
         // lane (column lane & 31, half hi) holds rows 8 i + 4 hi + j of the chunk in register 4 i + j
         unsigned pp[8], dd[8];
@@ -319,8 +319,8 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
           const u32x2_t sd = __builtin_amdgcn_permlane16_swap(dd[e], dd[4 + e], false, false);
           p0v[e] = sp[0]; p1v[e] = sp[1]; d0v[e] = sd[0]; d1v[e] = sd[1];
         }
-        pf[0][ch] = __builtin_bit_cast(bf16x8_t, p0v); pf[1][ch] = __builtin_bit_cast(bf16x8_t, p1v);
-        dsf[0][ch] = __builtin_bit_cast(bf16x8_t, d0v); dsf[1][ch] = __builtin_bit_cast(bf16x8_t, d1v);
+        pf[0][ch] = __builtin_bit_cast(h16x8_t, p0v); pf[1][ch] = __builtin_bit_cast(h16x8_t, p1v);
+        dsf[0][ch] = __builtin_bit_cast(h16x8_t, d0v); dsf[1][ch] = __builtin_bit_cast(h16x8_t, d1v);
       }
     }
 #pragma unroll
@@ -336,12 +336,12 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
         for (int nt = 0; nt < NT; ++nt) { tS[nt][u] = f32x4_t{0.f, 0.f, 0.f, 0.f}; tU[nt][u] = f32x4_t{0.f, 0.f, 0.f, 0.f}; }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          const bf16x8_t x1 = *(const bf16x8_t*)(T1 + row * STR + (((ks * 4 + fg) ^ sw) << 4));
-          const bf16x8_t x2 = *(const bf16x8_t*)(T2 + row * STR + (((ks * 4 + fg) ^ sw) << 4));
+          const h16x8_t x1 = *(const h16x8_t*)(T1 + row * STR + (((ks * 4 + fg) ^ sw) << 4));
+          const h16x8_t x2 = *(const h16x8_t*)(T2 + row * STR + (((ks * 4 + fg) ^ sw) << 4));
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt) {
-            tS[nt][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x1, y1[nt][ks], tS[nt][u], 0, 0, 0);
-            tU[nt][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x2, y2[nt][ks], tU[nt][u], 0, 0, 0);
+            tS[nt][u] = DFH_MFMA_16x16x32(x1, y1[nt][ks], tS[nt][u], 0, 0, 0);
+            tU[nt][u] = DFH_MFMA_16x16x32(x2, y2[nt][ks], tU[nt][u], 0, 0, 0);
           }
         }
       }
@@ -370,8 +370,8 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
         uint4 wp, wd;
         wp.x = pack2bf(p[0], p[1]); wp.y = pack2bf(p[2], p[3]); wp.z = pack2bf(p[4], p[5]); wp.w = pack2bf(p[6], p[7]);
         wd.x = pack2bf(ds[0], ds[1]); wd.y = pack2bf(ds[2], ds[3]); wd.z = pack2bf(ds[4], ds[5]); wd.w = pack2bf(ds[6], ds[7]);
-        pf[nt][ch] = __builtin_bit_cast(bf16x8_t, wp);
-        dsf[nt][ch] = __builtin_bit_cast(bf16x8_t, wd);
+        pf[nt][ch] = __builtin_bit_cast(h16x8_t, wp);
+        dsf[nt][ch] = __builtin_bit_cast(h16x8_t, wd);
       }
     }
     // ---- accumulate  out^T[d][col] += X^T[d][rows] . Z[rows][col]
@@ -379,13 +379,13 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
     for (int f = 0; f < DF; ++f)
 #pragma unroll
       for (int ch = 0; ch < 2; ++ch) {
-        const bf16x8_t a1 = X32 ? tr_frag_x32<STR>(T1, ch * 32 + (((fg & 1) << 4) | ((fg >> 1) << 2)), f * 16, fr) : tr_frag<STR>(T1, ch * 32 + fg * 8, f * 16, fr);
+        const h16x8_t a1 = X32 ? tr_frag_x32<STR>(T1, ch * 32 + (((fg & 1) << 4) | ((fg >> 1) << 2)), f * 16, fr) : tr_frag<STR>(T1, ch * 32 + fg * 8, f * 16, fr);
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc1[nt][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, dsf[nt][ch], acc1[nt][f], 0, 0, 0);
+        for (int nt = 0; nt < NT; ++nt) acc1[nt][f] = DFH_MFMA_16x16x32(a1, dsf[nt][ch], acc1[nt][f], 0, 0, 0);
         if (KV_SIDE) {
-          const bf16x8_t a2 = X32 ? tr_frag_x32<STR>(T2, ch * 32 + (((fg & 1) << 4) | ((fg >> 1) << 2)), f * 16, fr) : tr_frag<STR>(T2, ch * 32 + fg * 8, f * 16, fr);
+          const h16x8_t a2 = X32 ? tr_frag_x32<STR>(T2, ch * 32 + (((fg & 1) << 4) | ((fg >> 1) << 2)), f * 16, fr) : tr_frag<STR>(T2, ch * 32 + fg * 8, f * 16, fr);
 #pragma unroll
-          for (int nt = 0; nt < NT; ++nt) acc2[nt][f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, pf[nt][ch], acc2[nt][f], 0, 0, 0);
+          for (int nt = 0; nt < NT; ++nt) acc2[nt][f] = DFH_MFMA_16x16x32(a2, pf[nt][ch], acc2[nt][f], 0, 0, 0);
         }
       }
     if (more) store_tile((t + 1) & 1);

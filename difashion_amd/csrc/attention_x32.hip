@@ -199,12 +199,12 @@ __global__ __launch_bounds__(256, MINW) void attention_x32_kernel(const AttnArgs
     for (int idx = tid; idx < KVT * (NCH - DCH); idx += 256) {
       const int key = idx / (NCH - DCH), ch = DCH + (idx - key * (NCH - DCH));
       uint4 v = uint4{0u, 0u, 0u, 0u};
-      if (ch == DCH) v.x = key >= first_masked ? 0x3f803f80u : 0x00003f80u;      // {1.0, mask}
+      if (ch == DCH) v.x = key >= first_masked ? DFH_H16_ONE2 : DFH_H16_ONE_LO;      // {1.0, mask}
       *(uint4*)(Ks + key * KROW + ((ch ^ k_swz<KROW>(key)) << 4)) = v;
     }
     if (tid < 16) {
       const int row = D + (tid >> 3), ch = tid & 7;
-      const uint32_t w = row == D ? 0x3f803f80u : 0u;
+      const uint32_t w = row == D ? DFH_H16_ONE2 : 0u;
       *(uint4*)(Vs + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)) = uint4{w, w, w, w};
     }
   };
@@ -224,7 +224,6 @@ __global__ __launch_bounds__(256, MINW) void attention_x32_kernel(const AttnArgs
   f32x16_t o[DB][QB];
   float m_run[QB];
   float l_acc[QB];                                           // LSUM: this lane half's part of the softmax denominator
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v_t;
   auto den = [&](int qb) -> float {                          // the denominator as this lane sees it (the caller combines the halves)
     if constexpr (LSUM) return l_acc[qb];
     else return o[D / 32][qb][G::L_REG];
@@ -299,14 +298,14 @@ __global__ __launch_bounds__(256, MINW) void attention_x32_kernel(const AttnArgs
           const int qb = u & 3, pi = u >> 2;
           pw[kb][qb][pi] = pack2bf(__builtin_amdgcn_exp2f(s[kb][qb][2 * pi]), __builtin_amdgcn_exp2f(s[kb][qb][2 * pi + 1]));
           if constexpr (LSUM)
-            l_acc[qb] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v_t, pw[kb][qb][pi]), __builtin_bit_cast(bf16x2v_t, 0x3f803f80u), l_acc[qb], false);
+            l_acc[qb] = h16_dot2(pw[kb][qb][pi], DFH_H16_ONE2, l_acc[qb]);
         };
         auto fence = [] { __builtin_amdgcn_sched_barrier(0); };
         // S of score block kb, with `units` exponential units of block ekb (from u0 on) spread behind its MFMAs
         auto s_block = [&](int kb, int ekb, int u0, int units) {
-          bf16x8_t kf[KS];
+          h16x8_t kf[KS];
 #pragma unroll
-          for (int ks = 0; ks < KS; ++ks) kf[ks] = *(const bf16x8_t*)(Ks + kb * 32 * KROW + k_off[ks]);
+          for (int ks = 0; ks < KS; ++ks) kf[ks] = *(const h16x8_t*)(Ks + kb * 32 * KROW + k_off[ks]);
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
@@ -315,9 +314,9 @@ __global__ __launch_bounds__(256, MINW) void attention_x32_kernel(const AttnArgs
               // No VALU instruction reads a score block before at least four further MFMAs have issued behind the one that completed
               // it (the pipe is serial: 32 cycles each), so the XDL-write -> VALU-read wait states the compiler cannot see are covered.
               if (ks == 0)
-                asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, 0" : "=&v"(s[kb][qb]) : "v"(kf[ks]), "a"(__builtin_bit_cast(bf16x8_t, qf[qb][ks])));
+                asm volatile(DFH_MFMA_32x32x16_ASM " %0, %1, %2, 0" : "=&v"(s[kb][qb]) : "v"(kf[ks]), "a"(__builtin_bit_cast(h16x8_t, qf[qb][ks])));
               else
-                asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(s[kb][qb]) : "v"(kf[ks]), "a"(__builtin_bit_cast(bf16x8_t, qf[qb][ks])));
+                asm volatile(DFH_MFMA_32x32x16_ASM " %0, %1, %2, %0" : "+v"(s[kb][qb]) : "v"(kf[ks]), "a"(__builtin_bit_cast(h16x8_t, qf[qb][ks])));
               if (units > 0) {
                 fence();
                 const int from = ((ks * QB + qb) * units) / (KS * QB), upto = ((ks * QB + qb + 1) * units) / (KS * QB);
@@ -329,9 +328,9 @@ __global__ __launch_bounds__(256, MINW) void attention_x32_kernel(const AttnArgs
         };
         // P.V of (score block kb, 16-key half m2), with `units` exponential units of block ekb (from u0 on) behind its MFMAs
         auto pv_half = [&](int kb, int m2, int ekb, int u0, int units) {
-          bf16x8_t vf[DB];
+          h16x8_t vf[DB];
 #pragma unroll
-          for (int db = 0; db < DB; ++db) vf[db] = *(const bf16x8_t*)(Vs + v_row[db] + (((kb * 4 + m2 * 2 + hi) ^ v_sw[db]) << 4));
+          for (int db = 0; db < DB; ++db) vf[db] = *(const h16x8_t*)(Vs + v_row[db] + (((kb * 4 + m2 * 2 + hi) ^ v_sw[db]) << 4));
 #pragma unroll
           for (int db = 0; db < DB; ++db)
 #pragma unroll
@@ -341,7 +340,7 @@ __global__ __launch_bounds__(256, MINW) void attention_x32_kernel(const AttnArgs
               // the loop (one denominator register per query block aside), while S^T -- which the exponentials read -- stays in VGPRs.
               // The builtin leaves that choice to one per-function switch; with both accumulator sets in VGPRs the allocator shuffled
               // ~300 v_accvgpr_read / write / mov per tile through the VALU this pipeline is built to keep free.
-              asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(o[db][qb]) : "v"(vf[db]), "v"(__builtin_bit_cast(bf16x8_t, pv)));
+              asm volatile(DFH_MFMA_32x32x16_ASM " %0, %1, %2, %0" : "+a"(o[db][qb]) : "v"(vf[db]), "v"(__builtin_bit_cast(h16x8_t, pv)));
               if (units > 0) {
                 fence();
                 const int from = ((db * QB + qb) * units) / (DB * QB), upto = ((db * QB + qb + 1) * units) / (DB * QB);
@@ -373,16 +372,16 @@ __global__ __launch_bounds__(256, MINW) void attention_x32_kernel(const AttnArgs
       for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          const bf16x8_t kf = *(const bf16x8_t*)(Ks + kb * 32 * KROW + k_off[ks]);
+          const h16x8_t kf = *(const h16x8_t*)(Ks + kb * 32 * KROW + k_off[ks]);
 #pragma unroll
           for (int qb = 0; qb < QB; ++qb) {
             if (ks == 0) {
               f32x16_t z;
 #pragma unroll
               for (int r = 0; r < 16; ++r) z[r] = 0.f;
-              s[kb][qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, __builtin_bit_cast(bf16x8_t, qf[qb][ks]), z, 0, 0, 0);
+              s[kb][qb] = DFH_MFMA_32x32x16(kf, __builtin_bit_cast(h16x8_t, qf[qb][ks]), z, 0, 0, 0);
             } else {
-              s[kb][qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, __builtin_bit_cast(bf16x8_t, qf[qb][ks]), s[kb][qb], 0, 0, 0);
+              s[kb][qb] = DFH_MFMA_32x32x16(kf, __builtin_bit_cast(h16x8_t, qf[qb][ks]), s[kb][qb], 0, 0, 0);
             }
           }
         }
@@ -440,8 +439,7 @@ __global__ __launch_bounds__(256, MINW) void attention_x32_kernel(const AttnArgs
           for (int r = 0; r < 16; r += 2) {
             pw[kb][qb][r >> 1] = pack2bf(__builtin_amdgcn_exp2f(s[kb][qb][r]), __builtin_amdgcn_exp2f(s[kb][qb][r + 1]));
             if constexpr (LSUM)
-              l_acc[qb] = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v_t, pw[kb][qb][r >> 1]), __builtin_bit_cast(bf16x2v_t, 0x3f803f80u),
-                                                          l_acc[qb], false);
+              l_acc[qb] = h16_dot2(pw[kb][qb][r >> 1], DFH_H16_ONE2, l_acc[qb]);
           }
       mark(2);
 #pragma unroll
@@ -450,11 +448,11 @@ __global__ __launch_bounds__(256, MINW) void attention_x32_kernel(const AttnArgs
         for (int m2 = 0; m2 < 2; ++m2)
 #pragma unroll
           for (int db = 0; db < DB; ++db) {
-            const bf16x8_t vf = *(const bf16x8_t*)(Vs + v_row[db] + (((kb * 4 + m2 * 2 + hi) ^ v_sw[db]) << 4));
+            const h16x8_t vf = *(const h16x8_t*)(Vs + v_row[db] + (((kb * 4 + m2 * 2 + hi) ^ v_sw[db]) << 4));
 #pragma unroll
             for (int qb = 0; qb < QB; ++qb) {
               const uint4 pv = uint4{pw[kb][qb][4 * m2], pw[kb][qb][4 * m2 + 1], pw[kb][qb][4 * m2 + 2], pw[kb][qb][4 * m2 + 3]};
-              o[db][qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, __builtin_bit_cast(bf16x8_t, pv), o[db][qb], 0, 0, 0);
+              o[db][qb] = DFH_MFMA_32x32x16(vf, __builtin_bit_cast(h16x8_t, pv), o[db][qb], 0, 0, 0);
             }
           }
       mark(3);
@@ -511,11 +509,17 @@ __global__ __launch_bounds__(256, MINW) void attention_x32_kernel(const AttnArgs
   };
 
 
-  const bool poisoned = pass(std::false_type{});
-  if (__any(poisoned) && lane == 0) *poison_flag = 1u;
-  __syncthreads();
-  if (*poison_flag) {            // workgroup-uniform and essentially never: an in-tile score jump of > 2^100
+  if constexpr (DFH_H16_WIDE_EXPONENT) {
+    const bool poisoned = pass(std::false_type{});
+    if (__any(poisoned) && lane == 0) *poison_flag = 1u;
     __syncthreads();
+    if (*poison_flag) {            // workgroup-uniform and essentially never: an in-tile score jump of > 2^100
+      __syncthreads();
+      (void)pass(std::true_type{});
+    }
+  } else {
+    // a storage type with a 5-bit exponent cannot hold the fast pass's unchecked 2^(s - m): every tile takes the exact
+    // deferred-max form, which keeps the probabilities at or below 2^THR
     (void)pass(std::true_type{});
   }
 
@@ -584,7 +588,7 @@ __global__ __launch_bounds__(256, 2) void attention_xs_kernel(const AttnArgs a, 
     for (int idx = tid; idx < KVT * (NCH - DCH); idx += 256) {
       const int key = idx / (NCH - DCH), ch = DCH + (idx - key * (NCH - DCH));
       uint4 v = uint4{0u, 0u, 0u, 0u};
-      if (ch == DCH) v.x = key >= first_masked ? 0x3f803f80u : 0x00003f80u;      // {1.0, mask}
+      if (ch == DCH) v.x = key >= first_masked ? DFH_H16_ONE2 : DFH_H16_ONE_LO;      // {1.0, mask}
       *(uint4*)(Ks + key * KROW + ((ch ^ k_swz<KROW>(key)) << 4)) = v;
     }
     for (int idx = tid; idx < D * 8; idx += 256) {
@@ -605,7 +609,7 @@ __global__ __launch_bounds__(256, 2) void attention_xs_kernel(const AttnArgs a, 
     }
     if (tid < 16) {
       const int row = D + (tid >> 3), ch = tid & 7;
-      const uint32_t w = row == D ? 0x3f803f80u : 0u;
+      const uint32_t w = row == D ? DFH_H16_ONE2 : 0u;
       *(uint4*)(Vs + row * 128 + ((ch ^ ((row >> 1) & 7)) << 4)) = uint4{w, w, w, w};
     }
   }
@@ -695,16 +699,16 @@ __global__ __launch_bounds__(256, 2) void attention_xs_kernel(const AttnArgs a, 
         }
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          const bf16x8_t kf = *(const bf16x8_t*)(Ks + kb * 32 * KROW + k_off[ks]);
+          const h16x8_t kf = *(const h16x8_t*)(Ks + kb * 32 * KROW + k_off[ks]);
 #pragma unroll
           for (int qb = 0; qb < QB; ++qb) {
             if (ks == 0) {
               f32x16_t z;
 #pragma unroll
               for (int r = 0; r < 16; ++r) z[r] = 0.f;
-              s[kb][qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, __builtin_bit_cast(bf16x8_t, qf[qb][ks]), z, 0, 0, 0);
+              s[kb][qb] = DFH_MFMA_32x32x16(kf, __builtin_bit_cast(h16x8_t, qf[qb][ks]), z, 0, 0, 0);
             } else {
-              s[kb][qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, __builtin_bit_cast(bf16x8_t, qf[qb][ks]), s[kb][qb], 0, 0, 0);
+              s[kb][qb] = DFH_MFMA_32x32x16(kf, __builtin_bit_cast(h16x8_t, qf[qb][ks]), s[kb][qb], 0, 0, 0);
             }
           }
         }
@@ -764,11 +768,11 @@ __global__ __launch_bounds__(256, 2) void attention_xs_kernel(const AttnArgs a, 
         for (int m2 = 0; m2 < 2; ++m2)
 #pragma unroll
           for (int db = 0; db < DB; ++db) {
-            const bf16x8_t vf = *(const bf16x8_t*)(Vs + v_row[db] + (((kb * 4 + m2 * 2 + hi) ^ v_sw[db]) << 4));
+            const h16x8_t vf = *(const h16x8_t*)(Vs + v_row[db] + (((kb * 4 + m2 * 2 + hi) ^ v_sw[db]) << 4));
 #pragma unroll
             for (int qb = 0; qb < QB; ++qb) {
               const uint4 pv = uint4{pw[kb][qb][4 * m2], pw[kb][qb][4 * m2 + 1], pw[kb][qb][4 * m2 + 2], pw[kb][qb][4 * m2 + 3]};
-              o[db][qb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, __builtin_bit_cast(bf16x8_t, pv), o[db][qb], 0, 0, 0);
+              o[db][qb] = DFH_MFMA_32x32x16(vf, __builtin_bit_cast(h16x8_t, pv), o[db][qb], 0, 0, 0);
             }
           }
       }

@@ -1,37 +1,92 @@
 // Shared device/host helpers for the DiFashion gfx950 kernels.
 // Layout conventions (DESIGN.md "Data layout in HBM"):
-//   activations  : bf16, NHWC == [B][H*W][C] token-major (so convs, 1x1 convs and the
+//   activations  : the 16-bit storage type (bf16; fp16 under -DDFH_F16), NHWC == [B][H*W][C] token-major (so convs, 1x1 convs and the
 //                  transformer linears all see the same row-major [M][K] A operand)
-//   GEMM weights : bf16, [N][K] row-major (K contiguous); conv3x3 K index = (ky*3+kx)*Cin + c
+//   GEMM weights : storage type, [N][K] row-major (K contiguous); conv3x3 K index = (ky*3+kx)*Cin + c
 //   bias / temb  : fp32
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-typedef uint16_t bf16_t;  // raw bf16 bits
+// The 16-bit storage type of activations and packed weights is a property of the BUILD: bf16 by default, IEEE fp16 under
+// -DDFH_F16 (libdifashion_hip_f16.so).  Kernel sources never name either: they use bf16_t (raw storage bits, historic name),
+// h16x8_t (an MFMA operand fragment), bf2f / f2bf / pack2bf / h16lo / h16hi (conversions), DFH_MFMA_* (one alias per MFMA shape;
+// the operand layouts of the two types are the same) and the DFH_H16_* constants below.
+typedef uint16_t bf16_t;  // raw bits of the storage type
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
+typedef __attribute__((ext_vector_type(2))) float f32x2_t;
 
 #define DFH_DEVICE __device__ __forceinline__
 
-DFH_DEVICE float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
+#ifdef DFH_F16
+#define DFH_STORAGE_NAME "fp16"
+typedef __attribute__((ext_vector_type(8))) _Float16 h16x8_t;
+typedef __attribute__((ext_vector_type(2))) _Float16 h16x2_t;
+#define DFH_MFMA_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_f16
+#define DFH_MFMA_32x32x16 __builtin_amdgcn_mfma_f32_32x32x16_f16
+#define DFH_MFMA_16x16x32_ASM "v_mfma_f32_16x16x32_f16"
+#define DFH_MFMA_32x32x16_ASM "v_mfma_f32_32x32x16_f16"
+#define DFH_H16_ONE 0x3C00            // 1.0
+#define DFH_H16_ONE2 0x3c003c00u      // {1.0, 1.0}
+#define DFH_H16_ONE_LO 0x00003c00u    // {1.0, 0.0}
+// 5 exponent bits: a kernel may not park unchecked powers of two in this type (attention_x32.hip's fast softmax pass)
+constexpr bool DFH_H16_WIDE_EXPONENT = false;
+constexpr float DFH_H16_MAX = 65504.0f;
 
+DFH_DEVICE float bf2f(bf16_t v) { return (float)__builtin_bit_cast(_Float16, v); }
+DFH_DEVICE float h16lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)w); }
+DFH_DEVICE float h16hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
+// fp32 -> fp16, round-to-nearest-even (gfx950: v_cvt_pk_f16_f32, one instruction per pair).  Values beyond the largest finite
+// fp16 (+-inf included) SATURATE to +-65504 instead of becoming inf: one v_med3_f32 in front of the convert.  v_med3_f32 answers
+// min3 when an operand is NaN, which would launder a NaN into -65504, so a NaN is selected back in (v_cmp_u_f32 + v_cndmask_b32):
+// NaN stays NaN, as in the bf16 library (tests/test_fp16_build_cpu.py checks the folded constants).
+DFH_DEVICE float h16_sat(float f) {
+  const float c = __builtin_amdgcn_fmed3f(f, -DFH_H16_MAX, DFH_H16_MAX);
+  return f != f ? f : c;
+}
+DFH_DEVICE bf16_t f2bf(float f) { return __builtin_bit_cast(bf16_t, (_Float16)h16_sat(f)); }
+DFH_DEVICE uint32_t pack2bf(float lo, float hi) {
+  const f32x2_t v = {h16_sat(lo), h16_sat(hi)};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, h16x2_t));
+}
+// c + a.lo * b.lo + a.hi * b.hi on a packed pair (v_dot2_f32_f16)
+DFH_DEVICE float h16_dot2(uint32_t a, uint32_t b, float c) {
+  return __builtin_amdgcn_fdot2(__builtin_bit_cast(h16x2_t, a), __builtin_bit_cast(h16x2_t, b), c, false);
+}
+#else
+#define DFH_STORAGE_NAME "bf16"
+typedef __attribute__((ext_vector_type(8))) __bf16 h16x8_t;
+typedef __attribute__((ext_vector_type(2))) __bf16 h16x2_t;
+#define DFH_MFMA_16x16x32 __builtin_amdgcn_mfma_f32_16x16x32_bf16
+#define DFH_MFMA_32x32x16 __builtin_amdgcn_mfma_f32_32x32x16_bf16
+#define DFH_MFMA_16x16x32_ASM "v_mfma_f32_16x16x32_bf16"
+#define DFH_MFMA_32x32x16_ASM "v_mfma_f32_32x32x16_bf16"
+#define DFH_H16_ONE 0x3F80            // 1.0
+#define DFH_H16_ONE2 0x3f803f80u      // {1.0, 1.0}
+#define DFH_H16_ONE_LO 0x00003f80u    // {1.0, 0.0}
+constexpr bool DFH_H16_WIDE_EXPONENT = true;      // the exponent range of fp32
+
+DFH_DEVICE float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
+DFH_DEVICE float h16lo(uint32_t w) { return __uint_as_float(w << 16); }
+DFH_DEVICE float h16hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 // fp32 -> bf16, round-to-nearest-even, through the native __bf16 conversion: hipcc lowers it to
 // gfx950's v_cvt_pk_bf16_f32 (one instruction per PAIR; a hand-rolled RNE costs ~8 VALU + a NaN branch)
-typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 DFH_DEVICE bf16_t f2bf(float f) { return __builtin_bit_cast(bf16_t, (__bf16)f); }
 DFH_DEVICE uint32_t pack2bf(float lo, float hi) {
   const f32x2_t v = {lo, hi};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, h16x2_t));
 }
+DFH_DEVICE float h16_dot2(uint32_t a, uint32_t b, float c) {
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(h16x2_t, a), __builtin_bit_cast(h16x2_t, b), c, false);
+}
+#endif
 
 DFH_DEVICE void unpack8(const uint4& v, float* f) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
+  f[0] = h16lo(v.x); f[1] = h16hi(v.x);
+  f[2] = h16lo(v.y); f[3] = h16hi(v.y);
+  f[4] = h16lo(v.z); f[5] = h16hi(v.z);
+  f[6] = h16lo(v.w); f[7] = h16hi(v.w);
 }
 
 DFH_DEVICE uint4 pack8(const float* f) {
@@ -218,6 +273,20 @@ struct ProfScope {
       return -1;                                                 \
     }                                                            \
   } while (0)
+
+// Entry points the fp16-storage library refuses (they still compile and export their symbols): EVERY entry point that exists only
+// for the training step -- forward-for-backward, backward, gradient un-pack / norms / wire, loss gradient, optimizer and EMA, the
+// pure-fp32 ones included, and the size queries of the training arenas (those answer 0) -- since training stays bf16 (there is no
+// loss scaling); and the e4m3 legs, whose quantising epilogues are calibrated against bf16 producers.
+#ifdef DFH_F16
+#define DFH_BF16_ONLY_TRAINING_SIZE do { dfh::set_error(std::string(__func__) + ": refused by the fp16-storage library: training entry points are bf16 only; unset DFH_STORAGE"); return 0; } while (0)
+#define DFH_BF16_ONLY_TRAINING DFH_REQUIRE(false, "refused by the fp16-storage library: training / backward / optimizer entry points are bf16 only (no loss scaling); unset DFH_STORAGE")
+#define DFH_BF16_ONLY_FP8 DFH_REQUIRE(false, "refused by the fp16-storage library: the fp8 (e4m3) legs are calibrated against bf16 producers; unset DFH_STORAGE")
+#else
+#define DFH_BF16_ONLY_TRAINING
+#define DFH_BF16_ONLY_TRAINING_SIZE
+#define DFH_BF16_ONLY_FP8
+#endif
 
 // Bijective XCD-aware remap of a linear block id (guide T1): consecutive logical tiles land on
 // the same XCD (= same L2), so neighbouring tiles that share an A row panel or a W column panel

@@ -364,23 +364,23 @@ void gemm_bf16_kernel(const GemmArgs a) {
       const unsigned char* Bs = As + A_BYTES;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        bf16x8_t af[FM], bfr[FN];
+        h16x8_t af[FM], bfr[FN];
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
           const int row = wm * TM + i * 16 + fr;
-          af[i] = *(const bf16x8_t*)(As + row * 128 + (((ks * 4 + fg) ^ ((row >> 1) & 7)) << 4));
+          af[i] = *(const h16x8_t*)(As + row * 128 + (((ks * 4 + fg) ^ ((row >> 1) & 7)) << 4));
         }
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
           const int row = wn * TN + j * 16 + fr;
-          bfr[j] = *(const bf16x8_t*)(Bs + row * 128 + (((ks * 4 + fg) ^ ((row >> 1) & 7)) << 4));
+          bfr[j] = *(const h16x8_t*)(Bs + row * 128 + (((ks * 4 + fg) ^ ((row >> 1) & 7)) << 4));
         }
 #pragma unroll
         for (int i = 0; i < FM; ++i)
 #pragma unroll
           for (int j = 0; j < FN; ++j)
             // weights as MFMA-A: D[row = channel (fg*4+r)][col = pixel (fr)]
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
+            acc[i][j] = DFH_MFMA_16x16x32(bfr[j], af[i], acc[i][j], 0, 0, 0);
       }
       if (++buf == NSTAGE) buf = 0;
     }
@@ -503,8 +503,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
         }
         if (a.resid) {
           const uint2 rr = rpre[i][j];
-          v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-          v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+          v[0] += h16lo(rr.x); v[1] += h16hi(rr.x);
+          v[2] += h16lo(rr.y); v[3] += h16hi(rr.y);
         }
         if (tr) {
 #pragma unroll
@@ -713,8 +713,8 @@ void gemm_bf16_kernel(const GemmArgs a) {
       }
       if (a.resid) {
         const uint2 rr = *(const uint2*)(a.resid + (long)m * a.ld_res + n);
-        v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-        v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+        v[0] += h16lo(rr.x); v[1] += h16hi(rr.x);
+        v[2] += h16lo(rr.y); v[3] += h16hi(rr.y);
       }
       if (omode == OUT_BF16) {
         uint2 o; o.x = pack2bf(v[0], v[1]); o.y = pack2bf(v[2], v[3]);
@@ -763,8 +763,8 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce(const GemmArgs a) {
   else if (a.act == ACT_TANH) { for (int r = 0; r < 4; ++r) v[r] = tanhf(v[r]); }
   if (a.resid) {
     const uint2 rr = *(const uint2*)(a.resid + (long)m * a.ld_res + n);
-    v[0] += __uint_as_float(rr.x << 16); v[1] += __uint_as_float(rr.x & 0xffff0000u);
-    v[2] += __uint_as_float(rr.y << 16); v[3] += __uint_as_float(rr.y & 0xffff0000u);
+    v[0] += h16lo(rr.x); v[1] += h16hi(rr.x);
+    v[2] += h16lo(rr.y); v[3] += h16hi(rr.y);
   }
   if (a.out_mode == OUT_BF16) {
     uint2 o; o.x = pack2bf(v[0], v[1]); o.y = pack2bf(v[2], v[3]);

@@ -328,8 +328,8 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8GemmArgs a) {
           v[4 * g + 2] = acc[ci][pj][4 * g + 2] * sa * sw4.z + b4.z; v[4 * g + 3] = acc[ci][pj][4 * g + 3] * sa * sw4.w + b4.w;
           if (a.resid && m_ok && n < a.N) {
             const uint2 rr = *(const uint2*)(a.resid + (long)m * a.ld_res + n);
-            v[4 * g] += __uint_as_float(rr.x << 16); v[4 * g + 1] += __uint_as_float(rr.x & 0xffff0000u);
-            v[4 * g + 2] += __uint_as_float(rr.y << 16); v[4 * g + 3] += __uint_as_float(rr.y & 0xffff0000u);
+            v[4 * g] += h16lo(rr.x); v[4 * g + 1] += h16hi(rr.x);
+            v[4 * g + 2] += h16lo(rr.y); v[4 * g + 3] += h16hi(rr.y);
           }
         }
         if (!out8) {

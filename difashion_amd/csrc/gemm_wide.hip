@@ -255,7 +255,7 @@ __global__ __launch_bounds__(WN * 128, WN == 2 ? 2 : 1) void gemm_wide_kernel(co
       else asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(a0));
 #define WROW(i, ar)                                                                                                    \
       if constexpr (!(ABL & 4)) _Pragma("unroll") for (int j = 0; j < FN; ++j)                                        \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, b[j]), __builtin_bit_cast(bf16x8_t, ar), \
+        acc[i][j] = DFH_MFMA_16x16x32(__builtin_bit_cast(h16x8_t, b[j]), __builtin_bit_cast(h16x8_t, ar), \
                                                             acc[i][j], 0, 0, 0);
 #define WNEXT(rd, off, wt) WRD(rd, sa, off); asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(wt));
       // weights as MFMA-A: D[row = channel (fg*4+r)][col = pixel (fr)]

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(512, 2) void mlp2_fused_kernel(const MlpArgs a) {
   {
     const bf16_t* xr = a.x + (long)m * MC + 8 * g;                   // X fragments: token m, k = 32 ks + 8 g .. + 7
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) st.xf[ks] = *(const bf16x8_t*)(xr + 32 * ks);
+    for (int ks = 0; ks < KS; ++ks) st.xf[ks] = *(const h16x8_t*)(xr + 32 * ks);
   }
   {
     GemmArgs gg; gg.ln_stat = a.ln_stat; gg.ln_parts = a.ln_parts; gg.ln_cnt = a.ln_cnt; gg.ln_eps = a.ln_eps; gg.M = a.M;
@@ -139,8 +139,8 @@ __global__ __launch_bounds__(512, 2) void mlp2_fused_kernel(const MlpArgs a) {
     const int n = 16 * ct + 4 * g2;
     const float4 b4 = *(const float4*)(a.bias + n);
     const uint2 rr = *(const uint2*)(a.resid + row + n);
-    const float v0 = st.d2[ct][0] + b4.x + __uint_as_float(rr.x << 16), v1 = st.d2[ct][1] + b4.y + __uint_as_float(rr.x & 0xffff0000u);
-    const float v2 = st.d2[ct][2] + b4.z + __uint_as_float(rr.y << 16), v3 = st.d2[ct][3] + b4.w + __uint_as_float(rr.y & 0xffff0000u);
+    const float v0 = st.d2[ct][0] + b4.x + h16lo(rr.x), v1 = st.d2[ct][1] + b4.y + h16hi(rr.x);
+    const float v2 = st.d2[ct][2] + b4.z + h16lo(rr.y), v3 = st.d2[ct][3] + b4.w + h16hi(rr.y);
     uint2 o; o.x = pack2bf(v0, v1); o.y = pack2bf(v2, v3);
     *(uint2*)(a.out + row + n) = o;
     // the rounded tile also goes to LDS (the weight ring is dead: every wave passed the last iteration's barrier) for the statistics below

@@ -26,7 +26,7 @@ DFH_DEVICE void fence() { __builtin_amdgcn_sched_barrier(0); }
 struct Mlp2State {
   f32x4_t d1[2][4];           // [chunk parity][tile v0, g0, v1, g1]: first-GEMM accumulators (VGPRs: the GEGLU reads them)
   f32x4_t d2[CT];             // output accumulators
-  bf16x8_t xf[KS];            // X fragments (the MFMA B operand of the first GEMM and of the h2 segment)
+  h16x8_t xf[KS];            // X fragments (the MFMA B operand of the first GEMM and of the h2 segment)
   u32x4_t hreg;               // B operand of the second GEMM: the gated 32 hidden units of the previous chunk
   float rstd, ms;
   GeluK gk;
@@ -123,23 +123,23 @@ DFH_DEVICE void mlp2_iter(Mlp2State& st, const unsigned char* smem, const unsign
     asm volatile("" : "+s"(base));
     return *(gptr16_t)(base + lane16);
   };
-  bf16x8_t fr[WIN];
+  h16x8_t fr[WIN];
 #pragma unroll
-  for (int i = 0; i < WIN; ++i) fr[i] = *(const __attribute__((address_space(3))) bf16x8_t*)lds(g1_off(i));
+  for (int i = 0; i < WIN; ++i) fr[i] = *(const __attribute__((address_space(3))) h16x8_t*)lds(g1_off(i));
   fence();
 #pragma unroll
   for (int i = 0; i < 40; ++i) {
     if (KIND == 0) {
       const int t = i & 3, ks = i >> 2;
-      if (ks == 0) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(st.d1[PAR][t]) : "v"(fr[i % WIN]), "v"(st.xf[ks]));
-      else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(st.d1[PAR][t]) : "v"(fr[i % WIN]), "v"(st.xf[ks]));
+      if (ks == 0) asm volatile(DFH_MFMA_16x16x32_ASM " %0, %1, %2, 0" : "=&v"(st.d1[PAR][t]) : "v"(fr[i % WIN]), "v"(st.xf[ks]));
+      else asm volatile(DFH_MFMA_16x16x32_ASM " %0, %1, %2, %0" : "+v"(st.d1[PAR][t]) : "v"(fr[i % WIN]), "v"(st.xf[ks]));
     } else {
       const int ct = i % CT, kk = i / CT;
-      asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(st.d2[ct]) : "v"(fr[i % WIN]), "v"(st.xf[2 * Q + kk]));
+      asm volatile(DFH_MFMA_16x16x32_ASM " %0, %1, %2, %0" : "+v"(st.d2[ct]) : "v"(fr[i % WIN]), "v"(st.xf[2 * Q + kk]));
     }
     fence();
-    if (i + WIN < 40) fr[i % WIN] = *(const __attribute__((address_space(3))) bf16x8_t*)lds(g1_off(i + WIN));
-    else if (PREV) fr[i % WIN] = *(const __attribute__((address_space(3))) bf16x8_t*)lds(g2_off(i + WIN - 40));
+    if (i + WIN < 40) fr[i % WIN] = *(const __attribute__((address_space(3))) h16x8_t*)lds(g1_off(i + WIN));
+    else if (PREV) fr[i % WIN] = *(const __attribute__((address_space(3))) h16x8_t*)lds(g2_off(i + WIN - 40));
     if (PREV && (i & 1) == 0) geglu_slice2<PP>(st, vb, (i >> 1) / 5, (i >> 1) % 5);
     // the wave's eight pieces: ALL requested behind the first sixteen MFMAs (eight 16-byte loads per lane = 64 KB per CU in flight), written
     // to LDS behind the last sixteen.  With two staging registers (16 KB per CU in flight) an iteration took ~6000 cycles whatever it
@@ -152,9 +152,9 @@ DFH_DEVICE void mlp2_iter(Mlp2State& st, const unsigned char* smem, const unsign
     asm volatile("s_nop 1" ::: "memory");                  // the gated hidden units are VALU results read by the MFMAs below
 #pragma unroll
     for (int j = 0; j < CT; ++j) {
-      asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(st.d2[j]) : "v"(fr[(40 + j) % WIN]), "v"(__builtin_bit_cast(bf16x8_t, st.hreg)));
+      asm volatile(DFH_MFMA_16x16x32_ASM " %0, %1, %2, %0" : "+v"(st.d2[j]) : "v"(fr[(40 + j) % WIN]), "v"(__builtin_bit_cast(h16x8_t, st.hreg)));
       fence();
-      if (j + WIN < CT) fr[(40 + j) % WIN] = *(const __attribute__((address_space(3))) bf16x8_t*)lds(g2_off(j + WIN));
+      if (j + WIN < CT) fr[(40 + j) % WIN] = *(const __attribute__((address_space(3))) h16x8_t*)lds(g2_off(j + WIN));
       fence();
     }
   }

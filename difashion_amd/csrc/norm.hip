@@ -301,8 +301,8 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const GnArgs a) {
       const int p = idx / upp, j = idx - p * upp;
       pix[u] = p; ch[u] = j * 4;
       const uint2 r = *(const uint2*)(src + (long)p * ldc + j * 4);
-      v[u][0] = __uint_as_float(r.x << 16); v[u][1] = __uint_as_float(r.x & 0xffff0000u);
-      v[u][2] = __uint_as_float(r.y << 16); v[u][3] = __uint_as_float(r.y & 0xffff0000u);
+      v[u][0] = h16lo(r.x); v[u][1] = h16hi(r.x);
+      v[u][2] = h16lo(r.y); v[u][3] = h16hi(r.y);
       s += (v[u][0] + v[u][1]) + (v[u][2] + v[u][3]);
     }
   }
@@ -387,8 +387,8 @@ __global__ __launch_bounds__(MAXT) void gn_mid_kernel(const GnArgs a, const int 
   }
 #pragma unroll
   for (int u = 0; u < UNITS; ++u)      // out-of-range units hold zeros: they add nothing here and are masked in the second pass
-    s += (__uint_as_float(v[u].x << 16) + __uint_as_float(v[u].x & 0xffff0000u)) +
-         (__uint_as_float(v[u].y << 16) + __uint_as_float(v[u].y & 0xffff0000u));
+    s += (h16lo(v[u].x) + h16hi(v[u].x)) +
+         (h16lo(v[u].y) + h16hi(v[u].y));
   const float n = (float)a.HW * (float)cpg;
   const int gi = j / upp;                                       // group of this thread inside the block
   auto group_total = [&](float x, int slot) -> float {
@@ -409,8 +409,8 @@ __global__ __launch_bounds__(MAXT) void gn_mid_kernel(const GnArgs a, const int 
 #pragma unroll
   for (int u = 0; u < UNITS; ++u) {
     if (pp + u * ppb < a.HW) {
-      const float d0 = __uint_as_float(v[u].x << 16) - mean, d1 = __uint_as_float(v[u].x & 0xffff0000u) - mean;
-      const float d2 = __uint_as_float(v[u].y << 16) - mean, d3 = __uint_as_float(v[u].y & 0xffff0000u) - mean;
+      const float d0 = h16lo(v[u].x) - mean, d1 = h16hi(v[u].x) - mean;
+      const float d2 = h16lo(v[u].y) - mean, d3 = h16hi(v[u].y) - mean;
       q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
     }
   }
@@ -426,8 +426,8 @@ __global__ __launch_bounds__(MAXT) void gn_mid_kernel(const GnArgs a, const int 
   for (int u = 0; u < UNITS; ++u) {
     const int p = pp + u * ppb;
     if (p < a.HW) {
-      float y[4] = {(__uint_as_float(v[u].x << 16) - mean) * w0 + bt.x, (__uint_as_float(v[u].x & 0xffff0000u) - mean) * w1 + bt.y,
-                    (__uint_as_float(v[u].y << 16) - mean) * w2 + bt.z, (__uint_as_float(v[u].y & 0xffff0000u) - mean) * w3 + bt.w};
+      float y[4] = {(h16lo(v[u].x) - mean) * w0 + bt.x, (h16hi(v[u].x) - mean) * w1 + bt.y,
+                    (h16lo(v[u].y) - mean) * w2 + bt.z, (h16hi(v[u].y) - mean) * w3 + bt.w};
       if (a.silu) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) y[k] = silu_f(y[k]);

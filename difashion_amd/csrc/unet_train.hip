@@ -844,17 +844,19 @@ int dfh_unet::pack_all(const float* const* master, int count, hipStream_t s) {
 // ------------------------------------------------------------------------------------------- C ABI
 extern "C" {
 
-size_t dfh_unet_arena16t_bytes(dfh_unet* u) { u->build_train(); return u->a16t * 2 + 256; }
-size_t dfh_unet_grad16_bytes(const dfh_unet* u) { return u->a16 * 4 + 256; }
-size_t dfh_unet_grad32_bytes(const dfh_unet* u) { return u->a32 * 4 + 256; }
+size_t dfh_unet_arena16t_bytes(dfh_unet* u) { DFH_BF16_ONLY_TRAINING_SIZE; u->build_train(); return u->a16t * 2 + 256; }
+size_t dfh_unet_grad16_bytes(const dfh_unet* u) { DFH_BF16_ONLY_TRAINING_SIZE; return u->a16 * 4 + 256; }
+size_t dfh_unet_grad32_bytes(const dfh_unet* u) { DFH_BF16_ONLY_TRAINING_SIZE; return u->a32 * 4 + 256; }
 
 size_t dfh_unet_train_workspace_bytes(dfh_unet* u, int batch) {
+  DFH_BF16_ONLY_TRAINING_SIZE;
   if (batch <= 0) return 0;
   return u->plan_train(batch);
 }
 
 int dfh_unet_bind_train(dfh_unet* u, void* arena16t, void* grad16, void* grad32, void* workspace, size_t workspace_bytes,
                         int max_batch) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(u && arena16t && grad16 && grad32 && workspace, "null argument");
   DFH_REQUIRE(((uintptr_t)arena16t | (uintptr_t)grad16 | (uintptr_t)grad32 | (uintptr_t)workspace) % 256 == 0,
               "buffers must be 256-byte aligned");
@@ -866,11 +868,13 @@ int dfh_unet_bind_train(dfh_unet* u, void* arena16t, void* grad16, void* grad32,
 }
 
 int dfh_unet_pack_train(dfh_unet* u, const float* const* master_params, int count, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(u && master_params, "null argument");
   return u->pack_train(master_params, count, (hipStream_t)stream);
 }
 
 int dfh_unet_grad_sumsq(dfh_unet* u, float* out) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(u, "null argument");
   u->grad_sumsq_out = out;          // null un-registers: the un-pack then writes no norm (and keeps no pointer into caller memory)
   if (out && !u->sq_scratch) {      // ticket counter + block partials: allocated and zeroed HERE, outside any step
@@ -888,6 +892,7 @@ int dfh_unet_grad_sumsq(dfh_unet* u, float* out) {
 }
 
 int dfh_unet_pack_all(dfh_unet* u, const float* const* master_params, int count, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(u && master_params, "null argument");
   u->build_train();
   return u->pack_all(master_params, count, (hipStream_t)stream);
@@ -895,6 +900,7 @@ int dfh_unet_pack_all(dfh_unet* u, const float* const* master_params, int count,
 
 int dfh_unet_forward_train(dfh_unet* u, const void* sample, int sample_bf16, const float* timestep, const void* ehs, int ehs_bf16,
                            float* out, int batch, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   if (u) u->dup_tail = 0;          // the guidance-batch hint is an inference-walk hint: a training forward never consumes it and never leaves it behind
   DFH_REQUIRE(u && sample && timestep && ehs && out, "null argument");
   DFH_REQUIRE(u->tws != nullptr, "dfh_unet_bind_train not called");
@@ -904,19 +910,23 @@ int dfh_unet_forward_train(dfh_unet* u, const void* sample, int sample_bf16, con
 
 int dfh_unet_backward(dfh_unet* u, const float* d_out, float* d_sample, float* const* master_grads, int count, int overwrite,
                       void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(u && d_out, "null argument");
   return u->backward(d_out, d_sample, master_grads, count, (hipStream_t)stream, overwrite ? 1 : 0);
 }
 
 int dfh_unet_backward_begin(dfh_unet* u, const float* d_out, float* d_sample, size_t bucket_floats, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(u && d_out, "null argument");
   return u->backward_begin(d_out, d_sample, bucket_floats, (hipStream_t)stream);
 }
 int dfh_unet_backward_next(dfh_unet* u, size_t* lo, size_t* hi, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(u, "null argument");
   return u->backward_next(lo, hi, (hipStream_t)stream);
 }
 int dfh_unet_backward_finish(dfh_unet* u, float* const* master_grads, int count, int overwrite, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
   DFH_REQUIRE(u, "null argument");
   return u->backward_finish(master_grads, count, (hipStream_t)stream, overwrite ? 1 : 0);
 }

@@ -38,10 +38,10 @@ typedef __attribute__((ext_vector_type(2))) unsigned u32x2_t;
     "+v"(f[2][0]), "+v"(f[2][1]), "+v"(f[3][0]), "+v"(f[3][1]), "+v"(f[4][0]), "+v"(f[4][1]) : "n"(N))
 #define LGKM_WAIT1(N, f) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f[0]), "+v"(f[1]) : "n"(N))
 
-DFH_DEVICE bf16x8_t frag_of(const u32x2_t lo, const u32x2_t hi) {
+DFH_DEVICE h16x8_t frag_of(const u32x2_t lo, const u32x2_t hi) {
   typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
   const u32x4_t v = {lo[0], lo[1], hi[0], hi[1]};
-  return __builtin_bit_cast(bf16x8_t, v);
+  return __builtin_bit_cast(h16x8_t, v);
 }
 template <int N> DFH_DEVICE void wg_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // x / d for 0 <= x < 2^24 through a float reciprocal (exact after one fix-up step)
@@ -168,7 +168,7 @@ DFH_DEVICE void wgrad_piece(const WgradArgs& a, unsigned char* smem, const int b
 #pragma unroll
   for (int j = 0; j < 5; ++j) accb[j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   typedef __attribute__((ext_vector_type(8))) unsigned short u16x8_t;
-  const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, u16x8_t{0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80});
+  const h16x8_t ones = __builtin_bit_cast(h16x8_t, u16x8_t{DFH_H16_ONE, DFH_H16_ONE, DFH_H16_ONE, DFH_H16_ONE, DFH_H16_ONE, DFH_H16_ONE, DFH_H16_ONE, DFH_H16_ONE});
 
   if (nsteps > 0) {
     int issued = 0;
@@ -196,18 +196,18 @@ DFH_DEVICE void wgrad_piece(const WgradArgs& a, unsigned char* smem, const int b
       TR_PAIR(x, aa, 0); TR_PAIR(x, aa, 1); TR_PAIR(x, aa, 2); TR_PAIR(x, aa, 3); TR_PAIR(x, aa, 4);
 #undef TR_PAIR
       LGKM_WAIT5(10, y);                              // the ten dY reads are back (LDS returns in order)
-      bf16x8_t yf[5];
+      h16x8_t yf[5];
 #pragma unroll
       for (int nf = 0; nf < 5; ++nf) yf[nf] = frag_of(y[nf][0], y[nf][1]);
       if (do_bias) {                                  // column sums of dY = a row of ones as the A operand
 #pragma unroll
-        for (int nf = 0; nf < 5; ++nf) accb[nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, yf[nf], accb[nf], 0, 0, 0);
+        for (int nf = 0; nf < 5; ++nf) accb[nf] = DFH_MFMA_16x16x32(ones, yf[nf], accb[nf], 0, 0, 0);
       }
 #define WG_ROW(kf, N)                                                                                        \
       LGKM_WAIT1(N, x[kf]);                                                                                  \
-      { const bf16x8_t af = frag_of(x[kf][0], x[kf][1]);                                                      \
+      { const h16x8_t af = frag_of(x[kf][0], x[kf][1]);                                                      \
         _Pragma("unroll") for (int nf = 0; nf < 5; ++nf)                                                      \
-          acc[kf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, yf[nf], acc[kf][nf], 0, 0, 0); }
+          acc[kf][nf] = DFH_MFMA_16x16x32(af, yf[nf], acc[kf][nf], 0, 0, 0); }
       // D^T[row = kcol (fg*4+r)][col = n (L)]
       WG_ROW(0, 8) WG_ROW(1, 6) WG_ROW(2, 4) WG_ROW(3, 2) WG_ROW(4, 0)
 #undef WG_ROW

@@ -141,8 +141,8 @@ __global__ __launch_bounds__(256) void gn_wino_input_kernel(const GnWinoArgs a) 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const uint2 r = *(const uint2*)(a.Mprev + ((long)(i * 4 + jj) * Mtp + (long)b * tilesp + t) * a.C0 + c);
-          m[i][0] = __uint_as_float(r.x << 16); m[i][1] = __uint_as_float(r.x & 0xffff0000u);
-          m[i][2] = __uint_as_float(r.y << 16); m[i][3] = __uint_as_float(r.y & 0xffff0000u);
+          m[i][0] = h16lo(r.x); m[i][1] = h16hi(r.x);
+          m[i][2] = h16lo(r.y); m[i][3] = h16hi(r.y);
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void gn_wino_input_kernel(const GnWinoArgs a) 
           uint2 r; r.x = pack2bf(y[0], y[1]); r.y = pack2bf(y[2], y[3]);
           const int p = (2 * ty + i) * a.W + 2 * tx + jj;
           *(uint2*)(smem + p * RS + j * 8) = r;
-          s += (__uint_as_float(r.x << 16) + __uint_as_float(r.x & 0xffff0000u)) + (__uint_as_float(r.y << 16) + __uint_as_float(r.y & 0xffff0000u));
+          s += (h16lo(r.x) + h16hi(r.x)) + (h16lo(r.y) + h16hi(r.y));
         }
     }
   } else
@@ -176,7 +176,7 @@ __global__ __launch_bounds__(256) void gn_wino_input_kernel(const GnWinoArgs a) 
     const uint2 r = c < a.C0 ? *(const uint2*)(a.src0 + ((long)b * HW + p) * a.C0 + c)
                              : *(const uint2*)(a.src1 + ((long)b * HW + p) * a.C1 + (c - a.C0));
     *(uint2*)(smem + p * RS + j * 8) = r;
-    s += (__uint_as_float(r.x << 16) + __uint_as_float(r.x & 0xffff0000u)) + (__uint_as_float(r.y << 16) + __uint_as_float(r.y & 0xffff0000u));
+    s += (h16lo(r.x) + h16hi(r.x)) + (h16lo(r.y) + h16hi(r.y));
   }
   s = wave_sum(s);
   if ((tid & 63) == 0) red[tid >> 6] = s;
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void gn_wino_input_kernel(const GnWinoArgs a) 
   for (int idx = tid; idx < total; idx += 256) {
     const int p = idx / upp, j = idx - p * upp;
     const uint2 r = *(const uint2*)(smem + p * RS + j * 8);
-    const float v[4] = {__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
+    const float v[4] = {h16lo(r.x), h16hi(r.x), h16lo(r.y), h16hi(r.y)};
 #pragma unroll
     for (int k = 0; k < 4; ++k) { const float d = v[k] - mean; q += d * d; }
   }
@@ -202,10 +202,10 @@ __global__ __launch_bounds__(256) void gn_wino_input_kernel(const GnWinoArgs a) 
     uint2* slot = (uint2*)(smem + p * RS + j * 8);
     const uint2 r = *slot;
     const float4 gm = *(const float4*)(gam_s + j * 4), bt = *(const float4*)(bet_s + j * 4);
-    const float y0 = silu_f((__uint_as_float(r.x << 16) - mean) * rstd * gm.x + bt.x);
-    const float y1 = silu_f((__uint_as_float(r.x & 0xffff0000u) - mean) * rstd * gm.y + bt.y);
-    const float y2 = silu_f((__uint_as_float(r.y << 16) - mean) * rstd * gm.z + bt.z);
-    const float y3 = silu_f((__uint_as_float(r.y & 0xffff0000u) - mean) * rstd * gm.w + bt.w);
+    const float y0 = silu_f((h16lo(r.x) - mean) * rstd * gm.x + bt.x);
+    const float y1 = silu_f((h16hi(r.x) - mean) * rstd * gm.y + bt.y);
+    const float y2 = silu_f((h16lo(r.y) - mean) * rstd * gm.z + bt.z);
+    const float y3 = silu_f((h16hi(r.y) - mean) * rstd * gm.w + bt.w);
     uint2 o; o.x = pack2bf(y0, y1); o.y = pack2bf(y2, y3);
     *slot = o;
   }
@@ -225,8 +225,8 @@ __global__ __launch_bounds__(256) void gn_wino_input_kernel(const GnWinoArgs a) 
         const int x = 2 * tx - 1 + c4;
         uint2 v = uint2{0u, 0u};
         if ((unsigned)y < (unsigned)a.H && (unsigned)x < (unsigned)a.W) v = *(const uint2*)(smem + (y * a.W + x) * RS + j * 8);
-        d[r][c4][0] = __uint_as_float(v.x << 16); d[r][c4][1] = __uint_as_float(v.x & 0xffff0000u);
-        d[r][c4][2] = __uint_as_float(v.y << 16); d[r][c4][3] = __uint_as_float(v.y & 0xffff0000u);
+        d[r][c4][0] = h16lo(v.x); d[r][c4][1] = h16hi(v.x);
+        d[r][c4][2] = h16lo(v.y); d[r][c4][3] = h16hi(v.y);
       }
     }
     float qv[4][4][4];

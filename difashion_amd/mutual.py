@@ -104,13 +104,15 @@ class MutualEncoder(nn.Module):
             return self._packed
         dev = w1.device
         hid, flat = w1.shape
-        p1 = torch.empty((hid, flat), dtype=torch.bfloat16, device=dev)
-        p2 = torch.empty((flat, hid), dtype=torch.bfloat16, device=dev)
+        p1 = torch.empty((hid, flat), dtype=_lib.storage_dtype(), device=dev)
+        p2 = torch.empty((flat, hid), dtype=_lib.storage_dtype(), device=dev)
         s = _lib.stream_ptr()
         _lib.call("dfh_pack_matrix", _lib.ptr(w1.detach().float().contiguous()), _lib.ptr(p1), hid, flat, flat, 0, 0, 0, s)
         _lib.call("dfh_pack_matrix", _lib.ptr(w2.detach().float().contiguous()), _lib.ptr(p2), flat, hid, hid, 0, 0, 0, s)
-        p2t = torch.empty((hid, flat), dtype=torch.bfloat16, device=dev)     # W2^T for the data gradient of the hidden layer
-        _lib.call("dfh_pack_matrix_t", _lib.ptr(w2.detach().float().contiguous()), _lib.ptr(p2t), flat, hid, flat, 0, 0, 0, s)
+        p2t = None
+        if _lib.storage() == "bf16":         # training only (the fp16-storage library is inference only and refuses the transposed pack)
+            p2t = torch.empty((hid, flat), dtype=torch.bfloat16, device=dev)     # W2^T for the data gradient of the hidden layer
+            _lib.call("dfh_pack_matrix_t", _lib.ptr(w2.detach().float().contiguous()), _lib.ptr(p2t), flat, hid, flat, 0, 0, 0, s)
         zero = torch.zeros(256, dtype=torch.uint8, device=dev)
         self._packed = (p1, p2, b1.detach().float().contiguous(), b2.detach().float().contiguous(), zero, p2t)
         self._sig = sig
@@ -139,7 +141,7 @@ class MutualEncoder(nn.Module):
         p1, p2, b1, b2, zero, _ = self._pack()
         n = x_bf16.shape[0]
         hid, flat = p1.shape
-        h = torch.empty((n, hid), dtype=torch.bfloat16, device=x_bf16.device)
+        h = torch.empty((n, hid), dtype=_lib.storage_dtype(), device=x_bf16.device)
         keep = [self._gemm(x_bf16, flat, p1, b1, hid, ACT_LEAKY, h, OUT_BF16, zero, n)]
         hd = h
         if dropout_mask is not None:      # train-mode nn.Dropout(0.1) with a caller-supplied mask
@@ -198,7 +200,7 @@ class MutualEncoder(nn.Module):
     def forward(self, mutual_emb: torch.Tensor) -> torch.Tensor:
         bsz = mutual_emb.shape[0]
         x = mutual_emb.reshape(bsz, -1).float().contiguous()
-        xb = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+        xb = torch.empty(x.shape, dtype=_lib.storage_dtype(), device=x.device)
         _lib.call("dfh_cast_f32_to_bf16", _lib.ptr(x), _lib.ptr(xb), x.numel(), _lib.stream_ptr())
         if self.training:
             raise NotImplementedError("train-mode dropout needs an explicit mask: use forward_bf16(x, dropout_mask)")

@@ -136,7 +136,7 @@ class OutfitSampler:
         self.ts = list(self.sched._timesteps_host)
         self.is_ddim = isinstance(self.sched, DDIMScheduler)
         self.x_in = torch.empty((self.R * self.F, 2 * init_latents.shape[1], S, S), **f32)
-        self.mutual_bf = torch.empty((self.F, self.CL), dtype=torch.bfloat16, device=dev)
+        self.mutual_bf = torch.empty((self.F, self.CL), dtype=_lib.storage_dtype(), device=dev)
         self.eps_comb = torch.empty_like(self.latents) if (keep_eps or not self.is_ddim) else None
         self.mutual = self.null_lat.expand(self.F, -1, -1, -1).contiguous()   # stays when mutual guidance is off
         self.scales = (float(cate_scale), float(hist_scale), float(mutual_scale))
@@ -291,6 +291,7 @@ def train_forward(unet, fashion_encoder: MutualEncoder, scheduler, *, latents: t
     With grad enabled the returned loss carries an autograd graph of four native nodes (loss, U-Net, input assembly,
     MutualEncoder): ``loss.backward()`` / ``accelerator.backward(loss)`` (train.py:699) runs the HIP backward and adds
     the gradients into ``.grad`` of the U-Net and encoder parameters."""
+    _lib.require_bf16("train_forward / train_step")
     dev = latents.device
     if dev.type != "cuda":
         raise _lib.DfhError("train_forward runs on the HIP path only (device tensors required)")
@@ -307,7 +308,7 @@ def train_forward(unet, fashion_encoder: MutualEncoder, scheduler, *, latents: t
     sp = _lib.stream_ptr
     if use_mutual_guidance:
         tab, wt = _training_tables_on(n, olen, dev)
-        mb = torch.empty((n, CL), dtype=torch.bfloat16, device=dev)
+        mb = torch.empty((n, CL), dtype=_lib.storage_dtype(), device=dev)
         _lib.call("dfh_mutual_reduce", _lib.ptr(noisy), None, _lib.ptr(tab), _lib.ptr(wt),
                   _lib.ptr(mb), None, n, olen, CL, sp())
         mutual = fashion_encoder.forward_bf16(mb, dropout_mask).contiguous()

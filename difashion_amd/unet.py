@@ -201,6 +201,8 @@ class UNet2DConditionModel(nn.Module):
         operands quantised inside the kernel with static factors derived from the projection weights): built and parity-tested, but
         slower and less accurate than the bf16 kernels on this model, hence opt-in.  Sampling path only -- the training forward keeps
         bf16.  Takes effect at the next forward (the context is rebuilt)."""
+        if on:
+            _lib.require_bf16("enable_fp8()")
         self.fp8 = bool(on)
         self.fp8_attention = bool(attention) and self.fp8
         return self
@@ -309,6 +311,7 @@ class UNet2DConditionModel(nn.Module):
 
     def _ensure_train(self, batch: int):
         """Bind the training arenas / workspace (sized for ``batch``; grows on demand)."""
+        _lib.require_bf16("the U-Net training forward / backward")
         self._ensure_ctx(min(batch, self.max_batch))
         if self._train_buffers is not None and batch <= self._train_batch:
             return
@@ -367,8 +370,7 @@ class UNet2DConditionModel(nn.Module):
         tdev = torch.tensor(ts, dtype=torch.float32, device=ehs.device)
         nbytes = _lib.raw().dfh_unet_run_cache_bytes(self._ctx, B, len(ts))
         buf = torch.empty(nbytes, dtype=torch.uint8, device=ehs.device)
-        dt = {torch.float32: 0, torch.bfloat16: 1}
-        _lib.call("dfh_unet_run_cache", self._ctx, _lib.ptr(ehs), dt[ehs.dtype], B, _lib.ptr(tdev), len(ts), _lib.ptr(buf), nbytes,
+        _lib.call("dfh_unet_run_cache", self._ctx, _lib.ptr(ehs), _lib.dtype_code(ehs, "encoder_hidden_states"), B, _lib.ptr(tdev), len(ts), _lib.ptr(buf), nbytes,
                   _lib.stream_ptr())
         self._run_cache = dict(buf=buf, ehs=encoder_hidden_states, ehs_ptr=encoder_hidden_states.data_ptr(),
                                ehs_version=encoder_hidden_states._version, batch=B, index={t: i for i, t in reversed(list(enumerate(ts)))},
@@ -408,7 +410,7 @@ class UNet2DConditionModel(nn.Module):
             self._ensure_ctx(B)
         if not (self.assume_static_weights and self._packed_sig is not None):
             self.pack()
-        dt = {torch.float32: 0, torch.bfloat16: 1}
+        sample_code = _lib.dtype_code(sample, "sample")
         out = torch.empty((B, cfg["out_channels"], sample.shape[2], sample.shape[3]), dtype=torch.float32, device=sample.device)
         dup = 0 if train else int(getattr(self, "_dup_tail_once", 0) or 0)
         self._dup_tail_once = 0
@@ -416,11 +418,11 @@ class UNet2DConditionModel(nn.Module):
             _lib.call("dfh_unet_set_dup_tail", self._ctx, dup)
         rc = self._run_cache
         if (not train and cache_index is not None and rc is not None and rc["sig"] == self._packed_sig and rc["ctx_key"] == self._ctx_key):
-            _lib.call("dfh_unet_forward_cached", self._ctx, _lib.ptr(sample), dt[sample.dtype], _lib.ptr(rc["buf"]), B, rc["n"],
+            _lib.call("dfh_unet_forward_cached", self._ctx, _lib.ptr(sample), sample_code, _lib.ptr(rc["buf"]), B, rc["n"],
                       int(cache_index), _lib.ptr(out), _lib.stream_ptr())
         else:
-            _lib.call("dfh_unet_forward_train" if train else "dfh_unet_forward", self._ctx, _lib.ptr(sample), dt[sample.dtype],
-                      _lib.ptr(t), _lib.ptr(ehs), dt[ehs.dtype], _lib.ptr(out), B, _lib.stream_ptr())
+            _lib.call("dfh_unet_forward_train" if train else "dfh_unet_forward", self._ctx, _lib.ptr(sample), sample_code,
+                      _lib.ptr(t), _lib.ptr(ehs), _lib.dtype_code(ehs, "encoder_hidden_states"), _lib.ptr(out), B, _lib.stream_ptr())
         if sample.dtype != torch.float32:
             out = out.to(sample.dtype)
         return out
@@ -618,9 +620,8 @@ class UNet2DConditionModel(nn.Module):
             t = t.contiguous()
         if t is not None and t.numel() != B:
             raise ValueError("timestep must be a scalar or have one entry per batch row")
-        dt = {torch.float32: 0, torch.bfloat16: 1}
-        if sample.dtype not in dt or encoder_hidden_states.dtype not in dt:
-            raise TypeError("sample / encoder_hidden_states must be float32 or bfloat16")
+        _lib.dtype_code(sample, "sample")                  # float32 or the library's 16-bit storage type; anything else raises TypeError
+        _lib.dtype_code(encoder_hidden_states, "encoder_hidden_states")
         sample = sample.contiguous()
         ehs = encoder_hidden_states.contiguous()
         if train:
