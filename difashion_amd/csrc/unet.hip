@@ -41,12 +41,12 @@ int dfh_unet_create(const dfh_unet_config* cfg, dfh_unet** out) {
 }
 
 void dfh_unet_destroy(dfh_unet* u) { delete u; }
-int dfh_unet_num_params(const dfh_unet* u) { return (int)u->params.size(); }
-const char* dfh_unet_param_name(const dfh_unet* u, int i) { return u->params[i].name.c_str(); }
-int dfh_unet_param_ndim(const dfh_unet* u, int i) { return (int)u->params[i].shape.size(); }
-int dfh_unet_param_dim(const dfh_unet* u, int i, int d) { return u->params[i].shape[d]; }
-size_t dfh_unet_arena16_bytes(const dfh_unet* u) { return u->a16 * 2 + 256; }
-size_t dfh_unet_arena32_bytes(const dfh_unet* u) { return u->a32 * 4 + 256; }
+int dfh_unet_num_params(const dfh_unet* u) { return u->num_params(); }
+const char* dfh_unet_param_name(const dfh_unet* u, int i) { return u->param_name(i); }
+int dfh_unet_param_ndim(const dfh_unet* u, int i) { return u->param_ndim(i); }
+int dfh_unet_param_dim(const dfh_unet* u, int i, int d) { return u->param_dim(i, d); }
+size_t dfh_unet_arena16_bytes(const dfh_unet* u) { return u->arena16_bytes(); }
+size_t dfh_unet_arena32_bytes(const dfh_unet* u) { return u->arena32_bytes(); }
 
 size_t dfh_unet_workspace_bytes(dfh_unet* u, int batch) {
   if (batch <= 0) return 0;

@@ -1,40 +1,18 @@
-// Shared definition of the U-Net runtime object (parameter table, packing plan, inference walk).
-// Included by unet.hip (inference + C ABI) and unet_train.hip (training forward / backward).
+// The U-Net runtime object: its layer structs, build / packing plan, derived weights (folds, fp8 copies) and the inference walk.
+// Included by unet.hip (inference + C ABI) and unet_train.hip (training forward / backward).  The parameter table, the workspace head
+// and the launch context it shares with the VAE and the training walk live in walk_common.h.
 #pragma once
-#include <algorithm>
-#include <cmath>
-#include <cstring>
 #include <map>
-#include <string>
-#include <vector>
 
-#include "../../include/difashion_hip.h"
-#include "attention.h"
-#include "dfh_common.h"
+#include "walk_common.h"
 #include "elementwise.h"
-#include "gemm.h"
 #include "mlp_fused.h"
 #ifdef DFH_PROBES
 #include "token_linear.h"
 #endif
-#include "norm.h"
-#include "packtab.h"
 #include "bwd_elementwise.h"
 
 namespace dfhm {
-
-struct Mat { size_t off = 0; int N = 0, K = 0; };    // bf16 [N][K] at arena16 + off (elements)
-struct Vec { size_t off = 0; int N = 0; };           // fp32 [N] at arena32 + off (elements)
-
-enum PackKind { PK_VEC = 0, PK_MAT = 1, PK_CONV3 = 2 };
-struct PackOp {
-  int param, kind;
-  size_t dst;
-  int N, K, ldw, row_off, col_off, geglu, accumulate;
-  int cin_pad = 0;   // PK_CONV3: channels per tap in the packed layout (conv_in pads 4 -> 8)
-};
-
-struct ParamDesc { std::string name; std::vector<int> shape; };
 
 // transposed pack (training): master weight -> arena16t, see bwd_elementwise.hip pack_*_t kernels
 struct TPackOp { int param, conv; size_t dst; int N, K, ldt, t_row_off, t_col_off, geglu, o_pad; };
@@ -85,69 +63,11 @@ struct ConvL {
   size_t ph = 0; bool has_ph = false;
 };
 
-struct Tensor {
-  bf16_t* p = nullptr; int H = 0, W = 0, C = 0;
-  // GroupNorm statistics of this tensor written by the GEMM epilogue that produced it (gemm.h GemmArgs::gstat); null when the
-  // launch ran on a kernel that does not write them -- the consuming GroupNorm then computes its own
-  const float* gst = nullptr; int gst_cpg = 0, gst_chunks = 0;
-};
-
-struct Bump {
-  char* base = nullptr; size_t cap = 0, off = 0, peak = 0;
-  void* alloc(size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    char* p = base + off;
-    off += bytes;
-    if (off > peak) peak = off;
-    return p;
-  }
-};
-
-// host copy + device copy of a TabOp table; re-uploaded only when an entry (e.g. a master pointer) changed
-struct OpTable {
-  std::vector<TabOp> host, uploaded; TabOp* dev = nullptr; size_t cap = 0; unsigned blocks = 0;
-  void clear() { host.clear(); blocks = 0; }
-  void add(void* master, int kind, long dst, int N, int K, int ld, int p0, int p1, int p2, int p3, long /*elems*/) {
-    TabOp op; std::memset(&op, 0, sizeof(op));
-    op.master = master; op.dst = dst; op.kind = kind; op.N = N; op.K = K; op.ld = ld; op.p0 = p0; op.p1 = p1; op.p2 = p2; op.p3 = p3;
-    op.first_block = blocks;
-    blocks += dfh::tab_blocks(kind, N, K);
-    host.push_back(op);
-  }
-  // a PACK2 op: the plain pack (dst .. p3 as in add) and the transposed pack (dst2, ld2, q0 = t_row_off, q1 = t_col_off, q3 = o_pad) of one master
-  void add2(void* master, int kind, long dst, int N, int K, int ld, int p0, int p1, int p2, int p3, long dst2, int ld2, int q0, int q1, int q3) {
-    add(master, kind, dst, N, K, ld, p0, p1, p2, p3, 0);
-    TabOp& op = host.back();
-    op.dst2 = dst2; op.ld2 = ld2; op.q0 = q0; op.q1 = q1; op.q3 = q3;
-  }
-  int launch(void* arena_vec, void* arena_mat, hipStream_t s, void* arena_mat2 = nullptr, float* sq_partials = nullptr) {
-    if (host.empty()) return 0;
-    const size_t bytes = host.size() * sizeof(TabOp);
-    if (host.size() != uploaded.size() || std::memcmp(host.data(), uploaded.data(), bytes) != 0) {
-      if (host.size() > cap) {
-        if (dev) (void)hipFree(dev);
-        if (hipMalloc((void**)&dev, bytes) != hipSuccess) { dfh::set_error("hipMalloc of an op table failed"); return -1; }
-        cap = host.size();
-      }
-      // rare (first use / parameters re-homed): stream-ordered with respect to earlier launches that read the old table
-      if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        dfh::set_error("uploading an op table failed"); return -1;
-      }
-      uploaded = host;
-    }
-    return dfh::table_launch(dev, (int)host.size(), blocks, arena_vec, arena_mat, s, arena_mat2, sq_partials);
-  }
-  ~OpTable() { if (dev) (void)hipFree(dev); }
-};
-
 }  // namespace dfhm
 using namespace dfhm;
 
-struct dfh_unet {
+struct dfh_unet : ParamTable {
   dfh_unet_config cfg{};
-  std::vector<ParamDesc> params;
-  std::vector<PackOp> packs;
-  size_t a16 = 0, a32 = 0;         // arena sizes in elements
   // layers
   ConvL conv_in, conv_out;
   Mat te1, te2, tproj, kx_all, vx_all; Vec te1b, te2b, tprojb, cnw, cnb;
@@ -169,8 +89,7 @@ struct dfh_unet {
   std::vector<std::vector<AttL>> down_att, up_att;
   std::vector<ConvL> down_samp, up_samp;
   ResL mid_res[2]; AttL mid_att;
-  // bound memory
-  bf16_t* arena16 = nullptr; float* arena32 = nullptr;
+  // bound memory (the arenas: ParamTable)
   char* ws = nullptr; size_t ws_bytes = 0; int max_batch = 0;
   // planning results (bytes) for the last planned batch
   size_t plan_persist = 0, plan_temp = 0, plan_partial = 0, plan_total = 0; int plan_batch = 0;
@@ -208,42 +127,6 @@ struct dfh_unet {
   ~dfh_unet();
 
   // ---------------------------------------------------------------- build
-  int add_param(const std::string& name, std::vector<int> shape) {
-    params.push_back({name, std::move(shape)});
-    return (int)params.size() - 1;
-  }
-  size_t alloc16(size_t n) { size_t o = a16; a16 += (n + 127) & ~(size_t)127; return o; }
-  size_t alloc32(size_t n) { size_t o = a32; a32 += (n + 63) & ~(size_t)63; return o; }
-
-  Vec vec(const std::string& name, int N) {
-    Vec v; v.N = N; v.off = alloc32(N);
-    int p = add_param(name, {N});
-    packs.push_back({p, PK_VEC, v.off, N, 0, 0, 0, 0, 0, 0});
-    return v;
-  }
-  // packs a vector parameter into an existing fp32 range (batched biases / fused shortcut bias)
-  void vec_into(const std::string& name, int N, size_t dst, int geglu, int accumulate) {
-    int p = add_param(name, {N});
-    packs.push_back({p, PK_VEC, dst, N, 0, 0, 0, 0, geglu, accumulate});
-  }
-  Mat mat_alloc(int N, int K) { Mat m; m.N = N; m.K = K; m.off = alloc16((size_t)N * K); return m; }
-  void mat_into(const std::string& name, int N, int K, bool as_conv1x1, const Mat& dst, int row_off, int col_off, int geglu) {
-    std::vector<int> shape = as_conv1x1 ? std::vector<int>{N, K, 1, 1} : std::vector<int>{N, K};
-    int p = add_param(name, shape);
-    packs.push_back({p, PK_MAT, dst.off, N, K, dst.K, row_off, col_off, geglu, 0});
-  }
-  Mat mat(const std::string& name, int N, int K, bool as_conv1x1 = false, int geglu = 0) {
-    Mat m = mat_alloc(N, K);
-    mat_into(name, N, K, as_conv1x1, m, 0, 0, geglu);
-    return m;
-  }
-  void conv_into(const std::string& name, int cout, int cin, const Mat& dst, int col_off, int cin_pad = 0) {
-    int p = add_param(name, {cout, cin, 3, 3});
-    PackOp op{p, PK_CONV3, dst.off, cout, cin, dst.K, 0, col_off, 0, 0};
-    op.cin_pad = cin_pad ? cin_pad : cin;
-    packs.push_back(op);
-  }
-
   // largest image (pixels) whose wide resnet convs take Winograd: 256 = the 16x16 level (default); DFH_WINO_MAXHW=1024 adds the 32x32 level
   // (the A/B of profiles/r04: measured, not the default)
   static int wino_max_hw() {
@@ -608,23 +491,18 @@ struct dfh_unet {
   }
 
   // ---------------------------------------------------------------- run
-  struct Run {
-    dfh_unet* u; int B; hipStream_t s; bool dry;
-    Bump persist, temp; size_t partial_need = 0;
-    float* partial = nullptr; size_t partial_cap = 0;
-    float* gn_partial = nullptr; bf16_t* zero = nullptr;
+  struct Run : WalkBase {
+    dfh_unet* u;
     int temb_ld = 0;                 // row stride of the time-embedding rows: temb_total, or 0 when the whole batch shares one cached row
-    int rc = 0;
     // fp8 walk: per transformer layer and batch element the largest |V| of the self-attention (tracked by the V projection's epilogue,
     // zeroed at the start of the walk) and of the cross-attention (amax_slabs over the text V^T, once per forward or per run): [n_att][B]
     float* amax_self = nullptr; const float* amax_cross = nullptr;
 
-    bf16_t* w16(const Mat& m) const { return u->arena16 + m.off; }
-    float* v32(const Vec& v) const { return u->arena32 + v.off; }
     // Ba: the batch every tensor is ALLOCATED for (the call's batch); B: the batch the launches run on.  They differ only inside the
     // shared prefix of a guidance batch whose last `dup` images repeat the inputs of the `dup` images before them (dfh_unet::dup_tail):
     // there B = Ba - dup, and dup_images() then copies the repeated images' rows into place.
-    int Ba = 0;
+    int Ba;
+    Run(dfh_unet* u_, int B_, hipStream_t s_, bool dry_) : WalkBase(*u_, u_->cfg.norm_num_groups, B_, s_, dry_), u(u_), Ba(B_) {}
     Tensor palloc(int H, int W, int C) { return Tensor{(bf16_t*)persist.alloc((size_t)Ba * H * W * C * 2), H, W, C}; }
     Tensor talloc(int H, int W, int C) { return Tensor{(bf16_t*)temp.alloc((size_t)Ba * H * W * C * 2), H, W, C}; }
     void dup_bytes(void* p, size_t per_image, int n) {   // images [Ba - n, Ba) := images [Ba - 2n, Ba - n) of a [Ba][per_image bytes] buffer
@@ -645,10 +523,9 @@ struct dfh_unet {
     void gemm(GemmArgs g, Tensor* o = nullptr, Bump* bump = nullptr, int* rs_bn = nullptr) {
       if (rs_bn) *rs_bn = 0;
       if (rc) return;
-      g.zero = zero; g.partial = partial;
       static const bool pre_off = [] { const char* e = getenv("DFH_GN_PRE"); return e && e[0] == '0'; }();
       float* gst = nullptr;
-      const int G = u->cfg.norm_num_groups;
+      const int G = groups;
       // the consumers take at most GN_MAX_CHUNKS chunks per (image, group): a level fits when its 256-row chunk count does; gemm_launch
       // refuses the 128-row writer by itself when HW / 128 would exceed it (96x96 latents: 36 chunks of 256 rows, 72 of 128)
       if (o && bump && !pre_off && (o->H * o->W) % 128 == 0 && o->C % G == 0 &&
@@ -656,28 +533,18 @@ struct dfh_unet {
         gst = (float*)bump->alloc((size_t)Ba * G * ((o->H * o->W) / 128) * 2 * sizeof(float));      // same in the dry run; chunks of 256 or 128 pixel rows
         g.gstat = gst; g.gstat_cpg = o->C / G; g.gstat_hw = o->H * o->W;
       }
-      if (dry) { partial_need = std::max(partial_need, dfh::gemm_partial_floats(g) * sizeof(float)); return; }
-      if (dfh::gemm_partial_floats(g) * sizeof(float) > partial_cap) { dfh::set_error("split-K partial buffer too small"); rc = -1; return; }
+      if (!gemm_ready(g)) return;
       int gst_rows = 0;
       rc = dfh::gemm_launch(g, s, 0, 0, -1, &gst_rows, rs_bn);
       if (o && gst_rows) { o->gst = gst; o->gst_cpg = g.gstat_cpg; o->gst_chunks = g.gstat_hw / gst_rows; }
-    }
-    static GemmArgs base(int M, int N) {
-      GemmArgs g; std::memset(&g, 0, sizeof(g));
-      g.M = M; g.N = N; g.rows_per_b = M; g.out_mode = OUT_BF16; g.ld_out = N;
-      return g;
     }
     // out = act(x . W^T + bias) (+resid); x rows [M][K]
     // rowstat / rs_bn: ask the launch for the per-row statistics of its output (a LayerNorm folded into the consumers, gemm.h)
     void linear(const bf16_t* x, int M, int K, const Mat& W, const Vec* bias, int act, const bf16_t* resid, void* out,
                 int N, int out_mode = OUT_BF16, int ld_out = -1, int rows_per_b = 0, Tensor* o = nullptr, Bump* bump = nullptr,
                 float* rowstat = nullptr, int* rs_bn = nullptr) {
-      GemmArgs g = base(M, N);
-      g.p_src[0] = x; g.p_c[0] = K; g.nplain = 1;
-      g.W = w16(W); g.ldw = W.K;
-      g.bias = bias ? v32(*bias) : nullptr;
-      g.act = act; g.resid = resid; g.ld_res = N;
-      g.out = out; g.out_mode = out_mode; g.ld_out = ld_out < 0 ? (act == ACT_GEGLU ? N / 2 : N) : ld_out;
+      GemmArgs g = linear_desc(x, M, K, W, bias, resid, out, N, out_mode);
+      g.act = act; g.ld_out = ld_out < 0 ? (act == ACT_GEGLU ? N / 2 : N) : ld_out;
       if (rows_per_b) g.rows_per_b = rows_per_b;
       g.rowstat = rowstat;
       gemm(g, o, bump, rs_bn);
@@ -696,10 +563,7 @@ struct dfh_unet {
     }
     void groupnorm(const Tensor& x0, const Tensor* x1, const Vec& w, const Vec& b, float eps, int silu, Tensor& out) {
       if (rc || dry) return;
-      GnArgs a; std::memset(&a, 0, sizeof(a));
-      a.src0 = x0.p; a.C0 = x0.C; a.src1 = x1 ? x1->p : nullptr; a.C1 = x1 ? x1->C : 0;
-      a.B = B; a.HW = x0.H * x0.W; a.G = u->cfg.norm_num_groups;
-      a.gamma = v32(w); a.beta = v32(b); a.eps = eps; a.silu = silu; a.out = out.p; a.partial = gn_partial;
+      GnArgs a = gn_args(x0.p, x0.C, x1 ? x1->p : nullptr, x1 ? x1->C : 0, x0.H * x0.W, w, b, eps, silu, out.p);
       if (!x1 && x0.gst && x0.gst_cpg == x0.C / a.G) { a.pre = x0.gst; a.pre_chunks = x0.gst_chunks; }   // summed by its producer
       rc = dfh::groupnorm_launch(a, s);
     }
@@ -743,12 +607,9 @@ struct dfh_unet {
     void attention8(const bf16_t* Q, int ldq, const bf16_t* K, int ldk, const bf16_t* Vt, int ldvt, uint8_t* O8, const float* amax, int C,
                     int heads, int Nq, int Nk, long vt_bstride = 0, const float* f8 = nullptr) {
       if (rc || dry) return;
-      AttnArgs a; std::memset(&a, 0, sizeof(a));
+      AttnArgs a = attn_args(Q, ldq, K, ldk, Vt, ldvt, C, heads, Nq, Nk, vt_bstride);
       if (f8) { a.f8_rq = f8; a.f8_rk = f8 + C; a.f8_rv = f8 + 2 * C; a.f8_hs = f8 + 3 * C; }
-      a.vt_bstride = vt_bstride;
-      a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.Vt = Vt; a.ldvt = ldvt; a.O8 = O8; a.o_amax = amax; a.ldo = C;
-      a.B = B; a.H = heads; a.D = C / heads; a.Nq = Nq; a.Nk = Nk;
-      a.scale = 1.0f / sqrtf((float)a.D);
+      a.O8 = O8; a.o_amax = amax;
       rc = dfh::attention_launch(a, s);
     }
     void layernorm(const bf16_t* x, const Vec& w, const Vec& b, bf16_t* y, int M, int C) {
@@ -759,12 +620,9 @@ struct dfh_unet {
     void attention(const bf16_t* Q, int ldq, const bf16_t* K, int ldk, const bf16_t* Vt, int ldvt, bf16_t* O, int C,
                    int heads, int Nq, int Nk, long vt_bstride = 0, const float* f8 = nullptr) {
       if (rc || dry) return;
-      AttnArgs a; std::memset(&a, 0, sizeof(a));
+      AttnArgs a = attn_args(Q, ldq, K, ldk, Vt, ldvt, C, heads, Nq, Nk, vt_bstride);
       if (f8) { a.f8_rq = f8; a.f8_rk = f8 + C; a.f8_rv = f8 + 2 * C; a.f8_hs = f8 + 3 * C; }
-      a.vt_bstride = vt_bstride;
-      a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.Vt = Vt; a.ldvt = ldvt; a.O = O; a.ldo = C;
-      a.B = B; a.H = heads; a.D = C / heads; a.Nq = Nq; a.Nk = Nk;
-      a.scale = 1.0f / sqrtf((float)a.D);
+      a.O = O;
       rc = dfh::attention_launch(a, s);
     }
 
@@ -785,10 +643,7 @@ struct dfh_unet {
         gemm(g);
         return o;
       }
-      GemmArgs g = base(B * Ho * Wo, c.cout);
-      g.conv_src = x.p; g.conv_c = x.C; g.ntaps = 9;
-      g.Hin = x.H; g.Win = x.W; g.Hout = Ho; g.Wout = Wo; g.stride = stride; g.ups = ups;
-      g.W = w16(c.w); g.ldw = c.w.K; g.bias = v32(c.b);
+      GemmArgs g = conv_desc(x.p, x.C, x.H, x.W, Ho, Wo, stride, ups, c.w, c.b);
       g.out = o.p;
       gemm(g, &o, to_persist ? &persist : &temp);
       return o;
@@ -886,10 +741,7 @@ struct dfh_unet {
       }
       groupnorm(x0, x1, r.n1w, r.n1b, u->cfg.norm_eps, 1, g1);
       {
-        GemmArgs g = base(B * H * W, r.cout);
-        g.conv_src = g1.p; g.conv_c = r.cin; g.ntaps = 9;
-        g.Hin = H; g.Win = W; g.Hout = H; g.Wout = W; g.stride = 1;
-        g.W = w16(r.w1); g.ldw = r.w1.K; g.bias = v32(r.b1);
+        GemmArgs g = conv_desc(g1.p, r.cin, H, W, H, W, 1, 0, r.w1, r.b1);
         g.rowvec = temb_all; g.rv_ld = temb_ld; g.rv_off = r.temb_off; g.rows_per_b = H * W;
         g.out = h1.p;
         gemm(g, &h1, &temp);
@@ -897,10 +749,7 @@ struct dfh_unet {
       Tensor g2 = talloc(H, W, r.cout);
       groupnorm(h1, nullptr, r.n2w, r.n2b, u->cfg.norm_eps, 1, g2);
       {
-        GemmArgs g = base(B * H * W, r.cout);
-        g.conv_src = g2.p; g.conv_c = r.cout; g.ntaps = 9;
-        g.Hin = H; g.Win = W; g.Hout = H; g.Wout = W; g.stride = 1;
-        g.W = w16(r.w2); g.ldw = r.w2.K; g.bias = v32(r.b2);
+        GemmArgs g = conv_desc(g2.p, r.cout, H, W, H, W, 1, 0, r.w2, r.b2);
         if (r.shortcut) {   // 1x1 shortcut over the (possibly concatenated) block input rides along as K segments
           g.p_src[0] = x0.p; g.p_c[0] = x0.C; g.nplain = 1;
           if (x1) { g.p_src[1] = x1->p; g.p_c[1] = x1->C; g.nplain = 2; }
@@ -1186,7 +1035,7 @@ struct dfh_unet {
 
   int run(const void* sample, int sample_bf16, const float* timestep, const void* ehs, int ehs_bf16, float* out, int B,
           hipStream_t s, bool dry, const RunCache* rcache = nullptr) {
-    Run r; r.u = this; r.B = B; r.Ba = B; r.s = s; r.dry = dry;
+    Run r(this, B, s, dry);
     r.temb_ld = (rcache && rcache->temb_row) ? 0 : temb_total;
     // one-shot hint of the caller (dfh_unet_set_dup_tail): the last `dup` images repeat the sample / timestep of the `dup` before them
     const int dup = (!dry && dup_tail > 0 && 2 * dup_tail <= B) ? dup_tail : 0;
@@ -1196,12 +1045,9 @@ struct dfh_unet {
     const int nb = cfg.num_blocks, temb = boc[0] * 4;
     // fixed regions at the head of the workspace
     char* const wsb = dry ? nullptr : ws + fold_bytes();      // the fold region comes first (fold_layernorms)
-    Bump head; head.base = wsb;
-    r.zero = (bf16_t*)head.alloc(256);
-    r.gn_partial = (float*)head.alloc((size_t)B * GN_MAX_CHUNKS * 64 * 2 * sizeof(float));
-    r.partial = (float*)head.alloc(dry ? 0 : plan_partial);
-    r.partial_cap = dry ? 0 : plan_partial;
-    const size_t head_bytes = (head.off + 255) & ~(size_t)255;
+    const WorkspaceHead head(wsb, B, dry ? 0 : plan_partial);
+    r.bind_head(head);
+    const size_t head_bytes = head.bytes;
     if (!dry) {
       if (B != plan_batch) { dfh::set_error("forward batch differs from the planned batch"); return -1; }
       r.persist.base = wsb + head_bytes;
@@ -1315,10 +1161,7 @@ struct dfh_unet {
     Tensor g = r.palloc(h.H, h.W, h.C);
     r.groupnorm(h, nullptr, cnw, cnb, cfg.norm_eps, 1, g);
     {
-      GemmArgs ga = Run::base(B * S * S, cfg.out_channels);
-      ga.conv_src = g.p; ga.conv_c = g.C; ga.ntaps = 9;
-      ga.Hin = S; ga.Win = S; ga.Hout = S; ga.Wout = S; ga.stride = 1;
-      ga.W = r.w16(conv_out.w); ga.ldw = conv_out.w.K; ga.bias = r.v32(conv_out.b);
+      GemmArgs ga = r.conv_desc(g.p, g.C, S, S, S, S, 1, 0, conv_out.w, conv_out.b);
       ga.out = out; ga.out_mode = OUT_F32_T; ga.ld_out = S * S; ga.rows_per_b = S * S;
       r.gemm(ga);
     }
@@ -1327,9 +1170,8 @@ struct dfh_unet {
       plan_temp = (r.temp.peak + 255) & ~(size_t)255;
       plan_partial = (r.partial_need + 255) & ~(size_t)255;
       plan_batch = B;
-      // head is re-derived with the real partial size
-      Bump hd; hd.alloc(256); hd.alloc((size_t)B * GN_MAX_CHUNKS * 64 * 2 * sizeof(float)); hd.alloc(plan_partial);
-      plan_total = fold_bytes() + ((hd.off + 255) & ~(size_t)255) + plan_persist + plan_temp;
+      // the head with the real slab size
+      plan_total = fold_bytes() + WorkspaceHead(nullptr, B, plan_partial).bytes + plan_persist + plan_temp;
       taps.clear();
     } else {
       last_batch = B;
@@ -1342,14 +1184,12 @@ struct dfh_unet {
   int run_cache(const void* ehs, int ehs_bf16, int B, const float* timesteps, int n_t, void* cache, hipStream_t s) {
     if (B != plan_batch) run(nullptr, 0, nullptr, nullptr, 0, nullptr, B, nullptr, true);
     DFH_REQUIRE(plan_total <= ws_bytes, "workspace too small for this batch");
-    Run r; r.u = this; r.B = B; r.Ba = B; r.s = s; r.dry = false;
+    Run r(this, B, s, false);
     const int T = cfg.text_len, X = cfg.cross_attention_dim, Tp = (T + 7) & ~7;
     const int temb = cfg.block_out_channels[0] * 4, c0 = cfg.block_out_channels[0];
-    Bump head; head.base = ws + fold_bytes();
-    r.zero = (bf16_t*)head.alloc(256);
-    r.gn_partial = (float*)head.alloc((size_t)B * GN_MAX_CHUNKS * 64 * 2 * sizeof(float));
-    r.partial = (float*)head.alloc(plan_partial); r.partial_cap = plan_partial;
-    Bump tmp; tmp.base = head.base + ((head.off + 255) & ~(size_t)255);
+    const WorkspaceHead head(ws + fold_bytes(), B, plan_partial);
+    r.bind_head(head);
+    Bump tmp; tmp.base = ws + fold_bytes() + head.bytes;
     (void)hipMemsetAsync(r.zero, 0, 256, s);
     bf16_t* kx = (bf16_t*)cache;
     bf16_t* vxt = (bf16_t*)((char*)cache + cache_kx_bytes(*this, B));
@@ -1365,7 +1205,7 @@ struct dfh_unet {
     bf16_t* e1 = (bf16_t*)tmp.alloc((size_t)B * temb * 2);
     bf16_t* e2 = (bf16_t*)tmp.alloc((size_t)B * temb * 2);
     float* trow = (float*)tmp.alloc((size_t)B * temb_total * 4);
-    DFH_REQUIRE(fold_bytes() + ((head.off + 255) & ~(size_t)255) + tmp.off <= ws_bytes, "workspace too small for the run cache scratch");
+    DFH_REQUIRE(fold_bytes() + head.bytes + tmp.off <= ws_bytes, "workspace too small for the run cache scratch");
     for (int t0 = 0; t0 < n_t && !r.rc; t0 += B) {
       // always B rows (the planned GEMM shapes); rows past n_t repeat the last timestep and are not copied out
       const int n = std::min(B, n_t - t0);
@@ -1380,22 +1220,10 @@ struct dfh_unet {
     return r.rc;
   }
 
-  OpTable tab_pack, tab_pack_acc, tab_packt, tab_unpack, tab_pack2;
+  OpTable tab_packt, tab_unpack, tab_pack2;
   int pack_all(const float* const* master, int count, hipStream_t s);      // training: pack() + pack_train() with one read of the weights (unet_train.hip)
-  // every PackOp in one launch (plus one for the few biases that ADD onto an already packed vector)
   int pack(const float* const* master, int count, hipStream_t s) {
-    DFH_REQUIRE(count == (int)params.size(), "parameter count mismatch");
-    DFH_REQUIRE(arena16 && arena32, "arenas not bound");
-    tab_pack.clear(); tab_pack_acc.clear();
-    for (const PackOp& op : packs) {
-      void* src = (void*)master[op.param];
-      DFH_REQUIRE(src != nullptr, "null master parameter: " + params[op.param].name);
-      if (op.kind == PK_VEC) (op.accumulate ? tab_pack_acc : tab_pack).add(src, TAB_PACK_VEC, (long)op.dst, op.N, 0, 0, op.geglu, op.accumulate, 0, 0, op.N);
-      else if (op.kind == PK_MAT) tab_pack.add(src, TAB_PACK_MAT, (long)op.dst, op.N, op.K, op.ldw, op.row_off, op.col_off, op.geglu, 0, (long)op.N * op.K);
-      else tab_pack.add(src, TAB_PACK_CONV, (long)op.dst, op.N, op.K, op.ldw, 0, op.col_off, 0, op.cin_pad, (long)op.N * op.K * 9);
-    }
-    if (int rc = tab_pack.launch(arena32, arena16, s)) return rc;
-    if (int rc = tab_pack_acc.launch(arena32, arena16, s)) return rc;
+    if (int rc = pack_params(master, count, s)) return rc;
     if (int rc = quantize_fp8(s)) return rc;   // e4m3 copies of the LayerNorm-fed projections from the freshly packed bf16 matrices
     fold_valid = false; fold_dirty = true;     // the folded copies are re-derived by the next INFERENCE walk (a training step never pays)
     return 0;

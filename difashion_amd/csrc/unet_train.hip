@@ -28,14 +28,12 @@ namespace {
 struct GT { bf16_t* p = nullptr; bf16_t* g = nullptr; int H = 0, W = 0, C = 0; int gid = -1; };
 }
 
-struct dfh_unet::TrainRun {
-  dfh_unet* u = nullptr; int B = 0; hipStream_t s = nullptr; bool dry = true;
-  Bump persist, gtemp;
-  size_t partial_need = 0; float* partial = nullptr; size_t partial_cap = 0;
+struct dfh_unet::TrainRun : WalkBase {
+  dfh_unet* u;
+  // persist: every activation of the step and the gradients that cross layers; temp: layer-internal gradient buffers, a stack
   float* partial2 = nullptr;                                   // slab region of the weight-gradient launches on the side stream
   hipStream_t s2 = nullptr; bool forked = false;               // see wgrad() / join()
-  float* gn_partial = nullptr; bf16_t* zero = nullptr;
-  int rc = 0;
+  TrainRun(dfh_unet* u_, int B_, hipStream_t s_, bool dry_) : WalkBase(*u_, u_->cfg.norm_num_groups, B_, s_, dry_), u(u_) {}
   std::vector<std::function<void()>> tape;
   std::vector<char> gstate;
   const float* d_out = nullptr; float* d_sample = nullptr;   // set by backward()
@@ -49,14 +47,12 @@ struct dfh_unet::TrainRun {
   std::vector<int> bucket_last;                                // per bucket: lowest tape index writing into it (-1: never written)
   std::vector<std::pair<size_t, size_t>> ready;                // finished ranges not handed out yet
 
-  bf16_t* w16(const Mat& m) const { return u->arena16 + m.off; }
   bf16_t* w16t(const Mat& m) const { return u->arena16t + m.off; }
-  float* v32(const Vec& v) const { return u->arena32 + v.off; }
   float* g32(const Vec& v) const { return u->grad32 + v.off; }
 
   bf16_t* buf(size_t elems) { return (bf16_t*)persist.alloc(elems * 2); }
   float* fbuf(size_t elems) { return (float*)persist.alloc(elems * 4); }
-  bf16_t* gbuf(size_t elems) { return (bf16_t*)gtemp.alloc(elems * 2); }
+  bf16_t* gbuf(size_t elems) { return (bf16_t*)temp.alloc(elems * 2); }
   // activation + gradient buffer; io tensors (layer inputs / outputs) keep their gradient across layers
   GT act(int H, int W, int C, bool io = false) {
     GT t; t.H = H; t.W = W; t.C = C;
@@ -71,34 +67,11 @@ struct dfh_unet::TrainRun {
   bool acc(const GT& t) { const bool a = gstate[t.gid] != 0; gstate[t.gid] = 1; return a; }
 
   // ------------------------------------------------------------------ kernel wrappers
-  void gemm(GemmArgs g) {
-    if (rc) return;
-    g.zero = zero; g.partial = partial;
-    if (dry) { partial_need = std::max(partial_need, dfh::gemm_partial_floats(g) * sizeof(float)); return; }
-    if (dfh::gemm_partial_floats(g) * sizeof(float) > partial_cap) { dfh::set_error("split-K partial buffer too small"); rc = -1; return; }
-    rc = dfh::gemm_launch(g, s);
-  }
-  static GemmArgs base(int M, int N) {
-    GemmArgs g; std::memset(&g, 0, sizeof(g));
-    g.M = M; g.N = N; g.rows_per_b = M; g.out_mode = OUT_BF16; g.ld_out = N;
-    return g;
-  }
   // out = x . W^T + bias (+resid); returns the descriptor (the weight-gradient GEMM re-reads its K segments)
   GemmArgs linear(const bf16_t* x, int M, int K, const Mat& W, const Vec* bias, const bf16_t* resid, void* out, int N,
                   int out_mode = OUT_BF16) {
-    GemmArgs g = base(M, N);
-    g.p_src[0] = x; g.p_c[0] = K; g.nplain = 1;
-    g.W = w16(W); g.ldw = W.K;
-    g.bias = bias ? v32(*bias) : nullptr;
-    g.resid = resid; g.ld_res = N;
-    g.out = out; g.out_mode = out_mode;
+    GemmArgs g = linear_desc(x, M, K, W, bias, resid, out, N, out_mode);
     gemm(g);
-    return g;
-  }
-  GemmArgs conv_desc(const bf16_t* src, int C, int Hin, int Win, int Hout, int Wout, int stride, int ups, int N) {
-    GemmArgs g = base(B * Hout * Wout, N);
-    g.conv_src = src; g.conv_c = C; g.ntaps = 9;
-    g.Hin = Hin; g.Win = Win; g.Hout = Hout; g.Wout = Wout; g.stride = stride; g.ups = ups;
     return g;
   }
   // dW (packed fp32 gradient of the matrix at arena16 + w_off) += dY^T . A, A described by the forward descriptor
@@ -165,10 +138,8 @@ struct dfh_unet::TrainRun {
   }
   void groupnorm(const GT& x0, const GT* x1, const Vec& w, const Vec& b, float eps, int silu, bf16_t* out, float* stats) {
     if (rc || dry) return;
-    GnArgs a; std::memset(&a, 0, sizeof(a));
-    a.src0 = x0.p; a.C0 = x0.C; a.src1 = x1 ? x1->p : nullptr; a.C1 = x1 ? x1->C : 0;
-    a.B = B; a.HW = x0.H * x0.W; a.G = u->cfg.norm_num_groups;
-    a.gamma = v32(w); a.beta = v32(b); a.eps = eps; a.silu = silu; a.out = out; a.partial = gn_partial; a.stats_out = stats;
+    GnArgs a = gn_args(x0.p, x0.C, x1 ? x1->p : nullptr, x1 ? x1->C : 0, x0.H * x0.W, w, b, eps, silu, out);
+    a.stats_out = stats;
     rc = dfh::groupnorm_launch(a, s);
   }
   void groupnorm_bwd(const GT& x0, const GT* x1, const bf16_t* dy, const Vec& w, const Vec& b, const float* stats, int silu) {
@@ -193,11 +164,8 @@ struct dfh_unet::TrainRun {
   void attention(const bf16_t* Q, int ldq, const bf16_t* K, int ldk, const bf16_t* Vt, int ldvt, bf16_t* O, int C, int heads,
                  int Nq, int Nk, long vt_bstride, float* lse) {
     if (rc || dry) return;
-    AttnArgs a; std::memset(&a, 0, sizeof(a));
-    a.vt_bstride = vt_bstride;
-    a.Q = Q; a.ldq = ldq; a.K = K; a.ldk = ldk; a.Vt = Vt; a.ldvt = ldvt; a.O = O; a.ldo = C;
-    a.B = B; a.H = heads; a.D = C / heads; a.Nq = Nq; a.Nk = Nk;
-    a.scale = 1.0f / sqrtf((float)a.D); a.lse = lse;
+    AttnArgs a = attn_args(Q, ldq, K, ldk, Vt, ldvt, C, heads, Nq, Nk, vt_bstride);
+    a.O = O; a.lse = lse;
     rc = dfh::attention_launch(a, s);
   }
   void attention_bwd(const bf16_t* Q, int ldq, const bf16_t* K, int ldk, const bf16_t* V, int ldv, const bf16_t* O,
@@ -242,11 +210,11 @@ struct dfh_unet::TrainRun {
     f.Hin = H; f.Win = W; f.Hout = H; f.Wout = W; f.stride = 1; f.rows_per_b = H * W;
     f.W = WP; f.ldw = 4 * Ci; f.bias = v32(c.b); f.out = o.p;
     gemm(f);
-    const size_t mark = gtemp.off;
+    const size_t mark = temp.off;
     bf16_t* dyp = gbuf((size_t)4 * M * Co);
     bf16_t* dxp = gbuf((size_t)4 * M * Ci);
-    float* dwp = (float*)gtemp.alloc((size_t)16 * Co * Ci * sizeof(float));
-    gtemp.off = mark;
+    float* dwp = (float*)temp.alloc((size_t)16 * Co * Ci * sizeof(float));
+    temp.off = mark;
     const ConvL* cp = &c;
     tape.push_back([=] {
       TR_OP(dfh::phase_gather_launch(o.g, dyp, B, H, W, Co, s));
@@ -281,13 +249,13 @@ struct dfh_unet::TrainRun {
     const int Ho = ups ? x.H * 2 : (stride == 2 ? x.H / 2 : x.H);
     const int Wo = ups ? x.W * 2 : (stride == 2 ? x.W / 2 : x.W);
     GT o = act(Ho, Wo, c.cout, true);
-    GemmArgs f = conv_desc(x.p, x.C, x.H, x.W, Ho, Wo, stride, ups, c.cout);
-    f.W = w16(c.w); f.ldw = c.w.K; f.bias = v32(c.b); f.out = o.p;
+    GemmArgs f = conv_desc(x.p, x.C, x.H, x.W, Ho, Wo, stride, ups, c.w, c.b);
+    f.out = o.p;
     gemm(f);
-    const size_t mark = gtemp.off;
+    const size_t mark = temp.off;
     bf16_t* full = ups ? gbuf((size_t)B * Ho * Wo * x.C) : nullptr;      // dgrad at 2H before the 2x2 sum pool
     bf16_t* pooled = ups ? gbuf((size_t)B * x.H * x.W * x.C) : nullptr;
-    gtemp.off = mark;
+    temp.off = mark;
     const ConvL* cp = &c;
     tape.push_back([=] {
       const int M = B * Ho * Wo;
@@ -310,21 +278,19 @@ struct dfh_unet::TrainRun {
     const bool has1 = x1p != nullptr;
     const GT x1 = has1 ? *x1p : GT{};
     GT out = act(H, W, r.cout, true);
-    const size_t mark = gtemp.off;
+    const size_t mark = temp.off;
     GT g1 = act(H, W, r.cin);
     float* st1 = fbuf((size_t)B * G * 2);
     groupnorm(x0, x1p, r.n1w, r.n1b, u->cfg.norm_eps, 1, g1.p, st1);
     GT h1 = act(H, W, r.cout);
-    GemmArgs f1 = conv_desc(g1.p, r.cin, H, W, H, W, 1, 0, r.cout);
-    f1.W = w16(r.w1); f1.ldw = r.w1.K; f1.bias = v32(r.b1);
+    GemmArgs f1 = conv_desc(g1.p, r.cin, H, W, H, W, 1, 0, r.w1, r.b1);
     f1.rowvec = temb_all; f1.rv_ld = u->temb_total; f1.rv_off = r.temb_off; f1.rows_per_b = H * W;
     f1.out = h1.p;
     gemm(f1);
     GT g2 = act(H, W, r.cout);
     float* st2 = fbuf((size_t)B * G * 2);
     groupnorm(h1, nullptr, r.n2w, r.n2b, u->cfg.norm_eps, 1, g2.p, st2);
-    GemmArgs f2 = conv_desc(g2.p, r.cout, H, W, H, W, 1, 0, r.cout);
-    f2.W = w16(r.w2); f2.ldw = r.w2.K; f2.bias = v32(r.b2);
+    GemmArgs f2 = conv_desc(g2.p, r.cout, H, W, H, W, 1, 0, r.w2, r.b2);
     if (r.shortcut) {
       f2.p_src[0] = x0.p; f2.p_c[0] = x0.C; f2.nplain = 1;
       if (has1) { f2.p_src[1] = x1.p; f2.p_c[1] = x1.C; f2.nplain = 2; }
@@ -333,7 +299,7 @@ struct dfh_unet::TrainRun {
     }
     f2.out = out.p;
     gemm(f2);
-    gtemp.off = mark;
+    temp.off = mark;
     const ResL* rp = &r;
     tape.push_back([=] {
       const ResL& r = *rp;
@@ -361,7 +327,7 @@ struct dfh_unet::TrainRun {
     const int H = x.H, W = x.W, C = a.C, N = H * W, M = B * N, heads = a.heads;
     const int G = u->cfg.norm_num_groups, XT = u->x_total;
     GT out = act(H, W, C, true);
-    const size_t mark = gtemp.off;
+    const size_t mark = temp.off;
     const size_t MC = (size_t)M * C;
     GT gn = act(H, W, C);
     float* st = fbuf((size_t)B * G * 2);
@@ -405,10 +371,8 @@ struct dfh_unet::TrainRun {
     static const bool geglu_split = [] { const char* e = getenv("DFH_TRAIN_GEGLU_FUSED"); return e && e[0] == '0'; }();
     GemmArgs f_ff1;
     if (!geglu_split && (8 * C) % 128 == 0) {
-      f_ff1 = base(M, 8 * C);
-      f_ff1.p_src[0] = n3.p; f_ff1.p_c[0] = C; f_ff1.nplain = 1;
-      f_ff1.W = w16(a.ff1); f_ff1.ldw = a.ff1.K; f_ff1.bias = v32(a.ff1b);
-      f_ff1.act = ACT_GEGLU; f_ff1.out = ff.p; f_ff1.ld_out = 4 * C; f_ff1.pre_out = ffpre.p; f_ff1.ld_pre = 8 * C;
+      f_ff1 = linear_desc(n3.p, M, C, a.ff1, &a.ff1b, nullptr, ff.p, 8 * C);
+      f_ff1.act = ACT_GEGLU; f_ff1.ld_out = 4 * C; f_ff1.pre_out = ffpre.p; f_ff1.ld_pre = 8 * C;
       gemm(f_ff1);
     } else {
       f_ff1 = linear(n3.p, M, C, a.ff1, &a.ff1b, nullptr, ffpre.p, 8 * C);
@@ -416,7 +380,7 @@ struct dfh_unet::TrainRun {
     }
     GemmArgs f_ff2 = linear(ff.p, M, 4 * C, a.ff2, &a.ff2b, h2, h3, C);
     GemmArgs f_pout = linear(h3, M, C, a.pout, &a.poutb, x.p, out.p, C);
-    gtemp.off = mark;
+    temp.off = mark;
     const AttL* ap = &a;
     tape.push_back([=] {
       const AttL& a = *ap;
@@ -513,8 +477,8 @@ struct dfh_unet::TrainRun {
     TR_OP(dfh::nchw_to_nhwc_launch(sample, sample_bf16, x.p, B, cfg.in_channels, S * S, s));
     GT h = act(S, S, boc[0], true);
     {
-      GemmArgs f = conv_desc(x.p, x.C, S, S, S, S, 1, 0, boc[0]);
-      f.W = w16(U.conv_in.w); f.ldw = U.conv_in.w.K; f.bias = v32(U.conv_in.b); f.out = h.p;
+      GemmArgs f = conv_desc(x.p, x.C, S, S, S, S, 1, 0, U.conv_in.w, U.conv_in.b);
+      f.out = h.p;
       gemm(f);
       const GT h0 = h;
       tape.push_back([=] {
@@ -553,8 +517,7 @@ struct dfh_unet::TrainRun {
       GT g = act(S, S, h.C, true);
       float* st = fbuf((size_t)B * G * 2);
       groupnorm(h, nullptr, U.cnw, U.cnb, cfg.norm_eps, 1, g.p, st);
-      GemmArgs f = conv_desc(g.p, g.C, S, S, S, S, 1, 0, Co);
-      f.W = w16(U.conv_out.w); f.ldw = U.conv_out.w.K; f.bias = v32(U.conv_out.b);
+      GemmArgs f = conv_desc(g.p, g.C, S, S, S, S, 1, 0, U.conv_out.w, U.conv_out.b);
       f.out = out; f.out_mode = OUT_F32_T; f.ld_out = S * S; f.rows_per_b = S * S;
       gemm(f);
       bf16_t* dy = buf((size_t)M * Cop);
@@ -639,20 +602,16 @@ int dfh_unet::build_train() {
   return 0;
 }
 
-namespace {
-size_t head_bytes_for(int B, size_t partial) {
-  Bump hd; hd.alloc(256); hd.alloc((size_t)B * GN_MAX_CHUNKS * 64 * 2 * sizeof(float)); hd.alloc(partial); hd.alloc(partial);
-  return (hd.off + 255) & ~(size_t)255;
-}
-}
+// the training head has two slab regions: the main stream's and the side stream's (TrainRun::wgrad)
+static size_t head_bytes_for(int B, size_t partial) { return WorkspaceHead(nullptr, B, partial, 2).bytes; }
 
 size_t dfh_unet::plan_train(int B) {
   build_train();
-  TrainRun r; r.u = this; r.B = B; r.dry = true;
+  TrainRun r(this, B, nullptr, true);
   r.walk(nullptr, 0, nullptr, nullptr, 0, nullptr);
   for (auto it = r.tape.rbegin(); it != r.tape.rend(); ++it) (*it)();
   const size_t partial = (r.partial_need + 255) & ~(size_t)255;
-  tplan_total = head_bytes_for(B, partial) + ((r.persist.peak + 255) & ~(size_t)255) + ((r.gtemp.peak + 255) & ~(size_t)255) + 256;
+  tplan_total = head_bytes_for(B, partial) + ((r.persist.peak + 255) & ~(size_t)255) + ((r.temp.peak + 255) & ~(size_t)255) + 256;
   tplan_batch = B;
   return tplan_total;
 }
@@ -660,24 +619,21 @@ size_t dfh_unet::plan_train(int B) {
 int dfh_unet::forward_train(const void* sample, int sample_bf16, const float* timestep, const void* ehs, int ehs_bf16, float* out,
                             int B, hipStream_t s) {
   // size the regions for this batch with a dry walk, then lay them out in the bound workspace
-  TrainRun plan; plan.u = this; plan.B = B; plan.dry = true;
+  TrainRun plan(this, B, nullptr, true);
   plan.walk(nullptr, 0, nullptr, nullptr, 0, nullptr);
   for (int i = (int)plan.tape.size() - 1; i >= 0; --i) { plan.cur_entry = i; plan.tape[i](); }
   const size_t partial = (plan.partial_need + 255) & ~(size_t)255;
-  const size_t persist_bytes = (plan.persist.peak + 255) & ~(size_t)255, gtemp_bytes = (plan.gtemp.peak + 255) & ~(size_t)255;
+  const size_t persist_bytes = (plan.persist.peak + 255) & ~(size_t)255, gtemp_bytes = (plan.temp.peak + 255) & ~(size_t)255;
   const size_t head = head_bytes_for(B, partial);
   DFH_REQUIRE(head + persist_bytes + gtemp_bytes <= tws_bytes, "training workspace too small for this batch");
   delete tr;
-  tr = new TrainRun();
+  tr = new TrainRun(this, B, s, false);
   TrainRun& r = *tr;
-  r.u = this; r.B = B; r.s = s; r.dry = false;
-  Bump hd; hd.base = tws;
-  r.zero = (bf16_t*)hd.alloc(256);
-  r.gn_partial = (float*)hd.alloc((size_t)B * GN_MAX_CHUNKS * 64 * 2 * sizeof(float));
-  r.partial = (float*)hd.alloc(partial); r.partial_cap = partial;
-  r.partial2 = (float*)hd.alloc(partial);
+  const WorkspaceHead hd(tws, B, partial, 2);
+  r.bind_head(hd);
+  r.partial2 = hd.slab[1];
   r.persist.base = tws + head;
-  r.gtemp.base = tws + head + persist_bytes;
+  r.temp.base = tws + head + persist_bytes;
   (void)hipMemsetAsync(r.zero, 0, 256, s);
   r.walk(sample, sample_bf16, timestep, ehs, ehs_bf16, out);
   r.writes = std::move(plan.writes);          // same walk, same tape: entry i of the dry tape is entry i of this one

@@ -13,7 +13,8 @@
 //     next to the convs (4 x 34 GFLOP per image against 1.2 TFLOP), so it runs as three GEMMs per image -- S = Q K^T
 //     (fp32 out), row softmax (softmax_rows_kernel), O = P V against V^T from the transposed epilogue;
 //   * 3-channel images / 4-channel latents are padded to one 16-byte NHWC pixel (8 channels), conv_out to 4 outputs.
-#include "unet_model.h"
+#include "walk_common.h"
+#include "elementwise.h"
 
 namespace {
 
@@ -45,68 +46,45 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 
 }  // namespace
 
-struct dfh_vae {
+struct dfh_vae : ParamTable {
   dfh_vae_config cfg{};
-  std::vector<ParamDesc> params;
-  std::vector<PackOp> packs;
-  size_t a16 = 0, a32 = 0;
   // layers
   VConv e_in, e_out, d_in, d_out, quant, post_quant;
   std::vector<std::vector<VRes>> e_res, d_res;
   std::vector<VConv> e_down, d_up;
   VRes e_mid[2], d_mid[2]; VAtt e_att, d_att;
   Vec e_nw, e_nb, d_nw, d_nb;
-  // bound memory
-  bf16_t* arena16 = nullptr; float* arena32 = nullptr;
+  // bound memory (the arenas: ParamTable)
   char* ws = nullptr; size_t ws_bytes = 0;
-  OpTable tab_pack, tab_pack_acc;
 
-  // ---------------------------------------------------------------- build (same packing conventions as unet_model.h)
-  int add_param(const std::string& name, std::vector<int> shape) { params.push_back({name, std::move(shape)}); return (int)params.size() - 1; }
-  size_t alloc16(size_t n) { size_t o = a16; a16 += (n + 127) & ~(size_t)127; return o; }
-  size_t alloc32(size_t n) { size_t o = a32; a32 += (n + 63) & ~(size_t)63; return o; }
-  Vec vec(const std::string& name, int N, int npad = 0) {
-    Vec v; v.N = npad ? npad : N; v.off = alloc32(v.N);
-    packs.push_back({add_param(name, {N}), PK_VEC, v.off, N, 0, 0, 0, 0, 0, 0});
-    return v;
-  }
-  Mat mat_alloc(int N, int K) { Mat m; m.N = N; m.K = K; m.off = alloc16((size_t)N * K); return m; }
-  void conv_into(const std::string& name, int cout, int cin, const Mat& dst, int cin_pad) {
-    PackOp op{add_param(name, {cout, cin, 3, 3}), PK_CONV3, dst.off, cout, cin, dst.K, 0, 0, 0, 0};
-    op.cin_pad = cin_pad;
-    packs.push_back(op);
-  }
-  void mat_into(const std::string& name, int N, int K, bool conv1x1, const Mat& dst, int col_off) {
-    std::vector<int> shape = conv1x1 ? std::vector<int>{N, K, 1, 1} : std::vector<int>{N, K};
-    packs.push_back({add_param(name, shape), PK_MAT, dst.off, N, K, dst.K, 0, col_off, 0, 0});
-  }
+  // ---------------------------------------------------------------- build
   void build_conv(const std::string& pre, int cout, int cin, VConv& c) {
     const int cp = (cin + 7) & ~7;
     c.cin = cp; c.cout = cout; c.npad = (cout + 3) & ~3;            // GEMM N is a multiple of 4: padded rows stay zero
     c.w = mat_alloc(c.npad, 9 * cp);
-    conv_into(pre + ".weight", cout, cin, c.w, cp);
+    conv_into(pre + ".weight", cout, cin, c.w, 0, cp);
     c.b = vec(pre + ".bias", cout, c.npad);
   }
   void build_conv1x1(const std::string& pre, int cout, int cin, VConv& c) {
     const int cp = (cin + 7) & ~7;
     c.cin = cp; c.cout = cout; c.npad = (cout + 3) & ~3;
     c.w = mat_alloc(c.npad, cp);
-    mat_into(pre + ".weight", cout, cin, true, c.w, 0);
+    mat_into(pre + ".weight", cout, cin, true, c.w, 0, 0, 0);
     c.b = vec(pre + ".bias", cout, c.npad);
   }
   void build_resnet(const std::string& pre, int cin, int cout, VRes& r) {
     r.cin = cin; r.cout = cout; r.shortcut = cin != cout;
     r.n1w = vec(pre + ".norm1.weight", cin); r.n1b = vec(pre + ".norm1.bias", cin);
     r.w1 = mat_alloc(cout, 9 * cin);
-    conv_into(pre + ".conv1.weight", cout, cin, r.w1, cin);
+    conv_into(pre + ".conv1.weight", cout, cin, r.w1, 0);
     r.b1 = vec(pre + ".conv1.bias", cout);
     r.n2w = vec(pre + ".norm2.weight", cout); r.n2b = vec(pre + ".norm2.bias", cout);
     r.w2 = mat_alloc(cout, 9 * cout + (r.shortcut ? cin : 0));
-    conv_into(pre + ".conv2.weight", cout, cout, r.w2, cout);
+    conv_into(pre + ".conv2.weight", cout, cout, r.w2, 0);
     r.b2 = vec(pre + ".conv2.bias", cout);
     if (r.shortcut) {
-      mat_into(pre + ".conv_shortcut.weight", cout, cin, true, r.w2, 9 * cout);
-      packs.push_back({add_param(pre + ".conv_shortcut.bias", {cout}), PK_VEC, r.b2.off, cout, 0, 0, 0, 0, 0, /*accumulate=*/1});
+      mat_into(pre + ".conv_shortcut.weight", cout, cin, true, r.w2, 0, 9 * cout, 0);
+      vec_into(pre + ".conv_shortcut.bias", cout, r.b2.off, 0, /*accumulate=*/1);
     }
   }
   void build_mid(const std::string& pre, int C, VRes* res, VAtt& a) {
@@ -115,8 +93,7 @@ struct dfh_vae {
     a.C = C;
     a.gw = vec(ap + ".group_norm.weight", C); a.gb = vec(ap + ".group_norm.bias", C);
     auto lin = [&](const std::string& n, Mat& m, Vec& b) {
-      m = mat_alloc(C, C);
-      mat_into(ap + "." + n + ".weight", C, C, false, m, 0);
+      m = mat(ap + "." + n + ".weight", C, C);
       b = vec(ap + "." + n + ".bias", C);
     };
     lin("to_q", a.q, a.qb); lin("to_k", a.k, a.kb); lin("to_v", a.v, a.vb); lin("to_out.0", a.o, a.ob);
@@ -157,59 +134,22 @@ struct dfh_vae {
     return 0;
   }
 
-  int pack(const float* const* master, int count, hipStream_t s) {
-    DFH_REQUIRE(count == (int)params.size(), "parameter count mismatch");
-    DFH_REQUIRE(arena16 && arena32, "arenas not bound");
-    tab_pack.clear(); tab_pack_acc.clear();
-    for (const PackOp& op : packs) {
-      void* src = (void*)master[op.param];
-      DFH_REQUIRE(src != nullptr, "null master parameter: " + params[op.param].name);
-      if (op.kind == PK_VEC) (op.accumulate ? tab_pack_acc : tab_pack).add(src, TAB_PACK_VEC, (long)op.dst, op.N, 0, 0, 0, op.accumulate, 0, 0, op.N);
-      else if (op.kind == PK_MAT) tab_pack.add(src, TAB_PACK_MAT, (long)op.dst, op.N, op.K, op.ldw, 0, op.col_off, 0, 0, (long)op.N * op.K);
-      else tab_pack.add(src, TAB_PACK_CONV, (long)op.dst, op.N, op.K, op.ldw, 0, op.col_off, 0, op.cin_pad, (long)op.N * op.K * 9);
-    }
-    if (int rc = tab_pack.launch(arena32, arena16, s)) return rc;
-    return tab_pack_acc.launch(arena32, arena16, s);
-  }
-
   // ---------------------------------------------------------------- run
-  struct Run {
-    dfh_vae* u; int B; hipStream_t s; bool dry;
-    Bump persist, temp; size_t partial_need = 0;
-    float* partial = nullptr; size_t partial_cap = 0; float* gn_partial = nullptr; bf16_t* zero = nullptr;
-    int rc = 0;
-    bf16_t* w16(const Mat& m) const { return u->arena16 + m.off; }
-    float* v32(const Vec& v) const { return u->arena32 + v.off; }
+  struct Run : WalkBase {
+    Run(dfh_vae* u, int B_, hipStream_t s_, bool dry_) : WalkBase(*u, u->cfg.norm_num_groups, B_, s_, dry_) {}
     Tensor talloc(int H, int W, int C) { return Tensor{(bf16_t*)temp.alloc((size_t)B * H * W * C * 2), H, W, C}; }
     Tensor palloc(int H, int W, int C) { return Tensor{(bf16_t*)persist.alloc((size_t)B * H * W * C * 2), H, W, C}; }
-    void gemm(GemmArgs g) {
-      if (rc) return;
-      g.zero = zero; g.partial = partial;
-      if (dry) { partial_need = std::max(partial_need, dfh::gemm_partial_floats(g) * sizeof(float)); return; }
-      if (dfh::gemm_partial_floats(g) * sizeof(float) > partial_cap) { dfh::set_error("split-K partial buffer too small"); rc = -1; return; }
-      rc = dfh::gemm_launch(g, s);
-    }
-    static GemmArgs base(int M, int N) {
-      GemmArgs g; std::memset(&g, 0, sizeof(g));
-      g.M = M; g.N = N; g.rows_per_b = M; g.out_mode = OUT_BF16; g.ld_out = N;
-      return g;
-    }
     void groupnorm(const Tensor& x, const Vec& w, const Vec& b, int silu, Tensor& out) {
       if (rc || dry) return;
-      GnArgs a; std::memset(&a, 0, sizeof(a));
-      a.src0 = x.p; a.C0 = x.C; a.B = B; a.HW = x.H * x.W; a.G = u->cfg.norm_num_groups;
-      a.gamma = v32(w); a.beta = v32(b); a.eps = 1e-6f; a.silu = silu; a.out = out.p; a.partial = gn_partial;
-      rc = dfh::groupnorm_launch(a, s);
+      rc = dfh::groupnorm_launch(gn_args(x.p, x.C, nullptr, 0, x.H * x.W, w, b, 1e-6f, silu, out.p), s);
     }
     // 3x3 conv; mode 0 same size, 1 stride 2 over the right/bottom zero-extended input, 2 fused nearest-2x upsample
     Tensor conv(const Tensor& x, const VConv& c, int mode, bool to_persist, void* f32_nchw_out = nullptr) {
       const int Ho = mode == 2 ? x.H * 2 : (mode == 1 ? x.H / 2 : x.H), Wo = mode == 2 ? x.W * 2 : (mode == 1 ? x.W / 2 : x.W);
       const int ldo = (c.npad + 7) & ~7;      // narrow outputs (4 latent channels) land in a zero-filled 8-channel pixel
       Tensor o{nullptr, Ho, Wo, ldo};
-      GemmArgs g = base(B * Ho * Wo, c.npad);
-      g.conv_src = x.p; g.conv_c = x.C; g.ntaps = 9;
-      g.Hin = x.H; g.Win = x.W; g.Hout = Ho; g.Wout = Wo; g.stride = mode == 1 ? 2 : 1; g.ups = mode == 2 ? 1 : 0; g.pad0 = mode == 1;
-      g.W = w16(c.w); g.ldw = c.w.K; g.bias = v32(c.b);
+      GemmArgs g = conv_desc(x.p, x.C, x.H, x.W, Ho, Wo, mode == 1 ? 2 : 1, mode == 2 ? 1 : 0, c.w, c.b);   // c.w.N = c.npad
+      g.pad0 = mode == 1;
       if (f32_nchw_out) { g.out = f32_nchw_out; g.out_mode = OUT_F32_T; g.ld_out = Ho * Wo; g.rows_per_b = Ho * Wo; }
       else {
         o.p = (bf16_t*)(to_persist ? persist : temp).alloc((size_t)B * Ho * Wo * ldo * 2);
@@ -227,17 +167,14 @@ struct dfh_vae {
       groupnorm(x, r.n1w, r.n1b, 1, g1);
       Tensor h1 = talloc(H, W, r.cout);
       {
-        GemmArgs g = base(B * H * W, r.cout);
-        g.conv_src = g1.p; g.conv_c = r.cin; g.ntaps = 9; g.Hin = H; g.Win = W; g.Hout = H; g.Wout = W; g.stride = 1;
-        g.W = w16(r.w1); g.ldw = r.w1.K; g.bias = v32(r.b1); g.out = h1.p;
+        GemmArgs g = conv_desc(g1.p, r.cin, H, W, H, W, 1, 0, r.w1, r.b1);
+        g.out = h1.p;
         gemm(g);
       }
       Tensor g2 = talloc(H, W, r.cout);
       groupnorm(h1, r.n2w, r.n2b, 1, g2);
       {
-        GemmArgs g = base(B * H * W, r.cout);
-        g.conv_src = g2.p; g.conv_c = r.cout; g.ntaps = 9; g.Hin = H; g.Win = W; g.Hout = H; g.Wout = W; g.stride = 1;
-        g.W = w16(r.w2); g.ldw = r.w2.K; g.bias = v32(r.b2);
+        GemmArgs g = conv_desc(g2.p, r.cout, H, W, H, W, 1, 0, r.w2, r.b2);
         if (r.shortcut) { g.p_src[0] = x.p; g.p_c[0] = x.C; g.nplain = 1; }
         else { g.resid = x.p; g.ld_res = r.cout; }
         g.out = out.p;
@@ -248,10 +185,9 @@ struct dfh_vae {
     }
     void linear(const bf16_t* x, int M, int K, const Mat& W, const Vec* bias, const bf16_t* resid, void* out, int N, int out_mode = OUT_BF16,
                 int ld_out = -1, int rows_per_b = 0) {
-      GemmArgs g = base(M, N);
-      g.p_src[0] = x; g.p_c[0] = K; g.nplain = 1;
-      g.W = w16(W); g.ldw = W.K; g.bias = bias ? v32(*bias) : nullptr; g.resid = resid; g.ld_res = N;
-      g.out = out; g.out_mode = out_mode; if (ld_out >= 0) g.ld_out = ld_out; if (rows_per_b) g.rows_per_b = rows_per_b;
+      GemmArgs g = linear_desc(x, M, K, W, bias, resid, out, N, out_mode);
+      if (ld_out >= 0) g.ld_out = ld_out;
+      if (rows_per_b) g.rows_per_b = rows_per_b;
       gemm(g);
     }
     Tensor attention(const Tensor& x, const VAtt& a) {
@@ -297,13 +233,11 @@ struct dfh_vae {
 
   // plan + layout shared by encode / decode
   int run(bool encode, const float* in, float* out, int B, int size, hipStream_t s, bool dry, size_t* need) {
-    Run r; r.u = this; r.B = B; r.s = s; r.dry = dry;
-    Bump head; head.base = dry ? nullptr : ws;
-    r.zero = (bf16_t*)head.alloc(256);
-    r.gn_partial = (float*)head.alloc((size_t)B * GN_MAX_CHUNKS * 64 * 2 * sizeof(float));
+    Run r(this, B, s, dry);
     // region sizes come from a dry pass of the same walk (plan_* below)
-    r.partial = (float*)head.alloc(dry ? 0 : plan_partial); r.partial_cap = dry ? 0 : plan_partial;
-    const size_t head_bytes = (head.off + 255) & ~(size_t)255;
+    const WorkspaceHead head(dry ? nullptr : ws, B, dry ? 0 : plan_partial);
+    r.bind_head(head);
+    const size_t head_bytes = head.bytes;
     if (!dry) {
       r.persist.base = ws + head_bytes; r.temp.base = ws + head_bytes + plan_persist;
       if (head_bytes + plan_persist + plan_temp > ws_bytes) { dfh::set_error("VAE workspace too small"); return -1; }
@@ -323,24 +257,14 @@ struct dfh_vae {
       r.groupnorm(h, e_nw, e_nb, 1, g);
       Tensor m = r.conv(g, e_out, 0, true);                         // [M][2L] bf16 (2L = 8)
       // quant_conv 1x1 -> fp32 NCHW moments
-      GemmArgs q = Run::base(B * m.H * m.W, quant.npad);
-      q.p_src[0] = m.p; q.p_c[0] = m.C; q.nplain = 1;
-      q.W = r.w16(quant.w); q.ldw = quant.w.K; q.bias = r.v32(quant.b);
-      q.out = out; q.out_mode = OUT_F32_T; q.ld_out = m.H * m.W; q.rows_per_b = m.H * m.W;
-      r.gemm(q);
+      r.linear(m.p, B * m.H * m.W, m.C, quant.w, &quant.b, nullptr, out, quant.npad, OUT_F32_T, m.H * m.W, m.H * m.W);
     } else {
       Tensor z = r.palloc(size, size, post_quant.cin);
       if (!dry) r.rc = dfh::nchw_to_nhwc_launch(in, 0, z.p, B, cfg.latent_channels, size * size, s);
       // post_quant_conv 1x1 into a zero-filled 8-channel pixel
       Tensor pq = r.palloc(size, size, d_in.cin);
       if (!dry && !r.rc) (void)hipMemsetAsync(pq.p, 0, (size_t)B * size * size * pq.C * 2, s);
-      {
-        GemmArgs g = Run::base(B * size * size, post_quant.npad);
-        g.p_src[0] = z.p; g.p_c[0] = z.C; g.nplain = 1;
-        g.W = r.w16(post_quant.w); g.ldw = post_quant.w.K; g.bias = r.v32(post_quant.b);
-        g.out = pq.p; g.ld_out = pq.C;
-        r.gemm(g);
-      }
+      r.linear(z.p, B * size * size, z.C, post_quant.w, &post_quant.b, nullptr, pq.p, post_quant.npad, OUT_BF16, pq.C);
       Tensor h = r.conv(pq, d_in, 0, true);
       h = r.resnet(h, d_mid[0]); h = r.attention(h, d_att); h = r.resnet(h, d_mid[1]);
       for (int i = 0; i < nb; ++i) {
@@ -355,8 +279,7 @@ struct dfh_vae {
       plan_persist = (r.persist.peak + 255) & ~(size_t)255;
       plan_temp = (r.temp.peak + 255) & ~(size_t)255;
       plan_partial = (r.partial_need + 255) & ~(size_t)255;
-      Bump hd; hd.alloc(256); hd.alloc((size_t)B * GN_MAX_CHUNKS * 64 * 2 * sizeof(float)); hd.alloc(plan_partial);
-      if (need) *need = ((hd.off + 255) & ~(size_t)255) + plan_persist + plan_temp;
+      if (need) *need = WorkspaceHead(nullptr, B, plan_partial).bytes + plan_persist + plan_temp;
     }
     return r.rc;
   }
@@ -380,12 +303,12 @@ int dfh_vae_create(const dfh_vae_config* cfg, dfh_vae** out) {
   return 0;
 }
 void dfh_vae_destroy(dfh_vae* u) { delete u; }
-int dfh_vae_num_params(const dfh_vae* u) { return (int)u->params.size(); }
-const char* dfh_vae_param_name(const dfh_vae* u, int i) { return u->params[i].name.c_str(); }
-int dfh_vae_param_ndim(const dfh_vae* u, int i) { return (int)u->params[i].shape.size(); }
-int dfh_vae_param_dim(const dfh_vae* u, int i, int d) { return u->params[i].shape[d]; }
-size_t dfh_vae_arena16_bytes(const dfh_vae* u) { return u->a16 * 2 + 256; }
-size_t dfh_vae_arena32_bytes(const dfh_vae* u) { return u->a32 * 4 + 256; }
+int dfh_vae_num_params(const dfh_vae* u) { return u->num_params(); }
+const char* dfh_vae_param_name(const dfh_vae* u, int i) { return u->param_name(i); }
+int dfh_vae_param_ndim(const dfh_vae* u, int i) { return u->param_ndim(i); }
+int dfh_vae_param_dim(const dfh_vae* u, int i, int d) { return u->param_dim(i, d); }
+size_t dfh_vae_arena16_bytes(const dfh_vae* u) { return u->arena16_bytes(); }
+size_t dfh_vae_arena32_bytes(const dfh_vae* u) { return u->arena32_bytes(); }
 
 size_t dfh_vae_workspace_bytes(dfh_vae* u, int encode, int batch, int size) {
   size_t need = 0;
@@ -401,7 +324,7 @@ int dfh_vae_bind(dfh_vae* u, void* arena16, void* arena32, void* workspace, size
 }
 int dfh_vae_pack(dfh_vae* u, const float* const* master_params, int count, void* stream) {
   DFH_REQUIRE(u && master_params, "null argument");
-  return u->pack(master_params, count, (hipStream_t)stream);
+  return u->pack_params(master_params, count, (hipStream_t)stream);
 }
 static int vae_run(dfh_vae* u, bool encode, const float* in, float* out, int batch, int size, void* stream) {
   DFH_REQUIRE(u && in && out, "null argument");
