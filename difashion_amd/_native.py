@@ -1,0 +1,182 @@
+"""What the native-backed model wrappers (unet.py, vae.py, clip.py; the checkpoint part also mutual.py) share: the Python
+counterpart of csrc/walk_common.h.
+
+``NativeModule`` drives one family of C entry points (``dfh_<family>_create / _destroy / _num_params / _param_name / _param_ndim /
+_param_dim``): handle lifecycle, the parameter tree built from the C table, the table-ordered parameter list, the pack signature and
+the device / dtype guard.  A subclass supplies ``family``, ``_c_config()`` and what is its own (DESIGN.md section 3 lists which
+differences between the wrappers are deliberate).  The free functions are the checkpoint-directory halves every wrapper uses.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import os
+from typing import Callable, Optional
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+
+
+class FrozenDict(dict):
+    """diffusers-style config: attribute and mapping access."""
+
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError as e:
+            raise AttributeError(k) from e
+
+
+class _Node(nn.Module):
+    """Bare container used to rebuild the diffusers module tree from dotted parameter names."""
+
+
+def pack_signature(params):
+    """What a packed copy of ``params`` was made from: storage and version of every tensor, and the epoch the fused optimizer bumps
+    when a native kernel rewrites master weights in place."""
+    return tuple((p.data_ptr(), p._version) for p in params) + (_lib.weight_epoch(),)
+
+
+def save_checkpoint(module: nn.Module, save_directory: str, extra: dict, weights_name: Optional[str] = None):
+    """``config.json`` (the module's config, then ``extra``) + the state dict as one safetensors file."""
+    from safetensors.torch import save_file
+    os.makedirs(save_directory, exist_ok=True)
+    cfg = dict(module.config)
+    cfg.update(extra)
+    with open(os.path.join(save_directory, module.config_name), "w") as f:
+        json.dump(cfg, f, indent=2)
+    save_file({k: v.detach().cpu().contiguous() for k, v in module.state_dict().items()},
+              os.path.join(save_directory, weights_name or module.weights_name))
+
+
+def read_checkpoint_config(cls, path: str, subfolder: Optional[str] = None):
+    """(checkpoint directory, its config without the ``_``-prefixed bookkeeping keys)."""
+    d = os.path.join(path, subfolder) if subfolder else path
+    with open(os.path.join(d, cls.config_name)) as f:
+        cfg = json.load(f)
+    return d, {k: v for k, v in cfg.items() if not k.startswith("_")}
+
+
+class NativeModule(nn.Module):
+    family: str = ""                     # entry-point prefix: dfh_<family>_*
+    config_name = "config.json"
+    weights_name = "diffusion_pytorch_model.safetensors"
+    _fp32_rule = "master parameters must stay fp32 (the kernels pack their own bf16 copies)"
+    _ctx = None
+    _names = None
+    _packed_sig = None
+
+    # ------------------------------------------------------------------ native handle
+    def _c_config(self):
+        raise NotImplementedError
+
+    @classmethod
+    def _entry(cls, name: str):
+        return getattr(_lib.raw(), f"dfh_{cls.family}_{name}")
+
+    def _make_ctx(self):
+        c = self._c_config()
+        h = C.c_void_p()
+        _lib.call(f"dfh_{self.family}_create", C.byref(c), C.byref(h))
+        return h
+
+    @classmethod
+    def _table(cls, ctx):
+        name, ndim, dim = cls._entry("param_name"), cls._entry("param_ndim"), cls._entry("param_dim")
+        return [(name(ctx, i).decode(), tuple(dim(ctx, i, d) for d in range(ndim(ctx, i)))) for i in range(cls._entry("num_params")(ctx))]
+
+    def param_table(self):
+        """[(checkpoint key, shape)] as the native library enumerates them."""
+        ctx = self._make_ctx()
+        try:
+            return self._table(ctx)
+        finally:
+            self._entry("destroy")(ctx)
+
+    def _destroy_ctx(self):
+        if self._ctx is not None:
+            self._entry("destroy")(self._ctx)
+            self._ctx = None
+
+    def __del__(self):
+        try:
+            self._destroy_ctx()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------------ parameters
+    def _build_parameters(self, table, is_norm: Callable[[str], bool], init_seed: Optional[int], init_std: float,
+                          unseeded_zeros: bool = False):
+        """The parameter tree straight from the C table (single source of truth for names and shapes): ``_Node`` containers down
+        the dotted name; an entry whose module already holds the parameter (the U-Net's real ``conv_in``) is filled in place.
+        Non-norm weights are one ``randn(shape) * init_std`` each, in table order, from a CPU generator that is seeded only when
+        ``init_seed`` is given; without a seed they are zeros if ``unseeded_zeros`` (a checkpoint follows).  Norm weights are ones,
+        everything else zeros."""
+        g = torch.Generator(device="cpu")
+        if init_seed is not None:
+            g.manual_seed(init_seed)
+        for name, shape in table:
+            if not name.endswith(".weight"):
+                t = torch.zeros(shape)
+            elif is_norm(name):
+                t = torch.ones(shape)
+            elif init_seed is None and unseeded_zeros:
+                t = torch.zeros(shape)
+            else:
+                t = torch.randn(shape, generator=g) * init_std
+            *path, leaf = name.split(".")
+            m = self
+            for p in path:
+                if p not in m._modules:
+                    m.add_module(p, _Node())
+                m = m._modules[p]
+            if leaf in m._parameters:
+                m._parameters[leaf].data.copy_(t)
+            else:
+                m.register_parameter(leaf, nn.Parameter(t))
+
+    def _params_by_name(self):
+        return dict(self.named_parameters())
+
+    def _plist(self):
+        """The parameters in table order.  Resolved by name on every call: modules get replaced (the pipeline swaps the U-Net's
+        ``conv_in``), and a cached list would hand the kernels a dead tensor."""
+        named = self._params_by_name()
+        return [named[n] for n in self._names]
+
+    _signature = staticmethod(pack_signature)
+
+    @staticmethod
+    def _pointers(plist):
+        return (C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
+
+    def _pack_with(self, entry_name: str, force: bool = False):
+        """Run pack entry point ``entry_name`` over the master parameters unless the packed copy is still current."""
+        plist = self._plist()
+        sig = self._signature(plist)
+        if not force and sig == self._packed_sig:
+            return
+        _lib.call(entry_name, self._ctx, self._pointers(plist), len(plist), _lib.stream_ptr())
+        self._packed_sig = sig
+
+    # ------------------------------------------------------------------ plumbing
+    def register_to_config(self, **kwargs):
+        self.config.update(kwargs)
+
+    @property
+    def device(self) -> torch.device:
+        return next(self.parameters()).device
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return next(self.parameters()).dtype
+
+    def _require_hip_fp32(self, what: str) -> torch.device:
+        dev = self.device
+        if dev.type != "cuda":
+            raise _lib.DfhError(f"{what} runs only on the MI355X HIP path: move it to 'cuda' (no CPU fallback)")
+        if self.dtype != torch.float32:
+            raise _lib.DfhError(self._fp32_rule)
+        return dev

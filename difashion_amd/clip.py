@@ -13,16 +13,12 @@ to summation-order noise.  The fp32 ``nn.Parameter``s are read in place (no pack
 """
 from __future__ import annotations
 
-import ctypes as C
-import json
-import os
 from typing import Optional
 
 import torch
-import torch.nn as nn
 
 from . import _lib
-from .unet import FrozenDict, _Node
+from ._native import FrozenDict, NativeModule, read_checkpoint_config, save_checkpoint
 
 _ACT = {"quick_gelu": 1, "gelu": 2}
 
@@ -47,8 +43,10 @@ class BaseModelOutputWithPooling:
         return len(self.to_tuple())
 
 
-class CLIPTextModel(nn.Module):
-    config_name = "config.json"
+class CLIPTextModel(NativeModule):
+    family = "clip"
+    weights_name = "model.safetensors"
+    _fp32_rule = "parameters must stay fp32 (the kernels read them in place)"
 
     def __init__(self, vocab_size: int = 49408, hidden_size: int = 768, intermediate_size: int = 3072, num_hidden_layers: int = 12,
                  num_attention_heads: int = 12, max_position_embeddings: int = 77, hidden_act: str = "quick_gelu",
@@ -63,68 +61,15 @@ class CLIPTextModel(nn.Module):
                                  eos_token_id=eos_token_id, bos_token_id=bos_token_id, pad_token_id=pad_token_id)
         self._ctx = None
         self._ws = None
-        ctx = self._make_ctx()
-        try:
-            self._names = [n for n, _ in self._table(ctx)]
-            table = self._table(ctx)
-        finally:
-            _lib.raw().dfh_clip_destroy(ctx)
-        g = torch.Generator(device="cpu")
-        if init_seed is not None:
-            g.manual_seed(init_seed)
-        for name, shape in table:
-            norm = "layer_norm" in name.split(".")[-2]
-            if name.endswith(".weight") and not norm:
-                t = torch.randn(shape, generator=g) * init_std if init_seed is not None else torch.zeros(shape)
-            elif name.endswith(".weight"):
-                t = torch.ones(shape)
-            else:
-                t = torch.zeros(shape)
-            m = self
-            parts = name.split(".")
-            for p in parts[:-1]:
-                if p not in m._modules:
-                    m.add_module(p, _Node())
-                m = m._modules[p]
-            m.register_parameter(parts[-1], nn.Parameter(t))
+        table = self.param_table()
+        self._names = [n for n, _ in table]             # no bind / pack step that would fill them later: the masters are read in place
+        self._build_parameters(table, lambda name: "layer_norm" in name.split(".")[-2], init_seed, init_std, unseeded_zeros=True)
 
     # ------------------------------------------------------------------ plumbing
-    @property
-    def device(self) -> torch.device:
-        return next(self.parameters()).device
-
-    @property
-    def dtype(self) -> torch.dtype:
-        return next(self.parameters()).dtype
-
-    def _make_ctx(self):
+    def _c_config(self) -> _lib.CLIPConfigC:
         cfg = self.config
-        c = _lib.CLIPConfigC(cfg["vocab_size"], cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"],
-                             cfg["num_attention_heads"], cfg["max_position_embeddings"], _ACT[cfg["hidden_act"]], cfg["layer_norm_eps"])
-        h = C.c_void_p()
-        _lib.call("dfh_clip_create", C.byref(c), C.byref(h))
-        return h
-
-    @staticmethod
-    def _table(ctx):
-        lib = _lib.raw()
-        return [(lib.dfh_clip_param_name(ctx, i).decode(),
-                 tuple(lib.dfh_clip_param_dim(ctx, i, d) for d in range(lib.dfh_clip_param_ndim(ctx, i))))
-                for i in range(lib.dfh_clip_num_params(ctx))]
-
-    def param_table(self):
-        ctx = self._make_ctx()
-        try:
-            return self._table(ctx)
-        finally:
-            _lib.raw().dfh_clip_destroy(ctx)
-
-    def __del__(self):
-        try:
-            if self._ctx is not None:
-                _lib.raw().dfh_clip_destroy(self._ctx)
-        except Exception:
-            pass
+        return _lib.CLIPConfigC(cfg["vocab_size"], cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"],
+                                cfg["num_attention_heads"], cfg["max_position_embeddings"], _ACT[cfg["hidden_act"]], cfg["layer_norm_eps"])
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts the 4.32.1 layout (``text_model.*``, what published checkpoints hold), the flattened layout of newer transformers
@@ -145,11 +90,7 @@ class CLIPTextModel(nn.Module):
         if attention_mask is not None or position_ids is not None or output_attentions:
             raise NotImplementedError("the reference calls text_encoder(input_ids) only (difashion.py:224,340): no padding mask, "
                                       "default positions, no attention maps on this path")
-        dev = self.device
-        if dev.type != "cuda":
-            raise _lib.DfhError("CLIPTextModel runs only on the MI355X HIP path: move it to 'cuda' (no CPU fallback)")
-        if self.dtype != torch.float32:
-            raise _lib.DfhError("parameters must stay fp32 (the kernels read them in place)")
+        dev = self._require_hip_fp32("CLIPTextModel")
         cfg = self.config
         shape = tuple(input_ids.shape)
         T = shape[-1]
@@ -169,11 +110,10 @@ class CLIPTextModel(nn.Module):
         need = lib.dfh_clip_workspace_bytes(self._ctx, B, T)
         if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
             self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        named = dict(self.named_parameters())
-        plist = [named[n] for n in self._names]
+        plist = self._plist()
         if any(p.device != dev or not p.is_contiguous() for p in plist):
             raise _lib.DfhError("all parameters must be contiguous and on one device")
-        arr = (C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
+        arr = self._pointers(plist)
         D, L = cfg["hidden_size"], cfg["num_hidden_layers"]
         last = torch.empty((B, T, D), dtype=torch.float32, device=dev)
         pooled = torch.empty((B, D), dtype=torch.float32, device=dev)
@@ -185,21 +125,12 @@ class CLIPTextModel(nn.Module):
 
     # ------------------------------------------------------------------ checkpoints (transformers directory layout)
     def save_pretrained(self, save_directory: str, **unused):
-        from safetensors.torch import save_file
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = dict(self.config)
-        cfg.update(architectures=["CLIPTextModel"], model_type="clip_text_model")
-        with open(os.path.join(save_directory, self.config_name), "w") as f:
-            json.dump(cfg, f, indent=2)
-        save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()},
-                  os.path.join(save_directory, "model.safetensors"))
+        save_checkpoint(self, save_directory, dict(architectures=["CLIPTextModel"], model_type="clip_text_model"))
 
     @classmethod
     def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, revision=None, **unused):
         from ._ckpt import TRANSFORMERS_STEMS, load_weights
-        d = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(d, cls.config_name)) as f:
-            cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
+        d, cfg = read_checkpoint_config(cls, path, subfolder)
         model = cls(init_seed=None, **cfg)
         model.load_state_dict(load_weights(d, variant, TRANSFORMERS_STEMS))
         return model

@@ -9,14 +9,13 @@ GEMV-like problem (16.8 MB of bf16 weights): both linears go through dfh_gemm (s
 from __future__ import annotations
 
 import ctypes as C
-import json
-import os
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import FrozenDict, pack_signature, read_checkpoint_config, save_checkpoint
 
 ACT_LEAKY, ACT_TANH = 2, 3
 OUT_BF16, OUT_F32 = 0, 2
@@ -39,24 +38,14 @@ class _MutualStep(torch.autograd.Function):
         return None, None, None, None
 
 
-class _Config(dict):
-    """diffusers-style config: attribute and mapping access (the reference reads ``fashion_encoder.config`` both ways)."""
-
-    def __getattr__(self, k):
-        try:
-            return self[k]
-        except KeyError as e:
-            raise AttributeError(k) from e
-
-
 class MutualEncoder(nn.Module):
     config_name = "config.json"
     weights_name = "diffusion_pytorch_model.safetensors"
 
     def __init__(self, cate_num: int, cate_emb_size: int, latent_channels: int, latent_size: int, hid_dim: int, **unused):
         super().__init__()
-        self.config = _Config(cate_num=cate_num, cate_emb_size=cate_emb_size, latent_channels=latent_channels,
-                              latent_size=latent_size, hid_dim=hid_dim)
+        self.config = FrozenDict(cate_num=cate_num, cate_emb_size=cate_emb_size, latent_channels=latent_channels,
+                                 latent_size=latent_size, hid_dim=hid_dim)
         self.category_embedding = nn.Embedding(cate_num, cate_emb_size)  # unused in forward (difashion.py:28)
         self.latent_channels = latent_channels
         self.latent_size = latent_size
@@ -74,21 +63,12 @@ class MutualEncoder(nn.Module):
         self.config.update(kwargs)
 
     def save_pretrained(self, save_directory: str, **unused):
-        from safetensors.torch import save_file
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = dict(self.config)
-        cfg["_class_name"] = "MutualEncoder"
-        with open(os.path.join(save_directory, self.config_name), "w") as f:
-            json.dump(cfg, f, indent=2)
-        save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()},
-                  os.path.join(save_directory, self.weights_name))
+        save_checkpoint(self, save_directory, dict(_class_name="MutualEncoder"))
 
     @classmethod
     def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, **unused):
         from ._ckpt import load_weights
-        d = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(d, cls.config_name)) as f:
-            cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
+        d, cfg = read_checkpoint_config(cls, path, subfolder)
         ctor = {k: cfg[k] for k in ("cate_num", "cate_emb_size", "latent_channels", "latent_size", "hid_dim")}
         model = cls(**ctor)
         model.register_to_config(**cfg)          # extra keys (e.g. EMA state written by EMAModel.save_pretrained) survive
@@ -99,7 +79,7 @@ class MutualEncoder(nn.Module):
         w1, b1, w2, b2 = self.mlp[0].weight, self.mlp[0].bias, self.mlp[3].weight, self.mlp[3].bias
         if w1.device.type != "cuda":
             raise _lib.DfhError("MutualEncoder runs on the HIP path only: move it to 'cuda'")
-        sig = tuple((p.data_ptr(), p._version) for p in (w1, b1, w2, b2)) + (_lib.weight_epoch(),)
+        sig = pack_signature((w1, b1, w2, b2))
         if sig == self._sig:
             return self._packed
         dev = w1.device

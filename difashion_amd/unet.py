@@ -23,29 +23,19 @@ the bf16 kernel layouts whenever they change.  There is no PyTorch/CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
-import json
 import os
-from typing import Dict, Optional, Sequence, Tuple, Union
+from typing import Optional, Sequence, Union
 
 import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import FrozenDict, NativeModule, _Node, read_checkpoint_config, save_checkpoint  # noqa: F401  (FrozenDict / _Node: re-exported)
 
 
 class UNet2DConditionOutput:
     def __init__(self, sample: torch.Tensor):
         self.sample = sample
-
-
-class FrozenDict(dict):
-    """diffusers-style config: attribute and mapping access."""
-
-    def __getattr__(self, k):
-        try:
-            return self[k]
-        except KeyError as e:
-            raise AttributeError(k) from e
 
 
 class _UNetStep(torch.autograd.Function):
@@ -64,10 +54,6 @@ class _UNetStep(torch.autograd.Function):
         if d_sample is not None and d_sample.dtype != ctx.in_dtype:
             d_sample = d_sample.to(ctx.in_dtype)
         return None, d_sample, None, None, None
-
-
-class _Node(nn.Module):
-    """Bare container used to rebuild the diffusers module tree from dotted parameter names."""
 
 
 _DEFAULT_DOWN = ("CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "CrossAttnDownBlock2D", "DownBlock2D")
@@ -104,9 +90,8 @@ def _reject_unsupported_config(extra: dict):
         raise _lib.DfhError("UNet2DConditionModel: config not implemented by the HIP walk: " + "; ".join(bad))
 
 
-class UNet2DConditionModel(nn.Module):
-    config_name = "config.json"
-    weights_name = "diffusion_pytorch_model.safetensors"
+class UNet2DConditionModel(NativeModule):
+    family = "unet"
 
     def __init__(self, sample_size: int = 64, in_channels: int = 4, out_channels: int = 4,
                  down_block_types: Sequence[str] = _DEFAULT_DOWN, up_block_types: Sequence[str] = _DEFAULT_UP,
@@ -144,47 +129,12 @@ class UNet2DConditionModel(nn.Module):
         self._train_batch = 0
         self._grad_flat = None
         self._anchor = None
-        # parameter tree straight from the C table (single source of truth for names and shapes)
-        ctx = self._make_ctx()
-        try:
-            table = self._table(ctx)
-        finally:
-            _lib.raw().dfh_unet_destroy(ctx)
-        g = torch.Generator(device="cpu")
-        if init_seed is not None:
-            g.manual_seed(init_seed)
+        # conv_in is a real nn.Conv2d (the pipeline replaces it): its table entries are filled in place.  With init_seed=None the
+        # weights are still drawn, from the unseeded generator
         self.conv_in = nn.Conv2d(in_channels, block_out_channels[0], 3, 1, 1)
-        for name, shape in table:
-            is_norm = ".norm" in name or name.startswith("conv_norm_out")
-            if name.endswith(".weight") and not is_norm:
-                t = torch.randn(shape, generator=g) * init_std
-            elif name.endswith(".weight"):
-                t = torch.ones(shape)
-            else:
-                t = torch.zeros(shape)
-            if name.startswith("conv_in."):
-                getattr(self.conv_in, name.split(".")[1]).data.copy_(t)
-                continue
-            parts = name.split(".")
-            m = self
-            for p in parts[:-1]:
-                if p not in m._modules:
-                    m.add_module(p, _Node())
-                m = m._modules[p]
-            m.register_parameter(parts[-1], nn.Parameter(t))
+        self._build_parameters(self.param_table(), lambda name: ".norm" in name or name.startswith("conv_norm_out"), init_seed, init_std)
 
     # ------------------------------------------------------------------ config plumbing
-    def register_to_config(self, **kwargs):
-        self.config.update(kwargs)
-
-    @property
-    def device(self) -> torch.device:
-        return next(self.parameters()).device
-
-    @property
-    def dtype(self) -> torch.dtype:
-        return next(self.parameters()).dtype
-
     def enable_gradient_checkpointing(self):
         return None
 
@@ -230,44 +180,9 @@ class UNet2DConditionModel(nn.Module):
         c.text_len = cfg["text_len"]
         return c
 
-    def _make_ctx(self):
-        c = self._c_config()
-        h = C.c_void_p()
-        _lib.call("dfh_unet_create", C.byref(c), C.byref(h))
-        return h
-
-    @staticmethod
-    def _table(ctx):
-        lib = _lib.raw()
-        out = []
-        for i in range(lib.dfh_unet_num_params(ctx)):
-            name = lib.dfh_unet_param_name(ctx, i).decode()
-            shape = tuple(lib.dfh_unet_param_dim(ctx, i, d) for d in range(lib.dfh_unet_param_ndim(ctx, i)))
-            out.append((name, shape))
-        return out
-
-    def param_table(self):
-        """[(diffusers key, shape)] as the native library enumerates them."""
-        ctx = self._make_ctx()
-        try:
-            return self._table(ctx)
-        finally:
-            _lib.raw().dfh_unet_destroy(ctx)
-
-    def __del__(self):
-        try:
-            if self._ctx is not None:
-                _lib.raw().dfh_unet_destroy(self._ctx)
-        except Exception:
-            pass
-
     # ------------------------------------------------------------------ device state
     def _ensure_ctx(self, batch: int):
-        dev = self.device
-        if dev.type != "cuda":
-            raise _lib.DfhError("UNet2DConditionModel runs only on the MI355X HIP path: move it to 'cuda' (no CPU fallback)")
-        if self.dtype != torch.float32:
-            raise _lib.DfhError("master parameters must stay fp32 (the kernels pack their own bf16 copies)")
+        dev = self._require_hip_fp32("UNet2DConditionModel")
         in_ch = int(self.conv_in.weight.shape[1])
         if tuple(self.conv_in.kernel_size) != (3, 3) or tuple(self.conv_in.padding) != (1, 1) or tuple(self.conv_in.stride) != (1, 1):
             raise _lib.DfhError("conv_in must be a 3x3 / stride 1 / padding 1 convolution")
@@ -276,13 +191,11 @@ class UNet2DConditionModel(nn.Module):
         key = (in_ch, self.max_batch, dev.index, self.fp8, self.fp8_attention, tuple(sorted((k, str(v)) for k, v in self.config.items())))
         if self._ctx is not None and key == self._ctx_key:
             return
-        if self._ctx is not None:
-            _lib.raw().dfh_unet_destroy(self._ctx)
-            self._ctx = None
+        self._destroy_ctx()
         ctx = self._make_ctx()
         lib = _lib.raw()
         table = self._table(ctx)
-        params = dict(self.named_parameters())
+        params = self._params_by_name()
         for name, shape in table:
             if name not in params or tuple(params[name].shape) != shape:
                 lib.dfh_unet_destroy(ctx)
@@ -337,23 +250,11 @@ class UNet2DConditionModel(nn.Module):
         # ALWAYS (re-)registered, null included: the native side must never keep a pointer into a tensor this module has dropped
         _lib.call("dfh_unet_grad_sumsq", ctx, _lib.ptr(self._grad_sumsq) if self._grad_sumsq is not None else None)
 
-    def _signature(self, params):
-        return tuple((p.data_ptr(), p._version) for p in params) + (_lib.weight_epoch(),)
-
     def pack(self, force: bool = False):
         """fp32 master parameters -> bf16 kernel layouts (call happens automatically when they change)."""
         self._ensure_ctx(1)
-        named = dict(self.named_parameters())
-        plist = [named[n] for n in self._names]
-        sig = self._signature(plist)
-        if not force and sig == self._packed_sig:
-            return
-        arr = (C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
-        if self._train_buffers is not None:      # plain + transposed packs from ONE read of the masters
-            _lib.call("dfh_unet_pack_all", self._ctx, arr, len(plist), _lib.stream_ptr())
-        else:
-            _lib.call("dfh_unet_pack", self._ctx, arr, len(plist), _lib.stream_ptr())
-        self._packed_sig = sig
+        # with training arenas bound: plain + transposed packs from ONE read of the masters
+        self._pack_with("dfh_unet_pack_all" if self._train_buffers is not None else "dfh_unet_pack", force)
 
     # ------------------------------------------------------------------ per-run constants of a sampling loop
     def prepare_run(self, encoder_hidden_states: torch.Tensor, timesteps) -> None:
@@ -430,8 +331,7 @@ class UNet2DConditionModel(nn.Module):
     def grad_views(self):
         """Table-order list of the parameters' gradient tensors, creating missing ones as zero-filled views of one
         flat fp32 buffer (the layout the fused optimizer and the RCCL gradient all-reduce work on)."""
-        named = dict(self.named_parameters())
-        plist = [named[n] for n in self._names]
+        plist = self._plist()
         missing = [p for p in plist if p.requires_grad and p.grad is None]
         if missing:
             if self._grad_flat is None or self._grad_flat.device != self.device:
@@ -504,8 +404,7 @@ class UNet2DConditionModel(nn.Module):
         ``data_ptr`` moved: loss-scale un-scaling, ``clip_grad_norm_``, ``grad.mul_``) -- the optimizer then sums the squares itself."""
         if not self._grad_sumsq_ok or self._grad_sumsq is None or self._grad_sumsq_stamp is None:
             return False
-        named = dict(self.named_parameters())
-        plist = [named[n] for n in self._names]
+        plist = self._plist()
         if len(plist) != len(self._grad_sumsq_stamp):
             return False
         return all(p.grad is not None and (p.grad.data_ptr(), p.grad._version) == st for p, st in zip(plist, self._grad_sumsq_stamp))
@@ -655,23 +554,12 @@ class UNet2DConditionModel(nn.Module):
 
     # ------------------------------------------------------------------ checkpoints (diffusers directory layout)
     def save_pretrained(self, save_directory: str, **unused):
-        from safetensors.torch import save_file
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = dict(self.config)
-        cfg["in_channels"] = int(self.conv_in.weight.shape[1])
-        cfg["_class_name"] = "UNet2DConditionModel"
-        with open(os.path.join(save_directory, self.config_name), "w") as f:
-            json.dump(cfg, f, indent=2)
-        save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()},
-                  os.path.join(save_directory, self.weights_name))
+        save_checkpoint(self, save_directory, dict(in_channels=int(self.conv_in.weight.shape[1]), _class_name="UNet2DConditionModel"))
 
     @classmethod
     def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, **kwargs):
         from ._ckpt import load_weights
-        d = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(d, cls.config_name)) as f:
-            cfg = json.load(f)
-        cfg = {k: v for k, v in cfg.items() if not k.startswith("_")}
+        d, cfg = read_checkpoint_config(cls, path, subfolder)
         cfg.update({k: v for k, v in kwargs.items() if k in ("max_batch",)})
         model = cls(init_seed=None, **cfg)
         # keys the constructor does not know (e.g. the EMA state diffusers' EMAModel.save_pretrained adds) stay in .config

@@ -12,16 +12,12 @@ packed to bf16 GEMM layouts when they change.  No PyTorch / CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes as C
-import json
-import os
 from typing import Optional, Sequence
 
 import torch
-import torch.nn as nn
 
 from . import _lib
-from .unet import FrozenDict, _Node
+from ._native import FrozenDict, NativeModule, read_checkpoint_config, save_checkpoint
 
 
 class DiagonalGaussianDistribution:
@@ -52,9 +48,8 @@ class DecoderOutput:
         self.sample = sample
 
 
-class AutoencoderKL(nn.Module):
-    config_name = "config.json"
-    weights_name = "diffusion_pytorch_model.safetensors"
+class AutoencoderKL(NativeModule):
+    family = "vae"
 
     def __init__(self, in_channels: int = 3, out_channels: int = 3, latent_channels: int = 4,
                  block_out_channels: Sequence[int] = (128, 256, 512, 512), layers_per_block: int = 2, norm_num_groups: int = 32,
@@ -71,43 +66,10 @@ class AutoencoderKL(nn.Module):
         self._dev_buffers = None
         self._ws_bytes = 0
         self._packed_sig = None
-        ctx = self._make_ctx()
-        try:
-            table = self._table(ctx)
-        finally:
-            _lib.raw().dfh_vae_destroy(ctx)
-        g = torch.Generator(device="cpu")
-        if init_seed is not None:
-            g.manual_seed(init_seed)
-        for name, shape in table:
-            is_norm = "norm" in name.split(".")[-2]
-            if name.endswith(".weight") and not is_norm:
-                t = torch.randn(shape, generator=g) * init_std if init_seed is not None else torch.zeros(shape)
-            elif name.endswith(".weight"):
-                t = torch.ones(shape)
-            else:
-                t = torch.zeros(shape)
-            parts = name.split(".")
-            m = self
-            for p in parts[:-1]:
-                if p not in m._modules:
-                    m.add_module(p, _Node())
-                m = m._modules[p]
-            m.register_parameter(parts[-1], nn.Parameter(t))
+        self._build_parameters(self.param_table(), lambda name: "norm" in name.split(".")[-2], init_seed, init_std, unseeded_zeros=True)
 
     # ------------------------------------------------------------------ plumbing
-    def register_to_config(self, **kwargs):
-        self.config.update(kwargs)
-
-    @property
-    def device(self) -> torch.device:
-        return next(self.parameters()).device
-
-    @property
-    def dtype(self) -> torch.dtype:
-        return next(self.parameters()).dtype
-
-    def _make_ctx(self):
+    def _c_config(self) -> _lib.VAEConfigC:
         cfg = self.config
         c = _lib.VAEConfigC()
         c.in_channels, c.out_channels, c.latent_channels = cfg["in_channels"], cfg["out_channels"], cfg["latent_channels"]
@@ -115,37 +77,10 @@ class AutoencoderKL(nn.Module):
         for i, v in enumerate(cfg["block_out_channels"]):
             c.block_out_channels[i] = v
         c.layers_per_block, c.norm_num_groups = cfg["layers_per_block"], cfg["norm_num_groups"]
-        h = C.c_void_p()
-        _lib.call("dfh_vae_create", C.byref(c), C.byref(h))
-        return h
-
-    @staticmethod
-    def _table(ctx):
-        lib = _lib.raw()
-        return [(lib.dfh_vae_param_name(ctx, i).decode(),
-                 tuple(lib.dfh_vae_param_dim(ctx, i, d) for d in range(lib.dfh_vae_param_ndim(ctx, i))))
-                for i in range(lib.dfh_vae_num_params(ctx))]
-
-    def param_table(self):
-        ctx = self._make_ctx()
-        try:
-            return self._table(ctx)
-        finally:
-            _lib.raw().dfh_vae_destroy(ctx)
-
-    def __del__(self):
-        try:
-            if self._ctx is not None:
-                _lib.raw().dfh_vae_destroy(self._ctx)
-        except Exception:
-            pass
+        return c
 
     def _ensure(self, encode: bool, batch: int, size: int):
-        dev = self.device
-        if dev.type != "cuda":
-            raise _lib.DfhError("AutoencoderKL runs only on the MI355X HIP path: move it to 'cuda' (no CPU fallback)")
-        if self.dtype != torch.float32:
-            raise _lib.DfhError("master parameters must stay fp32 (the kernels pack their own bf16 copies)")
+        dev = self._require_hip_fp32("AutoencoderKL")
         lib = _lib.raw()
         if self._ctx is None:
             self._ctx = self._make_ctx()
@@ -167,14 +102,7 @@ class AutoencoderKL(nn.Module):
         self.pack()
 
     def pack(self, force: bool = False):
-        named = dict(self.named_parameters())
-        plist = [named[n] for n in self._names]
-        sig = tuple((p.data_ptr(), p._version) for p in plist) + (_lib.weight_epoch(),)
-        if not force and sig == self._packed_sig:
-            return
-        arr = (C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
-        _lib.call("dfh_vae_pack", self._ctx, arr, len(plist), _lib.stream_ptr())
-        self._packed_sig = sig
+        self._pack_with("dfh_vae_pack", force)
 
     # ------------------------------------------------------------------ the two calls of the reference
     @torch.no_grad()
@@ -214,21 +142,12 @@ class AutoencoderKL(nn.Module):
 
     # ------------------------------------------------------------------ checkpoints (diffusers directory layout)
     def save_pretrained(self, save_directory: str, **unused):
-        from safetensors.torch import save_file
-        os.makedirs(save_directory, exist_ok=True)
-        cfg = dict(self.config)
-        cfg["_class_name"] = "AutoencoderKL"
-        with open(os.path.join(save_directory, self.config_name), "w") as f:
-            json.dump(cfg, f, indent=2)
-        save_file({k: v.detach().cpu().contiguous() for k, v in self.state_dict().items()},
-                  os.path.join(save_directory, self.weights_name))
+        save_checkpoint(self, save_directory, dict(_class_name="AutoencoderKL"))
 
     @classmethod
     def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, **unused):
         from ._ckpt import load_weights, remap_deprecated_vae_attention
-        d = os.path.join(path, subfolder) if subfolder else path
-        with open(os.path.join(d, cls.config_name)) as f:
-            cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
+        d, cfg = read_checkpoint_config(cls, path, subfolder)
         model = cls(init_seed=None, **cfg)
         # published SD VAE weights still name the mid-block attention query / key / value / proj_attn (diffusers renames on load)
         model.load_state_dict(remap_deprecated_vae_attention(load_weights(d, variant)))

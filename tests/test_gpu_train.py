@@ -481,9 +481,8 @@ def test_pack_all_writes_the_same_arenas_as_pack_plus_pack_train(cfg):
     a16, a32 = m._buffers_dev[0], m._buffers_dev[1]
     a16t = m._train_buffers[0]
     got = (a16.clone(), a32.clone(), a16t.clone())
-    named = dict(m.named_parameters())
-    plist = [named[n] for n in m._names]
-    arr = (C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
+    plist = m._plist()
+    arr =(C.c_void_p * len(plist))(*[p.data_ptr() for p in plist])
     for buf in (a16, a32, a16t):
         buf.zero_()
     _lib.call("dfh_unet_pack", m._ctx, arr, len(plist), _lib.stream_ptr())
