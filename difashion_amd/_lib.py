@@ -57,6 +57,12 @@ class CLIPConfigC(C.Structure):
                 ("layer_norm_eps", C.c_float)]
 
 
+class CLIPVisionConfigC(C.Structure):
+    _fields_ = [("hidden_size", C.c_int), ("intermediate_size", C.c_int), ("num_hidden_layers", C.c_int), ("num_attention_heads", C.c_int),
+                ("image_size", C.c_int), ("patch_size", C.c_int), ("num_channels", C.c_int), ("projection_dim", C.c_int),
+                ("hidden_act", C.c_int), ("layer_norm_eps", C.c_float)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [
         ("conv_src", C.c_void_p), ("conv_c", C.c_int), ("conv", C.c_int),
@@ -138,6 +144,15 @@ SIGNATURES = {
     "dfh_clip_param_dim": (_i, [_vp, _i, _i]),
     "dfh_clip_workspace_bytes": (_sz, [_vp, _i, _i]),
     "dfh_clip_encode": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _i, _i, _vp]),
+    "dfh_clipv_create": (_i, [C.POINTER(CLIPVisionConfigC), C.POINTER(_vp)]),
+    "dfh_clipv_destroy": (None, [_vp]),
+    "dfh_clipv_num_params": (_i, [_vp]),
+    "dfh_clipv_param_name": (C.c_char_p, [_vp, _i]),
+    "dfh_clipv_param_ndim": (_i, [_vp, _i]),
+    "dfh_clipv_param_dim": (_i, [_vp, _i, _i]),
+    "dfh_clipv_workspace_bytes": (_sz, [_vp, _i]),
+    "dfh_clipv_encode": (_i, [_vp, C.POINTER(_vp), _i, _vp, _i, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "dfh_clipv_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "dfh_vae_create": (_i, [C.POINTER(VAEConfigC), C.POINTER(_vp)]),
     "dfh_vae_destroy": (None, [_vp]),
     "dfh_vae_num_params": (_i, [_vp]),
@@ -247,7 +262,8 @@ SIGNATURES = {
     "dfh_mse_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
 }
 _NO_STATUS = {"dfh_abi_version", "dfh_census_count", "dfh_unet_num_params", "dfh_unet_param_ndim", "dfh_unet_param_dim", "dfh_vae_num_params",
-              "dfh_vae_param_ndim", "dfh_vae_param_dim", "dfh_clip_num_params", "dfh_clip_param_ndim", "dfh_clip_param_dim"}
+              "dfh_vae_param_ndim", "dfh_vae_param_dim", "dfh_clip_num_params", "dfh_clip_param_ndim", "dfh_clip_param_dim",
+              "dfh_clipv_num_params", "dfh_clipv_param_ndim", "dfh_clipv_param_dim"}
 
 _lib = None
 _UNBOUND = set()

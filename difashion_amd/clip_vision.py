@@ -1,0 +1,148 @@
+"""``CLIPVisionModelWithProjection`` on the MI355X HIP path, behind the transformers call signature.
+
+What the reference's evaluation scripts require of the image side of their OpenCLIP ViT-H/14:
+  * ``model.encode_image(images)`` on batches of preprocessed 224 x 224 images -- Evaluation/extract_hist_embs.py:83-100 (history
+    embeddings per user), Evaluation/eval_utils.py:91-135 (CLIP score, CLIP image score), :503-535 (personalisation similarity).
+This class is that shared feature extractor under the architecture and the state-dict key names of
+``transformers.CLIPVisionModelWithProjection`` (``vision_model.*`` with transformers' own ``pre_layrnorm`` spelling,
+``visual_projection.weight``); ``open_clip`` checkpoints must be exported under those names first.  Resizing /
+normalising the images and the metrics computed from the embeddings stay with the caller.
+
+All arithmetic runs in the kernel library (``dfh_clipv_encode``, csrc/clip_vision.hip) in fp32 on the fp32 matrix instruction, in
+both storage builds.  The fp32 ``nn.Parameter``s are read in place (no packed copy).  No PyTorch / CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from . import _lib
+from ._native import FrozenDict, NativeModule, read_checkpoint_config, save_checkpoint
+
+_ACT = {"quick_gelu": 1, "gelu": 2}
+
+
+class CLIPVisionModelOutput:
+    """transformers' output object: ``.image_embeds`` / ``[0]``, ``.last_hidden_state`` / ``[1]``, ``.hidden_states``; plus
+    ``.pooler_output`` (the post-LayerNorm class token that ``visual_projection`` reads), which the evaluation tests compare too."""
+
+    def __init__(self, image_embeds, last_hidden_state, pooler_output, hidden_states=None):
+        self.image_embeds, self.last_hidden_state, self.pooler_output = image_embeds, last_hidden_state, pooler_output
+        self.hidden_states = hidden_states
+
+    def to_tuple(self):
+        return tuple(v for v in (self.image_embeds, self.last_hidden_state, self.hidden_states) if v is not None)
+
+    def __getitem__(self, i):
+        return self.to_tuple()[i]
+
+    def __iter__(self):
+        return iter(self.to_tuple())
+
+    def __len__(self):
+        return len(self.to_tuple())
+
+
+class CLIPVisionModelWithProjection(NativeModule):
+    family = "clipv"
+    weights_name = "model.safetensors"
+    _fp32_rule = "parameters must stay fp32 (the kernels read them in place)"
+
+    def __init__(self, hidden_size: int = 1280, intermediate_size: int = 5120, projection_dim: int = 1024, num_hidden_layers: int = 32,
+                 num_attention_heads: int = 16, num_channels: int = 3, image_size: int = 224, patch_size: int = 14,
+                 hidden_act: str = "gelu", layer_norm_eps: float = 1e-5, init_seed: Optional[int] = 0, init_std: float = 0.02, **unused):
+        super().__init__()
+        if hidden_act not in _ACT:
+            raise ValueError(f"hidden_act {hidden_act!r}: the CLIP vision towers use 'quick_gelu' (OpenAI ViT-L/14) / 'gelu' (OpenCLIP ViT-H/14)")
+        self.config = FrozenDict(hidden_size=hidden_size, intermediate_size=intermediate_size, projection_dim=projection_dim,
+                                 num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads, num_channels=num_channels,
+                                 image_size=image_size, patch_size=patch_size, hidden_act=hidden_act, layer_norm_eps=layer_norm_eps)
+        self._ctx = None
+        self._ws = None
+        table = self.param_table()
+        self._names = [n for n, _ in table]             # the masters are read in place: no bind / pack step
+        self._build_parameters(table, lambda name: "norm" in name.split(".")[-2], init_seed, init_std, unseeded_zeros=True)
+
+    # ------------------------------------------------------------------ plumbing
+    def _c_config(self) -> _lib.CLIPVisionConfigC:
+        cfg = self.config
+        return _lib.CLIPVisionConfigC(cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"],
+                                      cfg["image_size"], cfg["patch_size"], cfg["num_channels"], cfg["projection_dim"],
+                                      _ACT[cfg["hidden_act"]], cfg["layer_norm_eps"])
+
+    @property
+    def num_tokens(self) -> int:
+        return 1 + (self.config["image_size"] // self.config["patch_size"]) ** 2
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """Drops the ``position_ids`` buffer that checkpoints written by older transformers releases carry."""
+        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.endswith("position_ids")}, strict=strict, **kw)
+
+    # ------------------------------------------------------------------ model(pixel_values)
+    @torch.no_grad()
+    def forward(self, pixel_values: Optional[torch.Tensor] = None, attention_mask=None, output_attentions=None,
+                output_hidden_states: Optional[bool] = None, interpolate_pos_encoding: bool = False, return_dict: Optional[bool] = None):
+        if pixel_values is None:
+            raise ValueError("You have to specify pixel_values")
+        if attention_mask is not None or output_attentions:
+            raise NotImplementedError("the vision tower attends over all patches: no attention mask, no attention maps on this path")
+        if interpolate_pos_encoding:
+            raise NotImplementedError("interpolate_pos_encoding=True is not built: resize the images to the model's image_size "
+                                      "(the evaluation scripts' preprocessing does)")
+        dev = self._require_hip_fp32("CLIPVisionModelWithProjection")
+        cfg = self.config
+        S, Cn = cfg["image_size"], cfg["num_channels"]
+        if pixel_values.dim() != 4 or pixel_values.shape[1] != Cn:
+            raise ValueError(f"pixel_values must be [batch, {Cn}, {S}, {S}] (num_channels = {Cn}), got {tuple(pixel_values.shape)}")
+        if tuple(pixel_values.shape[2:]) != (S, S):
+            raise ValueError(f"Input image size ({pixel_values.shape[2]}*{pixel_values.shape[3]}) doesn't match model ({S}*{S}).")
+        if pixel_values.dtype != torch.float32:
+            raise TypeError(f"pixel_values must be float32 (the tower is fp32 end to end), got {pixel_values.dtype}")
+        if pixel_values.device != dev:
+            raise _lib.DfhError(f"pixel_values live on {pixel_values.device}, the model on {dev}: move them to the model's device "
+                                "(no CPU fallback)")
+        B = pixel_values.shape[0]
+        if B < 1:
+            raise ValueError("pixel_values holds no image")
+        px = pixel_values.contiguous()
+        lib = _lib.raw()
+        if self._ctx is None:
+            self._ctx = self._make_ctx()
+        need = lib.dfh_clipv_workspace_bytes(self._ctx, B)
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
+            self._ws = None                              # release the old block before asking for the larger one
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        plist = self._plist()
+        if any(p.device != dev or not p.is_contiguous() for p in plist):
+            raise _lib.DfhError("all parameters must be contiguous and on one device")
+        arr = self._pointers(plist)
+        D, L, T = cfg["hidden_size"], cfg["num_hidden_layers"], self.num_tokens
+        last = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+        pooled = torch.empty((B, D), dtype=torch.float32, device=dev)
+        embeds = torch.empty((B, cfg["projection_dim"]), dtype=torch.float32, device=dev)
+        hs = taps = None
+        if output_hidden_states:
+            hs = torch.empty((L + 1, B, T, D), dtype=torch.float32, device=dev)
+            taps = (C.c_void_p * (L + 1))(*[hs[i].data_ptr() for i in range(L + 1)])
+        _lib.call("dfh_clipv_encode", self._ctx, arr, len(plist), _lib.ptr(px), B, _lib.ptr(last), _lib.ptr(pooled), _lib.ptr(embeds),
+                  taps, _lib.ptr(self._ws), self._ws.numel(), _lib.stream_ptr())
+        out = CLIPVisionModelOutput(embeds, last, pooled, tuple(hs[i] for i in range(L + 1)) if hs is not None else None)
+        return out if return_dict is None or return_dict else out.to_tuple()
+
+    def encode_image(self, pixel_values: torch.Tensor) -> torch.Tensor:
+        """``open_clip``'s name for the projected image embedding (what the reference's evaluation scripts call)."""
+        return self.forward(pixel_values).image_embeds
+
+    # ------------------------------------------------------------------ checkpoints (transformers directory layout)
+    def save_pretrained(self, save_directory: str, **unused):
+        save_checkpoint(self, save_directory, dict(architectures=["CLIPVisionModelWithProjection"], model_type="clip_vision_model"))
+
+    @classmethod
+    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, revision=None, **unused):
+        from ._ckpt import TRANSFORMERS_STEMS, load_weights
+        d, cfg = read_checkpoint_config(cls, path, subfolder)
+        model = cls(init_seed=None, **cfg)
+        model.load_state_dict(load_weights(d, variant, TRANSFORMERS_STEMS))
+        return model

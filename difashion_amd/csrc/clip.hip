@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/difashion_hip.h"
+#include "clip_kernels.h"
 #include "dfh_common.h"
 
 namespace {
@@ -38,12 +39,12 @@ __global__ __launch_bounds__(256) void clip_embed_kernel(const int64_t* __restri
 }
 
 // ------------------------------------------------------------------ LayerNorm over the last dim, fp32 in / out, one wave per row
-// (two-pass mean / biased variance like torch.nn.functional.layer_norm)
+// (two-pass mean / biased variance like torch.nn.functional.layer_norm); input rows ldx floats apart, output rows dense
 __global__ __launch_bounds__(256) void clip_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                                                             const float* __restrict__ b, float* __restrict__ y, int M, int D, float eps) {
+                                                             const float* __restrict__ b, float* __restrict__ y, int M, int D, float eps, long ldx) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= M) return;
-  const float4* r = (const float4*)(x + (long)row * D);
+  const float4* r = (const float4*)(x + (long)row * ldx);
   float s = 0.f;
   for (int c = lane; c < D / 4; c += 64) { const float4 v = r[c]; s += (v.x + v.y) + (v.z + v.w); }
   const float mean = wave_sum(s) / (float)D;
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(256) void clip_layernorm_kernel(const float* __rest
 // banks, and the transposing store of a float4 along k writes consecutive rows of one k.  The next k-tile's global loads are issued
 // before the current tile's MFMAs (register prefetch).
 constexpr int CBM = 64, CBN = 64, CBK = 32, CLD = 80;
-enum { CLIP_ACT_NONE = 0, CLIP_ACT_QUICK_GELU = 1, CLIP_ACT_GELU = 2 };
+using dfh::CLIP_ACT_NONE; using dfh::CLIP_ACT_QUICK_GELU; using dfh::CLIP_ACT_GELU;
 
 DFH_DEVICE float clip_act(float v, int act) {
   if (act == CLIP_ACT_QUICK_GELU) return v / (1.0f + expf(-1.702f * v));           // x * sigmoid(1.702 x)
@@ -288,13 +289,29 @@ static size_t clip_ws_floats(const dfh_clip* c, int batch, int T) {
 }
 size_t dfh_clip_workspace_bytes(const dfh_clip* c, int batch, int seq_len) { return clip_ws_floats(c, batch, seq_len) * sizeof(float) + 256; }
 
-static int clip_linear(const float* A, int lda, const float* W, int K, const float* bias, const float* resid, int ld_res, float* out,
-                       int ld_out, int M, int N, int act, hipStream_t s) {
-  dfh::ProfScope ps(dfh::PC_OTHER, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N), s);
+}  // extern "C"
+
+// the two launchers the vision tower (clip_vision.hip) shares with this file: clip_kernels.h
+namespace dfh {
+int clip_linear(const float* A, int lda, const float* W, int K, const float* bias, const float* resid, int ld_res, float* out,
+                int ld_out, int M, int N, int act, int prof_class, hipStream_t s) {
+  ProfScope ps(prof_class, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N), s);
   const dim3 grid((N + CBN - 1) / CBN, (M + CBM - 1) / CBM);
   hipLaunchKernelGGL(clip_gemm_f32_kernel, grid, dim3(256), 0, s, A, lda, W, K, bias, resid, ld_res, out, ld_out, M, N, K, act);
-  return dfh::check_launch("clip_gemm_f32_kernel");
+  return check_launch("clip_gemm_f32_kernel");
 }
+int clip_layernorm(const float* x, long ldx, const float* g, const float* b, float* y, int M, int D, float eps, hipStream_t s) {
+  hipLaunchKernelGGL(clip_layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, s, x, g, b, y, M, D, eps, ldx);
+  return check_launch("clip_layernorm_kernel");
+}
+}  // namespace dfh
+
+static int clip_linear(const float* A, int lda, const float* W, int K, const float* bias, const float* resid, int ld_res, float* out,
+                       int ld_out, int M, int N, int act, hipStream_t s) {
+  return dfh::clip_linear(A, lda, W, K, bias, resid, ld_res, out, ld_out, M, N, act, dfh::PC_OTHER, s);
+}
+
+extern "C" {
 
 int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, const int64_t* input_ids, float* last_hidden_state,
                     float* pooler_output, int eos_token_id, float* hidden_states, void* workspace, size_t workspace_bytes, int batch,
@@ -318,7 +335,6 @@ int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, c
   float* hid = att + (size_t)M * D;
   const float* const* P = master_params;
   const float eps = c->cfg.layer_norm_eps, scale = 1.0f / sqrtf((float)d);
-  const dim3 ln_grid((M + 3) / 4);
   hipLaunchKernelGGL(clip_embed_kernel, dim3(M), dim3(256), 0, s, input_ids, P[c->tok], P[c->pos], x, T, D, c->cfg.vocab_size);
   if (int rc = dfh::check_launch("clip_embed_kernel")) return rc;
   const size_t hs_bytes = (size_t)M * D * sizeof(float);
@@ -328,16 +344,14 @@ int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, c
   }
   for (size_t l = 0; l < c->layers.size(); ++l) {
     const ClipLayer& L = c->layers[l];
-    hipLaunchKernelGGL(clip_layernorm_kernel, ln_grid, dim3(256), 0, s, x, P[L.ln1w], P[L.ln1b], ln, M, D, eps);
-    if (int rc = dfh::check_launch("clip_layernorm_kernel")) return rc;
+    if (int rc = dfh::clip_layernorm(x, D, P[L.ln1w], P[L.ln1b], ln, M, D, eps, s)) return rc;
     if (int rc = clip_linear(ln, D, P[L.qw], D, P[L.qb], nullptr, 0, qkv, 3 * D, M, D, CLIP_ACT_NONE, s)) return rc;
     if (int rc = clip_linear(ln, D, P[L.kw], D, P[L.kb], nullptr, 0, qkv + D, 3 * D, M, D, CLIP_ACT_NONE, s)) return rc;
     if (int rc = clip_linear(ln, D, P[L.vw], D, P[L.vb], nullptr, 0, qkv + 2 * D, 3 * D, M, D, CLIP_ACT_NONE, s)) return rc;
     hipLaunchKernelGGL(clip_attention_kernel, dim3(H, batch), dim3(256), lds, s, qkv, att, T, D, d, scale);
     if (int rc = dfh::check_launch("clip_attention_kernel")) return rc;
     if (int rc = clip_linear(att, D, P[L.ow], D, P[L.ob], x, D, x, D, M, D, CLIP_ACT_NONE, s)) return rc;       // x += out_proj(attention)
-    hipLaunchKernelGGL(clip_layernorm_kernel, ln_grid, dim3(256), 0, s, x, P[L.ln2w], P[L.ln2b], ln, M, D, eps);
-    if (int rc = dfh::check_launch("clip_layernorm_kernel")) return rc;
+    if (int rc = dfh::clip_layernorm(x, D, P[L.ln2w], P[L.ln2b], ln, M, D, eps, s)) return rc;
     if (int rc = clip_linear(ln, D, P[L.f1w], D, P[L.f1b], nullptr, 0, hid, I, M, I, c->cfg.hidden_act, s)) return rc;
     if (int rc = clip_linear(hid, I, P[L.f2w], I, P[L.f2b], x, D, x, D, M, D, CLIP_ACT_NONE, s)) return rc;      // x += fc2(act(fc1(.)))
     if (hidden_states && hipMemcpyAsync(hidden_states + (l + 1) * (size_t)M * D, x, hs_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
@@ -345,8 +359,7 @@ int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, c
       return -2;
     }
   }
-  hipLaunchKernelGGL(clip_layernorm_kernel, ln_grid, dim3(256), 0, s, x, P[c->fw], P[c->fb], last_hidden_state, M, D, eps);
-  if (int rc = dfh::check_launch("clip_layernorm_kernel")) return rc;
+  if (int rc = dfh::clip_layernorm(x, D, P[c->fw], P[c->fb], last_hidden_state, M, D, eps, s)) return rc;
   if (pooler_output) {
     hipLaunchKernelGGL(clip_pool_kernel, dim3(batch), dim3(256), 0, s, input_ids, last_hidden_state, pooler_output, T, D, eos_token_id);
     if (int rc = dfh::check_launch("clip_pool_kernel")) return rc;

@@ -259,6 +259,51 @@ int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, c
                     float* pooler_output, int eos_token_id, float* hidden_states, void* workspace, size_t workspace_bytes, int batch,
                     int seq_len, void* stream);
 
+/* ------------------------------------------------------------------ CLIP image encoder: vision tower + projection
+ * Replaces (arithmetic) the OpenCLIP ViT-H/14 ``encode_image`` that the reference's Evaluation/ scripts call on every generated and
+ * ground-truth image (Evaluation/extract_hist_embs.py:83-100, Evaluation/eval_utils.py:91-135, :503-535), under the architecture and
+ * key names of transformers' CLIPVisionModelWithProjection ("vision_model.*", "visual_projection.weight"; "pre_layrnorm" is the
+ * library's own spelling).  fp32 end to end in both storage builds (csrc/clip_vision.hip): patch embedding as im2col + GEMM, the
+ * linears and LayerNorms of the text tower, and a bidirectional attention kernel that streams K / V through LDS in key tiles
+ * (online softmax), so the sequence length is not bounded by LDS.  Master parameters are read in place: no arenas, no pack step.
+ * Image resize / normalisation and the metrics computed from the embeddings stay outside the library. */
+typedef struct dfh_clipv_config {
+  int hidden_size;                 /* 1024 (ViT-L/14) / 1280 (ViT-H/14) */
+  int intermediate_size;           /* 4096 / 5120 */
+  int num_hidden_layers;           /* 24 / 32 */
+  int num_attention_heads;         /* 16: head dim 64 / 80; any multiple of 4 up to 128 */
+  int image_size;                  /* 224 */
+  int patch_size;                  /* 14: tokens = 1 + (image_size / patch_size)^2 = 257 */
+  int num_channels;                /* 3 */
+  int projection_dim;              /* 768 / 1024 */
+  int hidden_act;                  /* 1 quick_gelu (OpenAI ViT-L/14) / 2 gelu, erf form (OpenCLIP ViT-H/14) */
+  float layer_norm_eps;            /* 1e-5 */
+} dfh_clipv_config;
+typedef struct dfh_clipv dfh_clipv;
+int dfh_clipv_create(const dfh_clipv_config* cfg, dfh_clipv** out);   /* host-only work */
+void dfh_clipv_destroy(dfh_clipv* c);
+int dfh_clipv_num_params(const dfh_clipv* c);
+const char* dfh_clipv_param_name(const dfh_clipv* c, int i);
+int dfh_clipv_param_ndim(const dfh_clipv* c, int i);
+int dfh_clipv_param_dim(const dfh_clipv* c, int i, int d);
+size_t dfh_clipv_workspace_bytes(const dfh_clipv* c, int batch);
+/* outputs = vision_model(pixel_values), T = 1 + (image_size / patch_size)^2:
+ *   master_params     : HOST array of `count` device pointers to the fp32 parameters, table order, each 16-byte aligned
+ *   pixel_values      : [batch][num_channels][image_size][image_size] fp32 (already resized and normalised)
+ *   last_hidden_state : [batch][T][hidden_size] fp32, the output of the last block (NOT normalised, as in transformers)
+ *   pooler_output     : NULL, or [batch][hidden_size] = post_layernorm(last_hidden_state[:, 0])
+ *   image_embeds      : NULL, or [batch][projection_dim] = visual_projection(pooler_output)
+ *   hidden_states     : NULL, or a HOST array of num_hidden_layers + 1 device pointers, each NULL or [batch][T][hidden_size] fp32:
+ *                       entry 0 receives the pre_layrnorm output, entry l the output of block l (output_hidden_states=True)
+ *   workspace         : >= dfh_clipv_workspace_bytes(batch), 256-byte aligned */
+int dfh_clipv_encode(dfh_clipv* c, const float* const* master_params, int count, const float* pixel_values, int batch,
+                     float* last_hidden_state, float* pooler_output, float* image_embeds, float* const* hidden_states,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* The attention kernel of the vision tower on its own (tests, microbenchmarks): O = softmax(Q K^T * scale) V per (batch, head), no
+ * mask.  qkv [batch * T][3 * heads * head_dim] fp32 (q | k | v, heads contiguous inside each), out [batch * T][heads * head_dim];
+ * head_dim a multiple of 4 up to 128, any T >= 1. */
+int dfh_clipv_attention(const float* qkv, float* out, int batch, int T, int heads, int head_dim, float scale, void* stream);
+
 /* ------------------------------------------------------------------ op-level entry points (tests, profiling)
  * ResnetBlock2D conv3x3 / Downsample2D / Upsample2D / 1x1 conv / Linear, as one implicit GEMM:
  *   out[M][N] = act( conv3x3(x) (+ a0 . W[:, k0:] + a1 . W[:, k1:]) + bias + rowvec[b] ) + resid */
