@@ -1,5 +1,5 @@
-"""What the native-backed model wrappers (unet.py, vae.py, clip.py; the checkpoint part also mutual.py) share: the Python
-counterpart of csrc/walk_common.h.
+"""What the native-backed model wrappers (unet.py, vae.py, clip.py, clip_vision.py; the checkpoint part also mutual.py) share: the
+Python counterpart of csrc/walk_common.h, and of csrc/clip_tower.h for the two CLIP towers (``ClipTower``, ``TupleOutput``).
 
 ``NativeModule`` drives one family of C entry points (``dfh_<family>_create / _destroy / _num_params / _param_name / _param_ndim /
 _param_dim``): handle lifecycle, the parameter tree built from the C table, the table-ordered parameter list, the pack signature and
@@ -180,3 +180,70 @@ class NativeModule(nn.Module):
         if self.dtype != torch.float32:
             raise _lib.DfhError(self._fp32_rule)
         return dev
+
+
+class TupleOutput:
+    """transformers-style output object: attributes, and the tuple protocol over those of ``_fields`` that are not None."""
+    _fields = ()
+
+    def to_tuple(self):
+        return tuple(v for v in (getattr(self, f) for f in self._fields) if v is not None)
+
+    def __getitem__(self, i):
+        return self.to_tuple()[i]
+
+    def __iter__(self):
+        return iter(self.to_tuple())
+
+    def __len__(self):
+        return len(self.to_tuple())
+
+
+class ClipTower(NativeModule):
+    """What CLIPTextModel and CLIPVisionModelWithProjection share: fp32 masters read in place (no arenas, no pack step), one workspace
+    block, the transformers checkpoint directory.  A subclass supplies ``family``, ``architecture``, ``model_type``, ``_c_config()``."""
+    weights_name = "model.safetensors"
+    _fp32_rule = "parameters must stay fp32 (the kernels read them in place)"
+    _ACT = {"quick_gelu": 1, "gelu": 2}
+    architecture = model_type = ""
+    _ws = None
+
+    def _init_tower(self, init_seed: Optional[int], init_std: float, act_hint: str, **config):
+        """``config`` in the key order of ``config.json``; ``act_hint``: which activations this tower's checkpoints use."""
+        if config["hidden_act"] not in self._ACT:
+            raise ValueError(f"hidden_act {config['hidden_act']!r}: {act_hint}")
+        self.config = FrozenDict(**config)
+        table = self.param_table()
+        self._names = [n for n, _ in table]             # no bind / pack step that would fill them later: the masters are read in place
+        # "norm", not "layer_norm": transformers spells the vision tower's first LayerNorm pre_layrnorm
+        self._build_parameters(table, lambda name: "norm" in name.split(".")[-2], init_seed, init_std, unseeded_zeros=True)
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """Drops the ``position_ids`` buffer that checkpoints written by older transformers releases carry."""
+        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.endswith("position_ids")}, strict=strict, **kw)
+
+    def _prepare(self, dev: torch.device, *batch_args):
+        """Context, a workspace of ``dfh_<family>_workspace_bytes(ctx, *batch_args)`` on ``dev`` and the checked parameters:
+        (pointer array, count) for the encode call."""
+        if self._ctx is None:
+            self._ctx = self._make_ctx()
+        need = self._entry("workspace_bytes")(self._ctx, *batch_args)
+        if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
+            self._ws = None                              # release the old block before asking for the larger one
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        plist = self._plist()
+        if any(p.device != dev or not p.is_contiguous() for p in plist):
+            raise _lib.DfhError("all parameters must be contiguous and on one device")
+        return self._pointers(plist), len(plist)
+
+    # ------------------------------------------------------------------ checkpoints (transformers directory layout)
+    def save_pretrained(self, save_directory: str, **unused):
+        save_checkpoint(self, save_directory, dict(architectures=[self.architecture], model_type=self.model_type))
+
+    @classmethod
+    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, revision=None, **unused):
+        from ._ckpt import TRANSFORMERS_STEMS, load_weights
+        d, cfg = read_checkpoint_config(cls, path, subfolder)
+        model = cls(init_seed=None, **cfg)
+        model.load_state_dict(load_weights(d, variant, TRANSFORMERS_STEMS))
+        return model

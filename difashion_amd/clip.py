@@ -18,67 +18,43 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._native import FrozenDict, NativeModule, read_checkpoint_config, save_checkpoint
-
-_ACT = {"quick_gelu": 1, "gelu": 2}
+from ._native import ClipTower, TupleOutput
 
 
-class BaseModelOutputWithPooling:
+class BaseModelOutputWithPooling(TupleOutput):
     """transformers' output object as far as the reference (and ``output_hidden_states=True`` debugging) uses it: ``[0]`` /
     ``.last_hidden_state``, ``[1]`` / ``.pooler_output``, ``.hidden_states``."""
+    _fields = ("last_hidden_state", "pooler_output", "hidden_states")
 
     def __init__(self, last_hidden_state, pooler_output, hidden_states=None):
         self.last_hidden_state, self.pooler_output, self.hidden_states = last_hidden_state, pooler_output, hidden_states
 
-    def to_tuple(self):
-        return tuple(v for v in (self.last_hidden_state, self.pooler_output, self.hidden_states) if v is not None)
 
-    def __getitem__(self, i):
-        return self.to_tuple()[i]
-
-    def __iter__(self):
-        return iter(self.to_tuple())
-
-    def __len__(self):
-        return len(self.to_tuple())
-
-
-class CLIPTextModel(NativeModule):
+class CLIPTextModel(ClipTower):
     family = "clip"
-    weights_name = "model.safetensors"
-    _fp32_rule = "parameters must stay fp32 (the kernels read them in place)"
+    architecture, model_type = "CLIPTextModel", "clip_text_model"
 
     def __init__(self, vocab_size: int = 49408, hidden_size: int = 768, intermediate_size: int = 3072, num_hidden_layers: int = 12,
                  num_attention_heads: int = 12, max_position_embeddings: int = 77, hidden_act: str = "quick_gelu",
                  layer_norm_eps: float = 1e-5, eos_token_id: int = 2, bos_token_id: int = 49406, pad_token_id: int = 1,
                  init_seed: Optional[int] = 0, init_std: float = 0.02, **unused):
         super().__init__()
-        if hidden_act not in _ACT:
-            raise ValueError(f"hidden_act {hidden_act!r}: the CLIP text towers of SD-1.5 / SD-2 use 'quick_gelu' / 'gelu'")
-        self.config = FrozenDict(vocab_size=vocab_size, hidden_size=hidden_size, intermediate_size=intermediate_size,
-                                 num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads,
-                                 max_position_embeddings=max_position_embeddings, hidden_act=hidden_act, layer_norm_eps=layer_norm_eps,
-                                 eos_token_id=eos_token_id, bos_token_id=bos_token_id, pad_token_id=pad_token_id)
-        self._ctx = None
-        self._ws = None
-        table = self.param_table()
-        self._names = [n for n, _ in table]             # no bind / pack step that would fill them later: the masters are read in place
-        self._build_parameters(table, lambda name: "layer_norm" in name.split(".")[-2], init_seed, init_std, unseeded_zeros=True)
+        self._init_tower(init_seed, init_std, "the CLIP text towers of SD-1.5 / SD-2 use 'quick_gelu' / 'gelu'",
+                         vocab_size=vocab_size, hidden_size=hidden_size, intermediate_size=intermediate_size,
+                         num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads,
+                         max_position_embeddings=max_position_embeddings, hidden_act=hidden_act, layer_norm_eps=layer_norm_eps,
+                         eos_token_id=eos_token_id, bos_token_id=bos_token_id, pad_token_id=pad_token_id)
 
     # ------------------------------------------------------------------ plumbing
     def _c_config(self) -> _lib.CLIPConfigC:
         cfg = self.config
         return _lib.CLIPConfigC(cfg["vocab_size"], cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"],
-                                cfg["num_attention_heads"], cfg["max_position_embeddings"], _ACT[cfg["hidden_act"]], cfg["layer_norm_eps"])
+                                cfg["num_attention_heads"], cfg["max_position_embeddings"], self._ACT[cfg["hidden_act"]], cfg["layer_norm_eps"])
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         """Accepts the 4.32.1 layout (``text_model.*``, what published checkpoints hold), the flattened layout of newer transformers
         releases, and drops the ``position_ids`` buffer old checkpoints carry."""
-        sd = {}
-        for k, v in state_dict.items():
-            if k.endswith("position_ids"):
-                continue
-            sd[k if k.startswith("text_model.") else "text_model." + k] = v
+        sd = {k if k.startswith("text_model.") else "text_model." + k: v for k, v in state_dict.items()}
         return super().load_state_dict(sd, strict=strict, **kw)
 
     # ------------------------------------------------------------------ text_encoder(input_ids)
@@ -104,33 +80,12 @@ class CLIPTextModel(NativeModule):
         B = ids.shape[0]
         if lo < 0 or hi >= cfg["vocab_size"]:
             raise IndexError(f"input_ids out of range [0, {cfg['vocab_size']}): min {lo}, max {hi}")
-        lib = _lib.raw()
-        if self._ctx is None:
-            self._ctx = self._make_ctx()
-        need = lib.dfh_clip_workspace_bytes(self._ctx, B, T)
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        plist = self._plist()
-        if any(p.device != dev or not p.is_contiguous() for p in plist):
-            raise _lib.DfhError("all parameters must be contiguous and on one device")
-        arr = self._pointers(plist)
+        arr, count = self._prepare(dev, B, T)
         D, L = cfg["hidden_size"], cfg["num_hidden_layers"]
         last = torch.empty((B, T, D), dtype=torch.float32, device=dev)
         pooled = torch.empty((B, D), dtype=torch.float32, device=dev)
         hs = torch.empty((L + 1, B, T, D), dtype=torch.float32, device=dev) if output_hidden_states else None
-        _lib.call("dfh_clip_encode", self._ctx, arr, len(plist), _lib.ptr(ids), _lib.ptr(last), _lib.ptr(pooled), int(cfg["eos_token_id"]),
+        _lib.call("dfh_clip_encode", self._ctx, arr, count, _lib.ptr(ids), _lib.ptr(last), _lib.ptr(pooled), int(cfg["eos_token_id"]),
                   _lib.ptr(hs), _lib.ptr(self._ws), self._ws.numel(), B, T, _lib.stream_ptr())
         out = BaseModelOutputWithPooling(last, pooled, tuple(hs[i] for i in range(L + 1)) if hs is not None else None)
         return out if return_dict is None or return_dict else out.to_tuple()
-
-    # ------------------------------------------------------------------ checkpoints (transformers directory layout)
-    def save_pretrained(self, save_directory: str, **unused):
-        save_checkpoint(self, save_directory, dict(architectures=["CLIPTextModel"], model_type="clip_text_model"))
-
-    @classmethod
-    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, revision=None, **unused):
-        from ._ckpt import TRANSFORMERS_STEMS, load_weights
-        d, cfg = read_checkpoint_config(cls, path, subfolder)
-        model = cls(init_seed=None, **cfg)
-        model.load_state_dict(load_weights(d, variant, TRANSFORMERS_STEMS))
-        return model

@@ -19,66 +19,42 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._native import FrozenDict, NativeModule, read_checkpoint_config, save_checkpoint
-
-_ACT = {"quick_gelu": 1, "gelu": 2}
+from ._native import ClipTower, TupleOutput
 
 
-class CLIPVisionModelOutput:
+class CLIPVisionModelOutput(TupleOutput):
     """transformers' output object: ``.image_embeds`` / ``[0]``, ``.last_hidden_state`` / ``[1]``, ``.hidden_states``; plus
     ``.pooler_output`` (the post-LayerNorm class token that ``visual_projection`` reads), which the evaluation tests compare too."""
+    _fields = ("image_embeds", "last_hidden_state", "hidden_states")
 
     def __init__(self, image_embeds, last_hidden_state, pooler_output, hidden_states=None):
         self.image_embeds, self.last_hidden_state, self.pooler_output = image_embeds, last_hidden_state, pooler_output
         self.hidden_states = hidden_states
 
-    def to_tuple(self):
-        return tuple(v for v in (self.image_embeds, self.last_hidden_state, self.hidden_states) if v is not None)
 
-    def __getitem__(self, i):
-        return self.to_tuple()[i]
-
-    def __iter__(self):
-        return iter(self.to_tuple())
-
-    def __len__(self):
-        return len(self.to_tuple())
-
-
-class CLIPVisionModelWithProjection(NativeModule):
+class CLIPVisionModelWithProjection(ClipTower):
     family = "clipv"
-    weights_name = "model.safetensors"
-    _fp32_rule = "parameters must stay fp32 (the kernels read them in place)"
+    architecture, model_type = "CLIPVisionModelWithProjection", "clip_vision_model"
 
     def __init__(self, hidden_size: int = 1280, intermediate_size: int = 5120, projection_dim: int = 1024, num_hidden_layers: int = 32,
                  num_attention_heads: int = 16, num_channels: int = 3, image_size: int = 224, patch_size: int = 14,
                  hidden_act: str = "gelu", layer_norm_eps: float = 1e-5, init_seed: Optional[int] = 0, init_std: float = 0.02, **unused):
         super().__init__()
-        if hidden_act not in _ACT:
-            raise ValueError(f"hidden_act {hidden_act!r}: the CLIP vision towers use 'quick_gelu' (OpenAI ViT-L/14) / 'gelu' (OpenCLIP ViT-H/14)")
-        self.config = FrozenDict(hidden_size=hidden_size, intermediate_size=intermediate_size, projection_dim=projection_dim,
-                                 num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads, num_channels=num_channels,
-                                 image_size=image_size, patch_size=patch_size, hidden_act=hidden_act, layer_norm_eps=layer_norm_eps)
-        self._ctx = None
-        self._ws = None
-        table = self.param_table()
-        self._names = [n for n, _ in table]             # the masters are read in place: no bind / pack step
-        self._build_parameters(table, lambda name: "norm" in name.split(".")[-2], init_seed, init_std, unseeded_zeros=True)
+        self._init_tower(init_seed, init_std, "the CLIP vision towers use 'quick_gelu' (OpenAI ViT-L/14) / 'gelu' (OpenCLIP ViT-H/14)",
+                         hidden_size=hidden_size, intermediate_size=intermediate_size, projection_dim=projection_dim,
+                         num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads, num_channels=num_channels,
+                         image_size=image_size, patch_size=patch_size, hidden_act=hidden_act, layer_norm_eps=layer_norm_eps)
 
     # ------------------------------------------------------------------ plumbing
     def _c_config(self) -> _lib.CLIPVisionConfigC:
         cfg = self.config
         return _lib.CLIPVisionConfigC(cfg["hidden_size"], cfg["intermediate_size"], cfg["num_hidden_layers"], cfg["num_attention_heads"],
                                       cfg["image_size"], cfg["patch_size"], cfg["num_channels"], cfg["projection_dim"],
-                                      _ACT[cfg["hidden_act"]], cfg["layer_norm_eps"])
+                                      self._ACT[cfg["hidden_act"]], cfg["layer_norm_eps"])
 
     @property
     def num_tokens(self) -> int:
         return 1 + (self.config["image_size"] // self.config["patch_size"]) ** 2
-
-    def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        """Drops the ``position_ids`` buffer that checkpoints written by older transformers releases carry."""
-        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.endswith("position_ids")}, strict=strict, **kw)
 
     # ------------------------------------------------------------------ model(pixel_values)
     @torch.no_grad()
@@ -107,17 +83,7 @@ class CLIPVisionModelWithProjection(NativeModule):
         if B < 1:
             raise ValueError("pixel_values holds no image")
         px = pixel_values.contiguous()
-        lib = _lib.raw()
-        if self._ctx is None:
-            self._ctx = self._make_ctx()
-        need = lib.dfh_clipv_workspace_bytes(self._ctx, B)
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
-            self._ws = None                              # release the old block before asking for the larger one
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        plist = self._plist()
-        if any(p.device != dev or not p.is_contiguous() for p in plist):
-            raise _lib.DfhError("all parameters must be contiguous and on one device")
-        arr = self._pointers(plist)
+        arr, count = self._prepare(dev, B)
         D, L, T = cfg["hidden_size"], cfg["num_hidden_layers"], self.num_tokens
         last = torch.empty((B, T, D), dtype=torch.float32, device=dev)
         pooled = torch.empty((B, D), dtype=torch.float32, device=dev)
@@ -126,7 +92,7 @@ class CLIPVisionModelWithProjection(NativeModule):
         if output_hidden_states:
             hs = torch.empty((L + 1, B, T, D), dtype=torch.float32, device=dev)
             taps = (C.c_void_p * (L + 1))(*[hs[i].data_ptr() for i in range(L + 1)])
-        _lib.call("dfh_clipv_encode", self._ctx, arr, len(plist), _lib.ptr(px), B, _lib.ptr(last), _lib.ptr(pooled), _lib.ptr(embeds),
+        _lib.call("dfh_clipv_encode", self._ctx, arr, count, _lib.ptr(px), B, _lib.ptr(last), _lib.ptr(pooled), _lib.ptr(embeds),
                   taps, _lib.ptr(self._ws), self._ws.numel(), _lib.stream_ptr())
         out = CLIPVisionModelOutput(embeds, last, pooled, tuple(hs[i] for i in range(L + 1)) if hs is not None else None)
         return out if return_dict is None or return_dict else out.to_tuple()
@@ -134,15 +100,3 @@ class CLIPVisionModelWithProjection(NativeModule):
     def encode_image(self, pixel_values: torch.Tensor) -> torch.Tensor:
         """``open_clip``'s name for the projected image embedding (what the reference's evaluation scripts call)."""
         return self.forward(pixel_values).image_embeds
-
-    # ------------------------------------------------------------------ checkpoints (transformers directory layout)
-    def save_pretrained(self, save_directory: str, **unused):
-        save_checkpoint(self, save_directory, dict(architectures=["CLIPVisionModelWithProjection"], model_type="clip_vision_model"))
-
-    @classmethod
-    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, revision=None, **unused):
-        from ._ckpt import TRANSFORMERS_STEMS, load_weights
-        d, cfg = read_checkpoint_config(cls, path, subfolder)
-        model = cls(init_seed=None, **cfg)
-        model.load_state_dict(load_weights(d, variant, TRANSFORMERS_STEMS))
-        return model

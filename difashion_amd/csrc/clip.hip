@@ -12,13 +12,8 @@
 // (v_mfma_f32_16x16x4_f32, 256 FLOP / clk / CU), weights are read in place from the fp32 master parameters (nn.Linear layout [N][K],
 // K contiguous: no packed copy, no arena), and the result agrees with the fp32 reference class to summation-order noise (1e-6),
 // not to bf16 noise.  No atomics: reruns are bit-identical.
-#include <cstring>
-#include <string>
-#include <vector>
-
 #include "../../include/difashion_hip.h"
-#include "clip_kernels.h"
-#include "dfh_common.h"
+#include "clip_tower.h"
 
 namespace {
 
@@ -230,17 +225,15 @@ __global__ __launch_bounds__(256) void clip_pool_kernel(const int64_t* __restric
   for (int c = threadIdx.x; c < D; c += 256) pooled[(long)b * D + c] = y[((long)b * T + pos) * D + c];
 }
 
-struct ClipLayer { int kw, kb, vw, vb, qw, qb, ow, ob, ln1w, ln1b, f1w, f1b, f2w, f2b, ln2w, ln2b; };
-
 }  // namespace
 
-struct dfh_clip {
+struct dfh_clip : dfh::ParamList {
   dfh_clip_config cfg{};
-  struct P { std::string name; std::vector<int> shape; };
-  std::vector<P> params;
   int tok = 0, pos = 0, fw = 0, fb = 0;
-  std::vector<ClipLayer> layers;
-  int add(const std::string& n, std::vector<int> s) { params.push_back({n, std::move(s)}); return (int)params.size() - 1; }
+  std::vector<dfh::ClipLayer> layers;
+  dfh::ClipWorkspace workspace(void* base, int batch, int T) const {
+    return dfh::ClipWorkspace(base, (size_t)batch * T, cfg.hidden_size, cfg.intermediate_size, 3 * (size_t)cfg.hidden_size, 0);
+  }
 };
 
 extern "C" {
@@ -257,37 +250,20 @@ int dfh_clip_create(const dfh_clip_config* cfg, dfh_clip** out) {
   const int D = cfg->hidden_size, I = cfg->intermediate_size;
   // transformers 4.32.1 state-dict names and order (CLIPTextModel -> text_model.*)
   const std::string tm = "text_model.";
-  c->tok = c->add(tm + "embeddings.token_embedding.weight", {cfg->vocab_size, D});
-  c->pos = c->add(tm + "embeddings.position_embedding.weight", {cfg->max_position_embeddings, D});
-  for (int l = 0; l < cfg->num_hidden_layers; ++l) {
-    const std::string p = tm + "encoder.layers." + std::to_string(l) + ".";
-    ClipLayer L;
-    L.kw = c->add(p + "self_attn.k_proj.weight", {D, D}); L.kb = c->add(p + "self_attn.k_proj.bias", {D});
-    L.vw = c->add(p + "self_attn.v_proj.weight", {D, D}); L.vb = c->add(p + "self_attn.v_proj.bias", {D});
-    L.qw = c->add(p + "self_attn.q_proj.weight", {D, D}); L.qb = c->add(p + "self_attn.q_proj.bias", {D});
-    L.ow = c->add(p + "self_attn.out_proj.weight", {D, D}); L.ob = c->add(p + "self_attn.out_proj.bias", {D});
-    L.ln1w = c->add(p + "layer_norm1.weight", {D}); L.ln1b = c->add(p + "layer_norm1.bias", {D});
-    L.f1w = c->add(p + "mlp.fc1.weight", {I, D}); L.f1b = c->add(p + "mlp.fc1.bias", {I});
-    L.f2w = c->add(p + "mlp.fc2.weight", {D, I}); L.f2b = c->add(p + "mlp.fc2.bias", {D});
-    L.ln2w = c->add(p + "layer_norm2.weight", {D}); L.ln2b = c->add(p + "layer_norm2.bias", {D});
-    c->layers.push_back(L);
-  }
-  c->fw = c->add(tm + "final_layer_norm.weight", {D});
-  c->fb = c->add(tm + "final_layer_norm.bias", {D});
+  c->tok = c->add_param(tm + "embeddings.token_embedding.weight", {cfg->vocab_size, D});
+  c->pos = c->add_param(tm + "embeddings.position_embedding.weight", {cfg->max_position_embeddings, D});
+  c->layers = dfh::add_encoder_layers(*c, tm, cfg->num_hidden_layers, D, I);
+  c->fw = c->add_param(tm + "final_layer_norm.weight", {D});
+  c->fb = c->add_param(tm + "final_layer_norm.bias", {D});
   *out = c;
   return 0;
 }
 void dfh_clip_destroy(dfh_clip* c) { delete c; }
-int dfh_clip_num_params(const dfh_clip* c) { return (int)c->params.size(); }
-const char* dfh_clip_param_name(const dfh_clip* c, int i) { return c->params[i].name.c_str(); }
-int dfh_clip_param_ndim(const dfh_clip* c, int i) { return (int)c->params[i].shape.size(); }
-int dfh_clip_param_dim(const dfh_clip* c, int i, int d) { return c->params[i].shape[d]; }
-
-static size_t clip_ws_floats(const dfh_clip* c, int batch, int T) {
-  const size_t M = (size_t)batch * T, D = c->cfg.hidden_size, I = c->cfg.intermediate_size;
-  return M * (D /* x */ + D /* ln */ + 3 * D /* qkv */ + D /* attention */ + I /* hidden */) + 64;
-}
-size_t dfh_clip_workspace_bytes(const dfh_clip* c, int batch, int seq_len) { return clip_ws_floats(c, batch, seq_len) * sizeof(float) + 256; }
+int dfh_clip_num_params(const dfh_clip* c) { return c->num_params(); }
+const char* dfh_clip_param_name(const dfh_clip* c, int i) { return c->param_name(i); }
+int dfh_clip_param_ndim(const dfh_clip* c, int i) { return c->param_ndim(i); }
+int dfh_clip_param_dim(const dfh_clip* c, int i, int d) { return c->param_dim(i, d); }
+size_t dfh_clip_workspace_bytes(const dfh_clip* c, int batch, int seq_len) { return c->workspace(nullptr, batch, seq_len).bytes(); }
 
 }  // extern "C"
 
@@ -306,19 +282,13 @@ int clip_layernorm(const float* x, long ldx, const float* g, const float* b, flo
 }
 }  // namespace dfh
 
-static int clip_linear(const float* A, int lda, const float* W, int K, const float* bias, const float* resid, int ld_res, float* out,
-                       int ld_out, int M, int N, int act, hipStream_t s) {
-  return dfh::clip_linear(A, lda, W, K, bias, resid, ld_res, out, ld_out, M, N, act, dfh::PC_OTHER, s);
-}
-
 extern "C" {
 
 int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, const int64_t* input_ids, float* last_hidden_state,
                     float* pooler_output, int eos_token_id, float* hidden_states, void* workspace, size_t workspace_bytes, int batch,
                     int seq_len, void* stream) {
   DFH_REQUIRE(c && master_params && input_ids && last_hidden_state && workspace, "null argument");
-  DFH_REQUIRE(count == (int)c->params.size(), "master_params count does not match dfh_clip_num_params");
-  for (int i = 0; i < count; ++i) DFH_REQUIRE(master_params[i] != nullptr, "null parameter pointer: " + c->params[i].name);
+  if (int rc = dfh::require_params(*c, master_params, count, "dfh_clip")) return rc;
   DFH_REQUIRE(batch > 0 && seq_len > 0 && seq_len <= c->cfg.max_position_embeddings,
               "sequence length must be in [1, max_position_embeddings] (CLIPTextEmbeddings raises too)");
   DFH_REQUIRE(workspace_bytes >= dfh_clip_workspace_bytes(c, batch, seq_len), "workspace smaller than dfh_clip_workspace_bytes");
@@ -328,38 +298,24 @@ int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, c
   const int M = batch * T;
   const size_t lds = ((size_t)T * (2 * d + 1) + 4 * d + 4 * 128) * sizeof(float);
   DFH_REQUIRE(lds <= 64 * 1024, "head_dim x sequence length does not fit the attention kernel's LDS tile");
-  float* x = (float*)workspace;
-  float* ln = x + (size_t)M * D;
-  float* qkv = ln + (size_t)M * D;
-  float* att = qkv + (size_t)M * 3 * D;
-  float* hid = att + (size_t)M * D;
+  const dfh::ClipWorkspace w = c->workspace(workspace, batch, T);
   const float* const* P = master_params;
   const float eps = c->cfg.layer_norm_eps, scale = 1.0f / sqrtf((float)d);
-  hipLaunchKernelGGL(clip_embed_kernel, dim3(M), dim3(256), 0, s, input_ids, P[c->tok], P[c->pos], x, T, D, c->cfg.vocab_size);
+  hipLaunchKernelGGL(clip_embed_kernel, dim3(M), dim3(256), 0, s, input_ids, P[c->tok], P[c->pos], w.x, T, D, c->cfg.vocab_size);
   if (int rc = dfh::check_launch("clip_embed_kernel")) return rc;
-  const size_t hs_bytes = (size_t)M * D * sizeof(float);
-  if (hidden_states && hipMemcpyAsync(hidden_states, x, hs_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-    dfh::set_error("dfh_clip_encode: hidden_states copy failed");
-    return -2;
-  }
-  for (size_t l = 0; l < c->layers.size(); ++l) {
-    const ClipLayer& L = c->layers[l];
-    if (int rc = dfh::clip_layernorm(x, D, P[L.ln1w], P[L.ln1b], ln, M, D, eps, s)) return rc;
-    if (int rc = clip_linear(ln, D, P[L.qw], D, P[L.qb], nullptr, 0, qkv, 3 * D, M, D, CLIP_ACT_NONE, s)) return rc;
-    if (int rc = clip_linear(ln, D, P[L.kw], D, P[L.kb], nullptr, 0, qkv + D, 3 * D, M, D, CLIP_ACT_NONE, s)) return rc;
-    if (int rc = clip_linear(ln, D, P[L.vw], D, P[L.vb], nullptr, 0, qkv + 2 * D, 3 * D, M, D, CLIP_ACT_NONE, s)) return rc;
+  // hidden_states[l]: slice l of one buffer
+  auto tap = [&](int l, const float* src) {
+    return dfh::tower_copy(hidden_states ? hidden_states + l * (size_t)M * D : nullptr, src, (size_t)M * D * sizeof(float), s,
+                           "dfh_clip_encode: hidden_states");
+  };
+  auto attention = [&](const float* qkv, float* att) {
     hipLaunchKernelGGL(clip_attention_kernel, dim3(H, batch), dim3(256), lds, s, qkv, att, T, D, d, scale);
-    if (int rc = dfh::check_launch("clip_attention_kernel")) return rc;
-    if (int rc = clip_linear(att, D, P[L.ow], D, P[L.ob], x, D, x, D, M, D, CLIP_ACT_NONE, s)) return rc;       // x += out_proj(attention)
-    if (int rc = dfh::clip_layernorm(x, D, P[L.ln2w], P[L.ln2b], ln, M, D, eps, s)) return rc;
-    if (int rc = clip_linear(ln, D, P[L.f1w], D, P[L.f1b], nullptr, 0, hid, I, M, I, c->cfg.hidden_act, s)) return rc;
-    if (int rc = clip_linear(hid, I, P[L.f2w], I, P[L.f2b], x, D, x, D, M, D, CLIP_ACT_NONE, s)) return rc;      // x += fc2(act(fc1(.)))
-    if (hidden_states && hipMemcpyAsync(hidden_states + (l + 1) * (size_t)M * D, x, hs_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-      dfh::set_error("dfh_clip_encode: hidden_states copy failed");
-      return -2;
-    }
-  }
-  if (int rc = dfh::clip_layernorm(x, D, P[c->fw], P[c->fb], last_hidden_state, M, D, eps, s)) return rc;
+    return dfh::check_launch("clip_attention_kernel");
+  };
+  if (int rc = tap(0, w.x)) return rc;
+  const dfh::ClipAccounting acct = {dfh::PC_OTHER, -1, -1, -1};
+  if (int rc = dfh::clip_blocks(P, c->layers, w, M, D, I, c->cfg.hidden_act, eps, acct, s, attention, tap)) return rc;
+  if (int rc = dfh::clip_layernorm(w.x, D, P[c->fw], P[c->fb], last_hidden_state, M, D, eps, s)) return rc;
   if (pooler_output) {
     hipLaunchKernelGGL(clip_pool_kernel, dim3(batch), dim3(256), 0, s, input_ids, last_hidden_state, pooler_output, T, D, eos_token_id);
     if (int rc = dfh::check_launch("clip_pool_kernel")) return rc;

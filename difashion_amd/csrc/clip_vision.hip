@@ -11,12 +11,9 @@
 //     K / V stream through LDS in key tiles under a running maximum / denominator, both products on v_mfma_f32_16x16x4_f32.
 // No atomics anywhere: reruns are bit-identical, and a row's result does not depend on the batch it rides in.
 #include <cmath>
-#include <string>
-#include <vector>
 
 #include "../../include/difashion_hip.h"
-#include "clip_kernels.h"
-#include "dfh_common.h"
+#include "clip_tower.h"
 
 namespace {
 
@@ -167,18 +164,18 @@ int clipv_attention(const float* qkv, float* out, int batch, int T, int H, int d
   return launch_attention<8, 32>(qkv, out, batch, T, H, d, scale, s);      // key tiles of 32: K + V tile of d = 128 stays at 34 KB
 }
 
-struct VisLayer { int kw, kb, vw, vb, qw, qb, ow, ob, ln1w, ln1b, f1w, f1b, f2w, f2b, ln2w, ln2b; };
-
 }  // namespace
 
-struct dfh_clipv {
+struct dfh_clipv : dfh::ParamList {
   dfh_clipv_config cfg{};
-  struct P { std::string name; std::vector<int> shape; };
-  std::vector<P> params;
   int cls = 0, patch = 0, pos = 0, prew = 0, preb = 0, postw = 0, postb = 0, proj = 0;
-  std::vector<VisLayer> layers;
+  std::vector<dfh::ClipLayer> layers;
   int grid = 0, T = 0, Kp = 0;     // patches per side, tokens, C * p * p
-  int add(const std::string& n, std::vector<int> s) { params.push_back({n, std::move(s)}); return (int)params.size() - 1; }
+  // the q k v region doubles as the im2col rows of the patch conv (the attention region as its output); tail: the pooled row of every image
+  dfh::ClipWorkspace workspace(void* base, int batch) const {
+    const size_t D = cfg.hidden_size;
+    return dfh::ClipWorkspace(base, (size_t)batch * T, D, cfg.intermediate_size, 3 * D > (size_t)Kp ? 3 * D : (size_t)Kp, (size_t)batch * D);
+  }
 };
 
 extern "C" {
@@ -206,47 +203,24 @@ int dfh_clipv_create(const dfh_clipv_config* cfg, dfh_clipv** out) {
   const int D = cfg->hidden_size, I = cfg->intermediate_size;
   // state-dict names and order of transformers' CLIPVisionModelWithProjection
   const std::string vm = "vision_model.";
-  c->cls = c->add(vm + "embeddings.class_embedding", {D});
-  c->patch = c->add(vm + "embeddings.patch_embedding.weight", {D, cfg->num_channels, cfg->patch_size, cfg->patch_size});
-  c->pos = c->add(vm + "embeddings.position_embedding.weight", {c->T, D});
-  c->prew = c->add(vm + "pre_layrnorm.weight", {D});
-  c->preb = c->add(vm + "pre_layrnorm.bias", {D});
-  for (int l = 0; l < cfg->num_hidden_layers; ++l) {
-    const std::string p = vm + "encoder.layers." + std::to_string(l) + ".";
-    VisLayer L;
-    L.kw = c->add(p + "self_attn.k_proj.weight", {D, D}); L.kb = c->add(p + "self_attn.k_proj.bias", {D});
-    L.vw = c->add(p + "self_attn.v_proj.weight", {D, D}); L.vb = c->add(p + "self_attn.v_proj.bias", {D});
-    L.qw = c->add(p + "self_attn.q_proj.weight", {D, D}); L.qb = c->add(p + "self_attn.q_proj.bias", {D});
-    L.ow = c->add(p + "self_attn.out_proj.weight", {D, D}); L.ob = c->add(p + "self_attn.out_proj.bias", {D});
-    L.ln1w = c->add(p + "layer_norm1.weight", {D}); L.ln1b = c->add(p + "layer_norm1.bias", {D});
-    L.f1w = c->add(p + "mlp.fc1.weight", {I, D}); L.f1b = c->add(p + "mlp.fc1.bias", {I});
-    L.f2w = c->add(p + "mlp.fc2.weight", {D, I}); L.f2b = c->add(p + "mlp.fc2.bias", {D});
-    L.ln2w = c->add(p + "layer_norm2.weight", {D}); L.ln2b = c->add(p + "layer_norm2.bias", {D});
-    c->layers.push_back(L);
-  }
-  c->postw = c->add(vm + "post_layernorm.weight", {D});
-  c->postb = c->add(vm + "post_layernorm.bias", {D});
-  c->proj = c->add("visual_projection.weight", {cfg->projection_dim, D});
+  c->cls = c->add_param(vm + "embeddings.class_embedding", {D});
+  c->patch = c->add_param(vm + "embeddings.patch_embedding.weight", {D, cfg->num_channels, cfg->patch_size, cfg->patch_size});
+  c->pos = c->add_param(vm + "embeddings.position_embedding.weight", {c->T, D});
+  c->prew = c->add_param(vm + "pre_layrnorm.weight", {D});
+  c->preb = c->add_param(vm + "pre_layrnorm.bias", {D});
+  c->layers = dfh::add_encoder_layers(*c, vm, cfg->num_hidden_layers, D, I);
+  c->postw = c->add_param(vm + "post_layernorm.weight", {D});
+  c->postb = c->add_param(vm + "post_layernorm.bias", {D});
+  c->proj = c->add_param("visual_projection.weight", {cfg->projection_dim, D});
   *out = c;
   return 0;
 }
 void dfh_clipv_destroy(dfh_clipv* c) { delete c; }
-int dfh_clipv_num_params(const dfh_clipv* c) { return (int)c->params.size(); }
-const char* dfh_clipv_param_name(const dfh_clipv* c, int i) { return (i >= 0 && i < (int)c->params.size()) ? c->params[i].name.c_str() : ""; }
-int dfh_clipv_param_ndim(const dfh_clipv* c, int i) { return (i >= 0 && i < (int)c->params.size()) ? (int)c->params[i].shape.size() : 0; }
-int dfh_clipv_param_dim(const dfh_clipv* c, int i, int d) {
-  return (i >= 0 && i < (int)c->params.size() && d >= 0 && d < (int)c->params[i].shape.size()) ? c->params[i].shape[d] : 0;
-}
-
-// x | ln | q k v (also the im2col rows of the patch conv) | attention (also the patch-conv output) | MLP hidden | pooled row
-static size_t clipv_ws_floats(const dfh_clipv* c, int batch) {
-  const size_t M = (size_t)batch * c->T, D = c->cfg.hidden_size, I = c->cfg.intermediate_size, K = c->Kp;
-  const size_t wide = 3 * D > K ? 3 * D : K;
-  return M * (D + D + wide + D + I) + (size_t)batch * D + 64;
-}
-size_t dfh_clipv_workspace_bytes(const dfh_clipv* c, int batch) {
-  return (c && batch > 0) ? clipv_ws_floats(c, batch) * sizeof(float) + 256 : 0;
-}
+int dfh_clipv_num_params(const dfh_clipv* c) { return c->num_params(); }
+const char* dfh_clipv_param_name(const dfh_clipv* c, int i) { return c->param_name(i); }
+int dfh_clipv_param_ndim(const dfh_clipv* c, int i) { return c->param_ndim(i); }
+int dfh_clipv_param_dim(const dfh_clipv* c, int i, int d) { return c->param_dim(i, d); }
+size_t dfh_clipv_workspace_bytes(const dfh_clipv* c, int batch) { return (c && batch > 0) ? c->workspace(nullptr, batch).bytes() : 0; }
 
 int dfh_clipv_attention(const float* qkv, float* out, int batch, int T, int heads, int head_dim, float scale, void* stream) {
   DFH_REQUIRE(qkv && out, "null argument");
@@ -261,11 +235,7 @@ int dfh_clipv_encode(dfh_clipv* c, const float* const* master_params, int count,
                      float* last_hidden_state, float* pooler_output, float* image_embeds, float* const* hidden_states,
                      void* workspace, size_t workspace_bytes, void* stream) {
   DFH_REQUIRE(c && master_params && pixel_values && last_hidden_state && workspace, "null argument");
-  DFH_REQUIRE(count == (int)c->params.size(), "master_params count does not match dfh_clipv_num_params");
-  for (int i = 0; i < count; ++i) {
-    DFH_REQUIRE(master_params[i] != nullptr, "null parameter pointer: " + c->params[i].name);
-    DFH_REQUIRE(((uintptr_t)master_params[i] & 15) == 0, "parameter pointer not 16-byte aligned: " + c->params[i].name);
-  }
+  if (int rc = dfh::require_params(*c, master_params, count, "dfh_clipv")) return rc;
   DFH_REQUIRE(batch > 0 && batch <= 65535, "batch must be in [1, 65535]");
   DFH_REQUIRE(workspace_bytes >= dfh_clipv_workspace_bytes(c, batch), "workspace smaller than dfh_clipv_workspace_bytes");
   DFH_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
@@ -276,73 +246,43 @@ int dfh_clipv_encode(dfh_clipv* c, const float* const* master_params, int count,
   const int T = c->T, D = g.hidden_size, I = g.intermediate_size, H = g.num_attention_heads, d = D / H, K = c->Kp;
   const int M = batch * T, Mp = batch * (T - 1);
   DFH_REQUIRE((double)batch * T < 2.0e9 / (3.0 * D > I ? 3.0 * D : I), "batch x tokens x width beyond 32-bit row offsets");
-  const size_t wide = 3 * (size_t)D > (size_t)K ? 3 * (size_t)D : (size_t)K;
-  float* x = (float*)workspace;
-  float* ln = x + (size_t)M * D;
-  float* qkv = ln + (size_t)M * D;
-  float* att = qkv + (size_t)M * wide;
-  float* hid = att + (size_t)M * D;
-  float* pooled = hid + (size_t)M * I;
+  const dfh::ClipWorkspace w = c->workspace(workspace, batch);
   const float* const* P = master_params;
   const float eps = g.layer_norm_eps, scale = 1.0f / sqrtf((float)d);
   const size_t hs_bytes = (size_t)M * D * sizeof(float);
-  auto tap = [&](int l, const float* src) -> int {
-    if (hidden_states && hidden_states[l] && hipMemcpyAsync(hidden_states[l], src, hs_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-      dfh::set_error("dfh_clipv_encode: hidden_states copy failed");
-      return -2;
-    }
-    return 0;
+  const dfh::ClipAccounting acct = {dfh::PC_LINEAR, dfh::CK_CLIPV_LINEAR, dfh::PC_LNORM, dfh::CK_CLIPV_LAYERNORM};
+  // hidden_states[l]: entry l of an array of pointers, any of which may be null
+  auto tap = [&](int l, const float* src) {
+    return dfh::tower_copy(hidden_states ? hidden_states[l] : nullptr, src, hs_bytes, s, "dfh_clipv_encode: hidden_states");
   };
-  auto lnorm = [&](const float* src, long ldx, int gi, int bi, float* dst, int rows) -> int {
-    dfh::ProfScope ps(dfh::PC_LNORM, 8.0 * rows * D, 8.0 * rows * D, s);
-    dfh::census(dfh::CK_CLIPV_LAYERNORM);
-    return dfh::clip_layernorm(src, ldx, P[gi], P[bi], dst, rows, D, eps, s);
-  };
-  auto linear = [&](const float* A, int lda, int wi, int Kd, int bi, const float* resid, float* out, int ld_out, int rows, int N, int act) -> int {
-    dfh::census(dfh::CK_CLIPV_LINEAR);
-    return dfh::clip_linear(A, lda, P[wi], Kd, bi >= 0 ? P[bi] : nullptr, resid, ld_out, out, ld_out, rows, N, act, dfh::PC_LINEAR, s);
-  };
+  auto attention = [&](const float* qkv, float* att) { return clipv_attention(qkv, att, batch, T, H, d, scale, s); };
   // embeddings: im2col -> qkv region, patch conv as a linear -> att region, + class token + positions -> ln, pre_layrnorm -> x
   {
     dfh::census(dfh::CK_CLIPV_EMBED);
     const long total = (long)Mp * K;
     {
       dfh::ProfScope ps(dfh::PC_OTHER, 0.0, 8.0 * total, s);
-      hipLaunchKernelGGL(clipv_im2col_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, pixel_values, qkv, g.num_channels,
+      hipLaunchKernelGGL(clipv_im2col_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, pixel_values, w.qkv, g.num_channels,
                          g.image_size, g.patch_size, c->grid, total);
       if (int rc = dfh::check_launch("clipv_im2col_kernel")) return rc;
     }
-    if (int rc = dfh::clip_linear(qkv, K, P[c->patch], K, nullptr, nullptr, 0, att, D, Mp, D, dfh::CLIP_ACT_NONE, dfh::PC_OTHER, s)) return rc;
+    if (int rc = dfh::clip_linear(w.qkv, K, P[c->patch], K, nullptr, nullptr, 0, w.att, D, Mp, D, dfh::CLIP_ACT_NONE, dfh::PC_OTHER, s)) return rc;
     {
       dfh::ProfScope ps(dfh::PC_OTHER, 1.0 * M * D, 8.0 * M * D, s);
-      hipLaunchKernelGGL(clipv_embed_kernel, dim3(M), dim3(256), 0, s, att, P[c->cls], P[c->pos], ln, T, D);
+      hipLaunchKernelGGL(clipv_embed_kernel, dim3(M), dim3(256), 0, s, w.att, P[c->cls], P[c->pos], w.ln, T, D);
       if (int rc = dfh::check_launch("clipv_embed_kernel")) return rc;
     }
   }
-  if (int rc = lnorm(ln, D, c->prew, c->preb, x, M)) return rc;
-  if (int rc = tap(0, x)) return rc;
-  for (size_t l = 0; l < c->layers.size(); ++l) {
-    const VisLayer& L = c->layers[l];
-    if (int rc = lnorm(x, D, L.ln1w, L.ln1b, ln, M)) return rc;
-    if (int rc = linear(ln, D, L.qw, D, L.qb, nullptr, qkv, 3 * D, M, D, dfh::CLIP_ACT_NONE)) return rc;
-    if (int rc = linear(ln, D, L.kw, D, L.kb, nullptr, qkv + D, 3 * D, M, D, dfh::CLIP_ACT_NONE)) return rc;
-    if (int rc = linear(ln, D, L.vw, D, L.vb, nullptr, qkv + 2 * D, 3 * D, M, D, dfh::CLIP_ACT_NONE)) return rc;
-    if (int rc = clipv_attention(qkv, att, batch, T, H, d, scale, s)) return rc;
-    if (int rc = linear(att, D, L.ow, D, L.ob, x, x, D, M, D, dfh::CLIP_ACT_NONE)) return rc;          // x += out_proj(attention)
-    if (int rc = lnorm(x, D, L.ln2w, L.ln2b, ln, M)) return rc;
-    if (int rc = linear(ln, D, L.f1w, D, L.f1b, nullptr, hid, I, M, I, g.hidden_act)) return rc;
-    if (int rc = linear(hid, I, L.f2w, I, L.f2b, x, x, D, M, D, dfh::CLIP_ACT_NONE)) return rc;         // x += fc2(act(fc1(.)))
-    if (int rc = tap((int)l + 1, x)) return rc;
-  }
-  if (hipMemcpyAsync(last_hidden_state, x, hs_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
-    dfh::set_error("dfh_clipv_encode: last_hidden_state copy failed");
-    return -2;
-  }
+  if (int rc = dfh::tower_layernorm(acct, w.ln, D, P[c->prew], P[c->preb], w.x, M, D, eps, s)) return rc;
+  if (int rc = tap(0, w.x)) return rc;
+  if (int rc = dfh::clip_blocks(P, c->layers, w, M, D, I, g.hidden_act, eps, acct, s, attention, tap)) return rc;
+  if (int rc = dfh::tower_copy(last_hidden_state, w.x, hs_bytes, s, "dfh_clipv_encode: last_hidden_state")) return rc;
   if (pooler_output || image_embeds) {
-    float* pl = pooler_output ? pooler_output : pooled;
-    if (int rc = lnorm(x, (long)T * D, c->postw, c->postb, pl, batch)) return rc;        // the class-token row of every image
+    float* pl = pooler_output ? pooler_output : w.tail;
+    if (int rc = dfh::tower_layernorm(acct, w.x, (long)T * D, P[c->postw], P[c->postb], pl, batch, D, eps, s)) return rc;   // the class-token row of every image
     if (image_embeds)
-      if (int rc = linear(pl, D, c->proj, D, -1, nullptr, image_embeds, g.projection_dim, batch, g.projection_dim, dfh::CLIP_ACT_NONE)) return rc;
+      if (int rc = dfh::tower_linear(acct, pl, D, P[c->proj], D, nullptr, nullptr, image_embeds, g.projection_dim, batch, g.projection_dim,
+                                     dfh::CLIP_ACT_NONE, s)) return rc;
   }
   return 0;
 }

@@ -244,7 +244,19 @@ DFH_DEVICE float wave_sum(float v) {
 
 // ---- host side ------------------------------------------------------------------------------
 #include <string>
+#include <vector>
 namespace dfh {
+// The master parameters of a model in checkpoint order, with the bodies of its dfh_<family>_num_params / _param_name / _param_ndim /
+// _param_dim entry points: an index or a dimension out of range answers "" / 0
+struct ParamDesc { std::string name; std::vector<int> shape; };
+struct ParamList {
+  std::vector<ParamDesc> params;
+  int add_param(const std::string& name, std::vector<int> shape) { params.push_back({name, std::move(shape)}); return (int)params.size() - 1; }
+  int num_params() const { return (int)params.size(); }
+  const char* param_name(int i) const { return i >= 0 && i < num_params() ? params[i].name.c_str() : ""; }
+  int param_ndim(int i) const { return i >= 0 && i < num_params() ? (int)params[i].shape.size() : 0; }
+  int param_dim(int i, int d) const { return d >= 0 && d < param_ndim(i) ? params[i].shape[d] : 0; }
+};
 void set_error(const std::string& msg);  // api.cpp
 int check_launch(const char* what);     // returns 0 or negative and records the message
 // Optional per-launch timing with HIP events recorded on the launch stream (bench.py roofline).

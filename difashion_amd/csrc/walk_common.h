@@ -28,8 +28,6 @@ struct PackOp {
   int cin_pad = 0;   // PK_CONV3: channels per tap in the packed layout (conv_in pads 4 -> 8)
 };
 
-struct ParamDesc { std::string name; std::vector<int> shape; };
-
 struct Tensor {
   bf16_t* p = nullptr; int H = 0, W = 0, C = 0;
   // GroupNorm statistics of this tensor written by the GEMM epilogue that produced it (gemm.h GemmArgs::gstat); null when the
@@ -87,17 +85,12 @@ struct OpTable {
 
 // Parameter table + packing plan of a model: the master parameters in checkpoint order (params), where each goes in the packed bf16 /
 // fp32 arenas (packs), and the arenas themselves.  The model's build() fills it through the helpers; pack_params() runs the plan.
-struct ParamTable {
-  std::vector<ParamDesc> params;
+struct ParamTable : dfh::ParamList {
   std::vector<PackOp> packs;
   size_t a16 = 0, a32 = 0;         // arena sizes in elements
   bf16_t* arena16 = nullptr; float* arena32 = nullptr;
   OpTable tab_pack, tab_pack_acc;
 
-  int add_param(const std::string& name, std::vector<int> shape) {
-    params.push_back({name, std::move(shape)});
-    return (int)params.size() - 1;
-  }
   size_t alloc16(size_t n) { size_t o = a16; a16 += (n + 127) & ~(size_t)127; return o; }
   size_t alloc32(size_t n) { size_t o = a32; a32 += (n + 63) & ~(size_t)63; return o; }
 
@@ -147,11 +140,7 @@ struct ParamTable {
     return tab_pack_acc.launch(arena32, arena16, s);
   }
 
-  // bodies of the dfh_{unet,vae}_num_params / param_* / arena*_bytes entry points
-  int num_params() const { return (int)params.size(); }
-  const char* param_name(int i) const { return params[i].name.c_str(); }
-  int param_ndim(int i) const { return (int)params[i].shape.size(); }
-  int param_dim(int i, int d) const { return params[i].shape[d]; }
+  // bodies of the dfh_{unet,vae}_arena*_bytes entry points (the table's own: dfh::ParamList)
   size_t arena16_bytes() const { return a16 * 2 + 256; }
   size_t arena32_bytes() const { return a32 * 4 + 256; }
 };

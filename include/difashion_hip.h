@@ -246,9 +246,10 @@ int dfh_clip_param_ndim(const dfh_clip* c, int i);
 int dfh_clip_param_dim(const dfh_clip* c, int i, int d);
 size_t dfh_clip_workspace_bytes(const dfh_clip* c, int batch, int seq_len);
 /* outputs = text_encoder(input_ids):
- *   master_params     : HOST array of `count` device pointers to the fp32 parameters, table order
+ *   master_params     : HOST array of `count` device pointers to the fp32 parameters, table order, each 16-byte aligned
  *   input_ids         : [batch][seq_len] int64 (tokenizer output, data_utils.py:107-110); causal mask only, no padding mask (the
- *                       reference passes input_ids alone)
+ *                       reference passes input_ids alone).  Ids outside [0, vocab_size) are CLAMPED here; refusing them, as
+ *                       nn.Embedding does, is the caller's part (the Python wrapper raises IndexError)
  *   last_hidden_state : [batch][seq_len][hidden_size] fp32 = outputs[0], after final_layer_norm
  *   pooler_output     : [batch][hidden_size] fp32 or NULL; the row at argmax(input_ids) when eos_token_id == 2 (transformers 4.32.1),
  *                       else at the first eos_token_id

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """What the Python model wrappers build, as text: run it on two commits and diff the outputs (CPU; needs only the built library).
 
-Per model (U-Net at SD-1.5 defaults and tiny, VAE at defaults and tiny, CLIP tiny and CLIP-L), once with ``init_seed=0`` and once
-with ``init_seed=None``: the native ``param_table()``, the ``state_dict()`` key order and a SHA-256 over the parameter bytes.  Then
-the four wrappers (MutualEncoder included) through ``save_pretrained`` / ``from_pretrained``: file names, sorted ``config.json``
-keys, what the reloaded object keeps in ``.config``, and whether the state dicts agree bit for bit.
+Per model (U-Net at SD-1.5 defaults and tiny, VAE at defaults and tiny, CLIP tiny and CLIP-L, two tiny CLIP vision towers), once with
+``init_seed=0`` and once with ``init_seed=None``: the native ``param_table()``, the ``state_dict()`` key order and a SHA-256 over the
+parameter bytes; the ViT-H/14 vision table without its weights.  Then the five wrappers (MutualEncoder included) through
+``save_pretrained`` / ``from_pretrained``: file names, sorted ``config.json`` keys, what the reloaded object keeps in ``.config``,
+and whether the state dicts agree bit for bit.
 
-A refactor of difashion_amd/{_native,unet,vae,clip,mutual}.py must leave this output unchanged (profiles/native_module_identity.txt).
+A refactor of difashion_amd/{_native,unet,vae,clip,clip_vision,mutual}.py must leave this output unchanged
+(profiles/native_module_identity.txt).
 The hashes are NOT a test: they would pin torch's CPU generator, not this code."""
 import hashlib
 import json
@@ -18,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 import difashion_amd as da
+from tests.helpers_clip_vision import TINY_GELU, TINY_QUICKGELU, VIT_H_14
 
 TINY_UNET = dict(sample_size=16, in_channels=8, block_out_channels=(64, 128, 256, 256), cross_attention_dim=64, attention_head_dim=(2, 2, 2, 2))
 TINY_VAE = dict(block_out_channels=(32, 64, 64, 64), sample_size=32)
@@ -25,7 +28,9 @@ TINY_CLIP = dict(vocab_size=1000, hidden_size=64, intermediate_size=128, num_hid
                  pad_token_id=999)
 MODELS = [("unet sd15", da.UNet2DConditionModel, {}), ("unet tiny", da.UNet2DConditionModel, TINY_UNET),
           ("vae default", da.AutoencoderKL, {}), ("vae tiny", da.AutoencoderKL, TINY_VAE),
-          ("clip tiny", da.CLIPTextModel, TINY_CLIP), ("clip L", da.CLIPTextModel, {})]
+          ("clip tiny", da.CLIPTextModel, TINY_CLIP), ("clip L", da.CLIPTextModel, {}),
+          ("clip vision tiny quick_gelu", da.CLIPVisionModelWithProjection, TINY_QUICKGELU.kwargs()),
+          ("clip vision tiny gelu", da.CLIPVisionModelWithProjection, TINY_GELU.kwargs())]
 
 
 def digest(sd):
@@ -78,6 +83,12 @@ def main():
     print(f"torch {torch.__version__}")
     for title, cls, kw in MODELS:
         describe(title, cls, kw)
+    vit = da.CLIPVisionModelWithProjection(init_seed=None, **TINY_GELU.kwargs())
+    vit.register_to_config(**VIT_H_14.kwargs())                         # the full-size table from the library alone: no weights
+    table = vit.param_table()
+    print(f"== clip vision ViT-H/14: {len(table)} table entries, {sum(torch.Size(s).numel() for _, s in table)} values, no weights")
+    for name, shape in table:
+        print(f"table {name} {shape}")
     unet = da.UNet2DConditionModel(init_seed=3, **TINY_UNET)
     unet.register_to_config(decay=0.9999, optimization_step=7)          # what diffusers' EMAModel.save_pretrained adds
     back = round_trip("unet tiny", unet, da.UNet2DConditionModel.from_pretrained, max_batch=3)
@@ -91,6 +102,8 @@ def main():
     print(f"max_batch {back.max_batch}; conv_in {tuple(back.conv_in.weight.shape)}")
     round_trip("vae tiny", da.AutoencoderKL(init_seed=3, **TINY_VAE), da.AutoencoderKL.from_pretrained)
     round_trip("clip tiny", da.CLIPTextModel(init_seed=3, **TINY_CLIP), da.CLIPTextModel.from_pretrained)
+    round_trip("clip vision tiny", da.CLIPVisionModelWithProjection(init_seed=3, **TINY_QUICKGELU.kwargs()),
+               da.CLIPVisionModelWithProjection.from_pretrained)
     torch.manual_seed(4)
     enc = da.MutualEncoder(cate_num=4, cate_emb_size=8, latent_channels=4, latent_size=16, hid_dim=32)
     enc.register_to_config(decay=0.9999)

@@ -171,8 +171,51 @@ def test_clip_context_and_parameter_table_without_a_gpu():
     names = [n for n, _ in m.param_table()]
     assert names[0] == "text_model.embeddings.token_embedding.weight" and names[2] == "text_model.encoder.layers.0.self_attn.k_proj.weight"
     assert names[-1] == "text_model.final_layer_norm.bias" and len(names) == 2 + 16 * 2 + 2 == len(list(m.parameters()))
-    assert lib.dfh_clip_workspace_bytes(m._make_ctx(), 51, 77) > 51 * 77 * (6 * 64 + 128) * 4
+    # x, ln, q k v, attention (6 D a row) + the MLP hidden, 64 floats of slack, 256 bytes for alignment: pinned exactly
+    assert lib.dfh_clip_workspace_bytes(m._make_ctx(), 51, 77) == (51 * 77 * (6 * 64 + 128) + 64) * 4 + 256
+    assert lib.dfh_clip_workspace_bytes(m._make_ctx(), 3, 16) == (3 * 16 * (6 * 64 + 128) + 64) * 4 + 256
+    _lib.call("dfh_clip_create", C.byref(_lib.CLIPConfigC(49408, 768, 3072, 12, 12, 77, 1, 1e-5)), C.byref(h))       # CLIP-L
+    assert lib.dfh_clip_workspace_bytes(h, 51, 77) == (51 * 77 * (6 * 768 + 3072) + 64) * 4 + 256
+    lib.dfh_clip_destroy(h)
     # both checkpoint key layouts load (4.32.1 nests under text_model., newer transformers releases do not)
     sd = {k[len("text_model."):]: v for k, v in m.state_dict().items()}
     sd["embeddings.position_ids"] = torch.arange(77)[None]
     da.CLIPTextModel(vocab_size=100, hidden_size=64, intermediate_size=128, num_hidden_layers=2, num_attention_heads=4).load_state_dict(sd)
+
+
+def test_clip_encode_guards_its_parameter_pointers_before_any_launch():
+    """Count, null and 16-byte alignment of the parameter pointers (the kernels read them as float4) are refused on the host, by
+    name, before any HIP call: the addresses are made up and no GPU is present."""
+    m = da.CLIPTextModel(vocab_size=100, hidden_size=64, intermediate_size=128, num_hidden_layers=2, num_attention_heads=4, init_seed=None)
+    lib, h = _lib.raw(), m._make_ctx()
+    try:
+        n = lib.dfh_clip_num_params(h)
+        buf, need = C.c_void_p(4096), lib.dfh_clip_workspace_bytes(h, 2, 16)
+        enc = lambda arr, cnt: _lib.call("dfh_clip_encode", h, arr, cnt, buf, buf, None, 2, None, buf, need, 2, 16, None)
+        with pytest.raises(_lib.DfhError, match="count does not match dfh_clip_num_params"):
+            enc((C.c_void_p * n)(*([4096] * n)), n - 1)
+        with pytest.raises(_lib.DfhError, match="null parameter pointer: text_model.embeddings.position_embedding.weight"):
+            enc((C.c_void_p * n)(*([4096, 0] + [4096] * (n - 2))), n)
+        with pytest.raises(_lib.DfhError, match="not 16-byte aligned: text_model.encoder.layers.0.self_attn.k_proj.weight"):
+            enc((C.c_void_p * n)(*([4096] * 2 + [4100] + [4096] * (n - 3))), n)
+        with pytest.raises(_lib.DfhError, match="not 16-byte aligned: text_model.final_layer_norm.bias"):
+            enc((C.c_void_p * n)(*([4096] * (n - 1) + [4104])), n)
+    finally:
+        lib.dfh_clip_destroy(h)
+
+
+def test_parameter_accessors_answer_empty_out_of_range():
+    """dfh_{unet,vae,clip}_param_name / _ndim / _dim check index and dimension (the clipv family: tests/test_clip_vision_cpu.py)."""
+    models = [_cfg_model(unet_ref.TINY), da.AutoencoderKL(block_out_channels=(32, 64, 64, 64), sample_size=32, init_seed=None),
+              da.CLIPTextModel(vocab_size=100, hidden_size=64, intermediate_size=128, num_hidden_layers=2, num_attention_heads=4, init_seed=None)]
+    for m in models:
+        name, ndim, dim, h = m._entry("param_name"), m._entry("param_ndim"), m._entry("param_dim"), m._make_ctx()
+        try:
+            n = m._entry("num_params")(h)
+            assert n == len(list(m.parameters())) and name(h, n - 1) != b"" and dim(h, 0, ndim(h, 0) - 1) > 0
+            for i in (-1, n, 10_000_000):
+                assert name(h, i) == b"" and ndim(h, i) == 0 and dim(h, i, 0) == 0, (m.family, i)
+            for d in (-1, ndim(h, 0), 9):
+                assert dim(h, 0, d) == 0, (m.family, d)
+        finally:
+            m._entry("destroy")(h)

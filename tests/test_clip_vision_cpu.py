@@ -3,6 +3,7 @@ all three places (header, both libraries, ctypes), the parameter table against t
 state dict, config checks, refusals and the checkpoint directory.  No compute call is made here; the arithmetic is checked on the
 GPU (tests/test_gpu_clip_vision.py) against the fixtures of tests/golden/make_golden_clip_vision.py."""
 import ctypes as C
+import dataclasses
 import json
 import os
 import re
@@ -14,7 +15,7 @@ import torch
 
 import difashion_amd as da
 from difashion_amd import _lib
-from tests.helpers_clip_vision import (CASES, FULL_SIZE_ROWS, TINY_QUICKGELU, VIT_H_14, case_inputs, checksum, fixture_path,
+from tests.helpers_clip_vision import (CASES, FULL_SIZE_ROWS, TINY_GELU, TINY_QUICKGELU, VIT_H_14, case_inputs, checksum, fixture_path,
                                        load_fixture, param_shapes)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -91,6 +92,23 @@ def test_vit_h_14_table_equals_the_real_class_without_allocating_weights():
         assert M * (6 * 1280 + 5120) * 4 < lib.dfh_clipv_workspace_bytes(h, 50) < M * (6 * 1280 + 5120) * 4 * 1.01
         assert lib.dfh_clipv_workspace_bytes(h, 0) == 0
         assert lib.dfh_clipv_param_name(h, 10_000) == b"" and lib.dfh_clipv_param_dim(h, 1, 9) == 0
+    finally:
+        lib.dfh_clipv_destroy(h)
+
+
+@pytest.mark.parametrize("cfg,im2col_wider", [(TINY_QUICKGELU, False), (TINY_GELU, True), (dataclasses.replace(TINY_GELU, image_size=56), True),
+                                              (VIT_H_14, False)], ids=["tiny_patch8", "tiny_patch14", "tiny_56_patch14", "vit_h_14"])
+def test_workspace_bytes_are_pinned_exactly(cfg, im2col_wider):
+    """x, ln, attention (3 D a row), the q k v region -- max(3 D, C p^2) wide, since it holds the im2col rows of the patch conv too --
+    the MLP hidden, one pooled row per image, 64 floats of slack, 256 bytes for alignment."""
+    h = C.c_void_p()
+    _lib.call("dfh_clipv_create", C.byref(_config_c(cfg)), C.byref(h))
+    lib = _lib.raw()
+    try:
+        D, I, T, K = cfg.hidden_size, cfg.intermediate_size, cfg.num_tokens, cfg.num_channels * cfg.patch_size ** 2
+        assert (K > 3 * D) == im2col_wider                                       # both branches of the max are covered
+        for B in (1, 3, 50):
+            assert lib.dfh_clipv_workspace_bytes(h, B) == (B * T * (3 * D + max(3 * D, K) + I) + B * D + 64) * 4 + 256, B
     finally:
         lib.dfh_clipv_destroy(h)
 

@@ -72,6 +72,18 @@ def test_error_behaviour_follows_the_transformers_class():
     assert m.dtype == torch.float32 and not any(p.requires_grad for p in m.parameters())
 
 
+def test_text_encode_leaves_the_vision_towers_census_alone():
+    """The two towers share one walk over the blocks but not its accounting: the text tower's launches are not counted."""
+    from difashion_amd import _lib
+    cfg, params, ids = case_inputs("tiny_short_seq")
+    m = hip_clip(cfg, params)
+    _lib.census_reset()
+    m(ids.to(DEV), output_hidden_states=True)
+    torch.cuda.synchronize()
+    vision = {k: v for k, v in _lib.census().items() if k.startswith("clipv_")}
+    assert len(vision) == 4 and not any(vision.values()), vision
+
+
 def test_prompt_table_built_with_the_hip_encoder():
     """PromptTable.build (the once-per-run encoding of the closed prompt set, data_utils.py:96-111) through the HIP encoder equals
     encoding each batch's prompts on the fly the way difashion.py:218-224 / :340-353 do."""
