@@ -83,6 +83,15 @@ class GemmDesc(C.Structure):
     ]
 
 
+class GemmPlanExtra(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("nbatch", "phase2x", "w_blocked", "n_split", "want_rowstat", "ln_cnt", "pre_out")]
+
+
+class GemmPlanInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kernel", "tile", "bm", "bn", "stages", "lean", "wide", "split", "n_major", "tm_xm", "tm_gm",
+                                       "gstat_rows", "rowstat_bn", "census")] + [("line", C.c_char * 512)]
+
+
 class Fp8GemmDesc(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("lda", C.c_int),
@@ -185,6 +194,7 @@ SIGNATURES = {
     "dfh_gemm_wgrad_partial_floats": (_sz, [C.POINTER(GemmDesc), _i]),
     "dfh_groupnorm_fold": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, C.c_float, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "dfh_gemm_wgrad_plan": (_i, [C.POINTER(GemmDesc), _i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dfh_gemm_plan": (_i, [C.POINTER(GemmDesc), C.POINTER(GemmPlanExtra), C.POINTER(GemmPlanInfo)]),
     "dfh_colsum": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "dfh_groupnorm": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _vp, _vp]),
     "dfh_gemm_gstat": (_i, [C.POINTER(GemmDesc), _vp, C.POINTER(C.c_int)]),

@@ -11,6 +11,7 @@
 #include "dfh_common.h"
 #include "elementwise.h"
 #include "gemm.h"
+#include "gemm_plan.h"
 #include "mlp_fused.h"
 #include "norm.h"
 #include "wgrad.h"
@@ -19,6 +20,7 @@
 namespace dfh {
 static thread_local std::string g_err;
 void set_error(const std::string& msg) { g_err = msg; }
+const char* last_error() { return g_err.c_str(); }
 int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -118,7 +120,7 @@ void dfh_census_reset(void) { std::memset(dfh::g_census, 0, sizeof(dfh::g_census
 int dfh_census_count(void) { return dfh::CK_COUNT; }
 const char* dfh_census_name(int i) { return (i >= 0 && i < dfh::CK_COUNT) ? dfh::kCensusNames[i] : ""; }
 long dfh_census_get(int i) { return (i >= 0 && i < dfh::CK_COUNT) ? dfh::g_census[i] : -1; }
-const char* dfh_last_error(void) { return dfh::g_err.c_str(); }
+const char* dfh_last_error(void) { return dfh::last_error(); }
 #define DFH_STR2(x) #x
 #define DFH_STR(x) DFH_STR2(x)
 #ifdef DFH_F16
@@ -196,6 +198,37 @@ int dfh_gemm_wgrad_plan(const dfh_gemm_desc* d, int msplit, int* tiles, int* who
   if (int rc = fill_wgrad(d, nullptr, 8, nullptr, 8, msplit, w)) return rc;
   dfh::wgrad_plan_only(w);
   *tiles = w.xblocks; *whole_tiles = w.whole; *slices = w.msplit;
+  return 0;
+}
+
+int dfh_gemm_plan(const dfh_gemm_desc* d, const dfh_gemm_plan_extra* x, dfh_gemm_plan_info* out) {
+  DFH_REQUIRE(d && out, "null argument");
+  std::memset(out, 0, sizeof(*out));
+  static float present[4];            // stands for every pointer the plan only tests for presence
+  dfh_gemm_desc t = *d;
+  if (!t.W) t.W = present;
+  if (!t.out) t.out = present;
+  if (!t.zero_page) t.zero_page = present;
+  if (!t.partial) t.partial = present;
+  GemmArgs g;
+  if (int rc = fill_gemm(&t, &g)) return rc;
+  if (d->gstat_cpg > 0 && d->gstat_hw > 0) { g.gstat = present; g.gstat_cpg = d->gstat_cpg; g.gstat_hw = d->gstat_hw; }
+  if (x) {
+    g.nbatch = x->nbatch; g.w_blocked = x->w_blocked;
+    if (x->phase2x) { g.phase2x = x->phase2x; g.ntaps = 4; g.nbatch = 4; }
+    if (x->n_split > 0) { g.out2 = present; g.ld_out2 = g.rows_per_b; g.n_split = x->n_split; }
+    if (x->want_rowstat) g.rowstat = present;
+    if (x->ln_cnt > 0) { g.ln_stat = present; g.ln_s = present; g.ln_cnt = x->ln_cnt; g.ln_parts = g.p_c[0] / x->ln_cnt; g.ln_eps = 1e-5f; }
+    if (x->pre_out) { g.pre_out = present; g.ld_pre = g.N; }
+  }
+  const GemmArgs given = g;
+  dfh::GemmPlan p;
+  const int rc = dfh::gemm_plan(g, dfh::gemm_force_decode(d->force_tile, d->force_split, d->force_order), dfh::GemmKnobs::from_env(), p);
+  dfh::gemm_plan_format(out->line, sizeof(out->line), given, rc ? nullptr : &p, rc ? dfh::last_error() : nullptr);
+  if (rc) return rc;
+  out->kernel = p.kernel; out->tile = p.tile; out->bm = p.bm; out->bn = p.bn; out->stages = p.stages; out->lean = p.lean; out->wide = p.wide;
+  out->split = p.split; out->n_major = p.n_major; out->tm_xm = p.tm_xm; out->tm_gm = p.tm_gm; out->gstat_rows = p.gstat_rows;
+  out->rowstat_bn = p.rowstat_bn; out->census = p.census;
   return 0;
 }
 

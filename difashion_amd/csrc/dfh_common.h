@@ -258,6 +258,7 @@ struct ParamList {
   int param_dim(int i, int d) const { return d >= 0 && d < param_ndim(i) ? params[i].shape[d] : 0; }
 };
 void set_error(const std::string& msg);  // api.cpp
+const char* last_error();                // the message of the last refusal on this thread (dfh_last_error)
 int check_launch(const char* what);     // returns 0 or negative and records the message
 // Optional per-launch timing with HIP events recorded on the launch stream (bench.py roofline).
 enum ProfClass { PC_CONV3 = 0, PC_LINEAR = 1, PC_ATTN = 2, PC_GNORM = 3, PC_LNORM = 4, PC_SPLITK = 5, PC_OTHER = 6,

@@ -129,6 +129,23 @@ DFH_DEVICE float2 ln_row_stats(const GemmArgs& a, int m) {
 }
 #endif
 
+// The public force_tile ids (dfh_gemm_desc::force_tile, gemm_launch): 0 = the heuristics.  Decoded once, by gemm_force_decode (gemm_plan.h).
+// A pinned kernel that cannot take the launch (fp32 / transposed output, GEGLU, N % 8 ...) falls back to the heuristic tile.
+enum GemmForceTile {
+  GF_AUTO = 0,
+  GF_TILE_256x160 = 1, GF_TILE_256x128 = 2, GF_TILE_128x64 = 3, GF_TILE_128x160 = 4, GF_TILE_128x128 = 5,   // gemm_bf16_kernel tiles (kGemmTiles[id - 1])
+  GF_WIDE = 6,               // gemm_wide_kernel 256 x 160; 7 / 8 = its 128 x 160 / 256 x 320 experiment variants (probe builds), 9 = the 256 x 128 sibling
+  GF_WIDE_128 = 7, GF_WIDE_320 = 8, GF_WIDE_SIB = 9,
+  GF_8WAVE = 10,             // the eight-wave 128 x 160 tile, one tile per workgroup (the default tile, pinned)
+  GF_WS_160 = 11, GF_WS_128 = 12,     // probe builds: the wave-specialised kernel
+  GF_ABLATE_FIRST = 13, GF_ABLATE_LAST = 18,   // probe builds: k-loop ablations of the wide kernel (19 is refused with them)
+  GF_HALO = 20,              // probe builds: the halo-patch conv kernel
+  GF_BIG = 21,               // the 256 x 320 eight-wave tile
+  GF_BIG_GEGLU = 23,         // the 256 x 256 GEGLU tile
+  GF_PERSIST = 24,           // probe builds: the persistent 128 x 160 kernel
+  GF_TOKEN_LINEAR = 30,      // probe builds: the register-resident token linear; the product build ends in the wide launcher's refusal
+};
+
 namespace dfh {
 int gemm_fp8_launch(Fp8GemmArgs a, hipStream_t stream);
 // out[sl][b] = max |x| over rows row0[sl] .. row0[sl] + nrows[sl] - 1 (cols columns each) of batch element b of a bf16 [B][.][ld] tensor
@@ -139,8 +156,8 @@ int quant_rows_fp8_launch(const bf16_t* x, int ldx, uint8_t* q, float* scale, in
 // LayerNorm whose output is quantised per token: q [M][C] e4m3, scale [M]
 int layernorm_fp8_launch(const bf16_t* x, const float* gamma, const float* beta, uint8_t* q, float* scale, int M, int C, float eps,
                          hipStream_t stream);
-// Picks a tile shape + split-K factor, launches, and (if split) launches the reduce.  ``partial``
-// must hold gemm_partial_floats(...) floats when the heuristic splits.
+// Plans the launch (gemm_plan.h: tile shape, split-K factor, tile order ...), launches, and (if split) launches the reduce.
+// ``partial`` must hold gemm_partial_floats(...) floats when the heuristic splits.  The host rules below live in gemm_plan.hip.
 int gemm_launch(GemmArgs a, hipStream_t stream, int force_tile = 0, int force_split = 0, int force_order = -1,
                 int* gstat_rows = nullptr,        // *gstat_rows: pixel rows per statistics chunk a.gstat was filled with (256 / 128), 0 = not filled
                 int* rowstat_bn = nullptr);       // *rowstat_bn: column tile of the a.rowstat records written (0 = none: kernel / shape cannot)
@@ -176,7 +193,8 @@ size_t gemm_partial_floats(const GemmArgs& a);
 int gemm_count_ksteps(const GemmArgs& a);
 // 256 x 160 wide-tile variant (gemm_wide.hip): higher arithmetic intensity against the LDS staging path
 bool gemm_wide_eligible(const GemmArgs& a);
-int gemm_wide_pick(const GemmArgs& a);                       // 0 none, 1 = 256 x 160, 2 = 128 x 160
+int gemm_wide_pick(const GemmArgs& a);                       // 0 none, 1 = 256 x 160, 4 = 256 x 128
+int gemm_wide_ksteps(const GemmArgs& a);                     // 32-deep k-steps of the wide kernel
 int gemm_wide_launch(GemmArgs a, hipStream_t stream, int variant = 1);
 #ifdef DFH_PROBES   // scripts/probes/kernels: experiments that lost their A/B, built only into the probe library
 // wave-specialised 256 x {160,128} kernel (gemm_ws.hip): loader waves + matrix waves, one workgroup per CU

@@ -23,12 +23,10 @@
 #include "gemm.h"
 #include "gemm_kiter.h"
 #include "gemm_wide_epilogue.h"
-#include "norm.h"   // GN_MAX_CHUNKS: what the consuming GroupNorm kernels accept per (image, group)
-#ifdef DFH_PROBES
-#include "token_linear.h"
-#endif
+#include "gemm_plan.h"
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -798,399 +796,69 @@ int launch_tile(const GemmArgs& a, hipStream_t stream) {
   return dfh::check_launch("gemm_bf16_kernel");
 }
 
-struct TileInfo { int bm, bn; };
-// variant ids (force_tile - 1):
-//   0: 256x160 8 waves 3 stages   1: 256x128 8 waves 3 stages   2: 128x64 4 waves 3 stages
-//   3: 128x160 4 waves 2 stages   4: 128x128 4 waves 2 stages
-//   5: 128x160 EIGHT waves (4 x 2, 32 x 80 each) 2 stages, external id 10 (ids 6-9 are the wide kernel) -- the default
-//      128 x 160 kernel: issuing a k-step's 36 LDS-DMA pieces costs a wave ~100 cycles apiece during which it issues no
-//      MFMA, so with one wave per SIMD (a 4-wave workgroup alone on its CU: the 256-tile launches of the 16x16 level) a
-//      k-step takes 0.93 us against 0.29 us of MFMA work; two waves per SIMD overlap the two (0.75 us; 12.6 / 25.0 / 69.2
-//      vs 15.0 / 28.3 / 78.5 us on 4096 x 1280 x {320, 1280, 5120}), and at two workgroups per CU (122 VGPRs: 16 waves
-//      fit) it still wins 4-5 % (scripts/gemm_deepring_probe.py).  A 4-stage ring on the 4-wave tile gained nothing.
-constexpr TileInfo kTiles[6] = {{256, 160}, {256, 128}, {128, 64}, {128, 160}, {128, 128}, {128, 160}};
-constexpr int kNumTiles = 5;                      // ids 1..5 of force_tile; the eight-wave 128 x 160 variant is id 10
-constexpr int kEightWave = 5;
-
-// one plain K segment of a multiple of 64 channels, W rows long enough: the LEAN k-loop applies
-bool lean_plain(const GemmArgs& a) {
-  // same-box A/B (scripts/gemm_lean_probe.py): 4096 x 1280 x {1280, 5120} 26.8 -> 25.7 / 77 -> 71 us (one workgroup per CU),
-  // 0-3 % at two workgroups per CU -- the LDS-DMA issue itself (~100 cycles per 1-KB piece), not its address arithmetic,
-  // is what paces the loop
-  if (a.ntaps != 0 || a.nplain < 1 || a.p_c[0] % BK != 0 || a.p_c[0] <= 0) return false;
-  // 32-bit byte offsets from the segment / weight-plane bases inside the kernel
-  const double amax = (double)a.M * std::max(a.p_c[0], a.nplain > 1 ? a.p_c[1] : 0) * 2.0, wmax = (double)a.N * a.ldw * 2.0;
-  if (amax >= 4.0e9 || wmax >= 4.0e9) return false;
-  return a.nplain == 1 || (a.p_c[1] % BK == 0 && a.p_c[1] > 0);
-}
-
-// the "big" tile: 256 x 320, eight waves, 64-deep k-steps (see the kernel's WEPI note)
-// the GEGLU projections on a 256 x 256 eight-wave tile (128 x 64 per wave: whole (value, gate) block pairs inside a wave)
-int launch_big_geglu(const GemmArgs& a, hipStream_t s) {
-  return lean_plain(a) ? launch_tile<256, 256, 2, 4, 2, true, true>(a, s) : launch_tile<256, 256, 2, 4, 2, false, true>(a, s);
-}
-
-int launch_big(const GemmArgs& a, hipStream_t s) {
+// the gemm_bf16_kernel instantiation a GK_TILE / GK_BIG / GK_BIG_GEGLU plan names: tile, ring depth and LEAN k-loop are plan fields (gemm_plan.hip)
+int launch_planned(const dfh::GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+  // the GEGLU projections on a 256 x 256 eight-wave tile (128 x 64 per wave: whole (value, gate) block pairs inside a wave)
+  if (p.kernel == dfh::GK_BIG_GEGLU) return p.lean ? launch_tile<256, 256, 2, 4, 2, true, true>(a, s) : launch_tile<256, 256, 2, 4, 2, false, true>(a, s);
+  // the "big" tile: 256 x 320, eight waves, 64-deep k-steps (see the kernel's WEPI note)
   // (a 128 x 320 sibling for the 32x32 level -- one tile per CU there too -- was measured and dropped: equal to the eight-wave
   //  128 x 160 kernel in isolation, conv3x3 class +0.3 ms per step in situ: profiles/r03/big_tile_probe.txt)
-  return lean_plain(a) ? launch_tile<256, 320, 2, 4, 2, true, true>(a, s) : launch_tile<256, 320, 2, 4, 2, false, true>(a, s);
-}
-
-int launch_variant(int tile, const GemmArgs& a, hipStream_t s) {
-  switch (tile) {
+  if (p.kernel == dfh::GK_BIG) return p.lean ? launch_tile<256, 320, 2, 4, 2, true, true>(a, s) : launch_tile<256, 320, 2, 4, 2, false, true>(a, s);
+  switch (p.tile) {
     case 0: return launch_tile<256, 160, 4, 2, 3>(a, s);
     case 1: return launch_tile<256, 128, 4, 2, 3>(a, s);
     case 2: return launch_tile<128, 64, 2, 2, 3>(a, s);
     case 3: return launch_tile<128, 160, 2, 2, 2>(a, s);
-    case 5: {
-      // launches of at most ~one workgroup per CU (the 8x8-level Winograd GEMM: 16 planes x 256 rows = 256 workgroups; the 16x16-level token
-      // linears), each a chain of k-steps that wait for lines requested one stage ahead: a 4-stage ring keeps three stages in flight.
-      // DFH_DEEP4=0 turns it off (A/B).
-      static const bool deep4_off = [] { const char* e = getenv("DFH_DEEP4"); return e && e[0] == '0'; }();
-      static const bool deep4_all = [] { const char* e = getenv("DFH_DEEP4"); return !(e && e[0] == '1'); }();     // 1: batched launches only (A/B: 16.32 -> 16.25 ms with single launches too)
-      const long wgs = (long)((a.M + 127) / 128) * ((a.N + 159) / 160) * (a.nbatch > 1 ? a.nbatch : 1) * a.ksplit;
-      if (!deep4_off && (a.nbatch > 1 || deep4_all) && wgs <= 320) return lean_plain(a) ? launch_tile<128, 160, 4, 2, 4, true>(a, s) : launch_tile<128, 160, 4, 2, 4>(a, s);
-      return lean_plain(a) ? launch_tile<128, 160, 4, 2, 2, true>(a, s) : launch_tile<128, 160, 4, 2, 2>(a, s);
-    }
+    case dfh::kEightWave:
+      if (p.stages == 4) return p.lean ? launch_tile<128, 160, 4, 2, 4, true>(a, s) : launch_tile<128, 160, 4, 2, 4>(a, s);     // the deep ring (DFH_DEEP4)
+      return p.lean ? launch_tile<128, 160, 4, 2, 2, true>(a, s) : launch_tile<128, 160, 4, 2, 2>(a, s);
     default: return launch_tile<128, 128, 2, 2, 2>(a, s);
   }
+}
+
+// DFH_GEMM_PLAN_DUMP=<file>: one line per gemm_launch call, the launch's shape key and its plan (or refusal), appended
+FILE* plan_dump_file() {
+  static FILE* const f = [] { const char* path = getenv("DFH_GEMM_PLAN_DUMP"); return path && path[0] ? fopen(path, "a") : nullptr; }();
+  return f;
 }
 
 }  // namespace
 
 namespace dfh {
 
-int gemm_count_ksteps(const GemmArgs& a) {
-  int n = a.ntaps * ((a.conv_c + BK - 1) / BK);
-  for (int i = 0; i < a.nplain; ++i) n += (a.p_c[i] + BK - 1) / BK;
-  return n;
-}
-
-int gemm_pick_split(const GemmArgs& a, int* tile_out) {
-  // column tile: 160 when it divides N (320/640/1280/...), else 128 (GEGLU needs 32-aligned pairs), 64 for N <= 64
-  const bool geglu = a.act == ACT_GEGLU;
-  const bool n160 = !geglu && (a.N % 160 == 0 || (a.N % 128 != 0 && a.N > 128));
-  // Measured on MI355X (scripts/gemm_microbench.py): the 128-row / 4-wave / 2-stage variants at two
-  // workgroups per CU beat the 256-row / 8-wave / 3-stage ring on every U-Net shape except the 8x8 level.
-  int tile;
-  if (a.N <= 64 && !geglu) tile = 2;
-  else if (a.M > 128 && a.M <= 1024 && gemm_count_ksteps(a) >= 64) tile = n160 ? 0 : 1;
-  else tile = n160 ? kEightWave : 4;   // same-box A/B over the whole step: linear class 7.65 -> 7.33 ms, conv3x3 6.92 -> 6.87 ms
-  const TileInfo ti = kTiles[tile];
-  const int blocks = ((a.M + ti.bm - 1) / ti.bm) * ((a.N + ti.bn - 1) / ti.bn);
-  const int ksteps = gemm_count_ksteps(a);
-  int split = 1;
-  if (!geglu && blocks < 384 && ksteps >= (a.ntaps ? 64 : 160)) {     // plain K = 5120 (80 k-steps) loses: 67 -> 72 us
-    // deep-K launches that leave CUs idle or at one workgroup each (16x16 level at batch 16: 256 tiles; 8x8 level: 64-128):
-    // split K until about 512 workgroups are resident.  The slab round trip pays for itself on the 3x3 convs
-    // (M=4096: 205 -> 149 us with 2 slices; M=2048: 111 -> 78 us with 4; scripts/gemm_split_probe*.py)
-    const int target = ti.bm == 256 ? 256 : 512;        // the 8-wave 256-row tiles run one workgroup per CU
-    split = std::max(1, std::min((target + blocks / 2) / blocks, ksteps / 16));
-  } else if (!geglu && blocks < 160 && ksteps >= 16) {
-    // shallow K (1x1 / linear): more than two slices cost more in slab traffic than they win
-    split = std::min({(256 + blocks - 1) / blocks, ksteps / 8, 64});
-    if (split < 1) split = 1;
-  }
-  if (tile_out) *tile_out = tile;
-  return split;
-}
-
-size_t gemm_partial_floats(const GemmArgs& a) {
-  if (a.nbatch > 1) return 0;     // batched launches never split K
-  int tile;
-  const int s = gemm_pick_split(a, &tile);
-  return s > 1 ? (size_t)s * a.M * a.N : 0;
-}
-
-// Tile order of a launch (dfh_common.h tile_coords) for a bm x bn tile.  DFH_TMAP="xm,gm" pins it for every launch (probe).
-// The rules are the measured ones (scripts/pmc_traffic_calib.sh + scripts/tile_order_probe.py, profiles/r02): launch TIME does
-// not depend on the order (+-2 %: the over-fetched bytes come out of the Infinity Cache), fabric traffic does --
-//   * many column tiles over a weight matrix that cannot stay in one XCD's L2 (GEGLU projections at the 32x32 / 16x16 levels:
-//     40 / 80 column tiles, 6.5 / 26 MB of weights): groups of 8 row tiles walked column by column, FETCH 11-12 x -> 5 x the
-//     algorithmic bytes;
-//   * single-pass 3x3 convs with few column tiles and big weights (32x32 level: 128 x 4 tiles, 7-22 MB): a 4 x 2 grid of XCDs
-//     (each XCD streams half of the weights instead of all of them), 3.0 / 4.2 x -> 2.5 / 3.1 x; not at the 64x64 level, where
-//     splitting the column tiles over XCDs doubles the (20 x larger) pixel traffic.
-static void gemm_pick_tile_order(GemmArgs& a, int split, int bm, int bn) {
-  static const int env_xm = [] { const char* e = getenv("DFH_TMAP"); return e ? atoi(e) : -1; }();
-  static const int env_gm = [] { const char* e = getenv("DFH_TMAP"); const char* c = e ? strchr(e, ',') : nullptr; return c ? atoi(c + 1) : 0; }();
-  a.tm_xm = 0; a.tm_gm = 0;
-  if (env_xm >= 0) {            // probe knob; xm must divide the 8 XCDs (anything else would enumerate some tiles twice and others never)
-    a.tm_xm = (env_xm == 1 || env_xm == 2 || env_xm == 4 || env_xm == 8) ? env_xm : 0; a.tm_gm = env_gm; return;
-  }
-  if (split > 1 || a.n_major) return;
-  double kk = (double)a.ntaps * a.conv_c;
-  for (int i = 0; i < a.nplain; ++i) kk += a.p_c[i];
-  const double w_bytes = (double)a.N * kk * 2.0;
-  const double a_bytes = a.ntaps ? (double)(a.M / (a.Hout * a.Wout)) * a.Hin * a.Win * a.conv_c * 2.0 : (double)a.M * kk * 2.0;
-  const int ntm = (a.M + bm - 1) / bm, ntn = (a.N + bn - 1) / bn;
-  if (w_bytes <= 2.0e6 || ntm < 16) return;          // the weights stay resident in every L2: nothing to order
-  if (ntn >= 16) { a.tm_gm = 8; return; }
-  if (!a.ntaps) return;
-  // few column tiles: an xm x (8 / xm) grid of XCDs fetches (8 / xm) x the pixels + xm x the weights in total (xm = 8 is the
-  // legacy order: every XCD streams all the weights).  Measured 4 x 2 against 8 x 1: better on the 32x32-level convs (21 + 8 x 7
-  // MB -> 2 x 21 + 4 x 7), WORSE at 64x64 where the pixels outweigh the weights 20 : 1 -- so pick the minimum of the model.
-  int best = 8; double cost = a_bytes + 8.0 * w_bytes;
-  for (int xm = 4; xm >= 2; xm >>= 1) {
-    if (ntm % xm || ntn % (8 / xm)) continue;
-    const double c = (8.0 / xm) * a_bytes + xm * w_bytes;
-    if (c < 0.95 * cost) { cost = c; best = xm; }
-  }
-  if (best != 8) { a.tm_xm = best; a.tm_gm = 8; }
-}
-
-// Launches for the 256 x 320 tile: one workgroup per CU, so the grid has to come out at whole rounds of the 256 CUs (a 257th tile
-// would run alone for a whole round).  DFH_GEMM_BIG=0 turns it off, =2 also sends the plain linears there (A/B).
-int gemm_big_pick(const GemmArgs& a) {
-  static const int mode = [] { const char* e = getenv("DFH_GEMM_BIG"); return e ? atoi(e) : 2; }();   // 0 off, 1 convs, 2 + deep linears, 3 + all linears (A/B)
-  if (mode == 0) return 0;
-  if (a.out_mode != OUT_BF16 || a.act == ACT_GEGLU || a.ln_stat) return 0;
-  if (a.N % 320 != 0 || (a.ld_out & 7) || (a.resid && (a.ld_res & 7))) return 0;
-  const int ksteps = gemm_count_ksteps(a);
-  if (ksteps < 16 && (a.ntaps || mode < 3)) return 0;   // conv_in (K = 72): prologue + four-pass epilogue outweigh two k-steps (34.6 vs 24.3 us)
-  if (a.ntaps == 0 && mode < 2) return 0;
-  const long tiles = (long)((a.M + 255) / 256) * (a.N / 320), rem = tiles % 256;
-  return (tiles >= 224 && (rem == 0 || rem >= 224 || tiles >= 1024)) ? 1 : 0;
-}
-
-// GEGLU projections for the 256 x 256 tile: whole rounds of the CUs, as above.  DFH_GEMM_BIGG=0 turns it off (A/B).
-int gemm_big_geglu_pick(const GemmArgs& a) {
-  static const int mode = [] { const char* e = getenv("DFH_GEMM_BIGG"); return e ? atoi(e) : 1; }();
-  if (mode == 0 || a.act != ACT_GEGLU || a.out_mode != OUT_BF16 || a.resid || a.rowvec) return 0;
-  if (a.N % 256 != 0 || (a.ld_out & 7)) return 0;
-  // (16x16 level: 640 tiles = 2.5 rounds, still 5 % ahead of the 256 x 128 tile in isolation: profiles/r03/geglu_tile_probe.txt)
-  const long tiles = (long)((a.M + 255) / 256) * (a.N / 256), rem = tiles % 256;
-  return (tiles >= 224 && (rem == 0 || rem >= 224 || tiles >= 512)) ? 1 : 0;
-}
-
-bool wino_blocked(int N, int C) {
-  static const bool off = [] { const char* e = getenv("DFH_W_BLOCKED"); return e && e[0] == '0'; }();      // A/B
-  return !off && N % 160 == 0 && C % 64 == 0;          // the batched launch then runs on a LEAN instantiation (128 x 160 eight-wave / 256 x 320)
-}
-
-int wino_gemm_tile(const GemmArgs& a) {
-  static const int pin = [] { const char* e = getenv("DFH_WINO_TILE"); return e ? atoi(e) : -1; }();      // probe
-  if (pin >= 0) return pin;
-  return 0;
-}
-
-// Batched launches (Winograd planes, phase planes of an upsample conv) for the 256 x 320 eight-wave tile: planes of at least 512 rows whose
-// tiles together make whole rounds of the CUs (16x16-level Winograd: 16 planes x 16 tiles = 256 workgroups, 78.7 us on the 128 x 160 tile -> 67.1 us).
-// DFH_BATCH_BIG=0 turns it off (A/B).
-static bool batched_big_pick(const GemmArgs& a) {
-  static const bool off = [] { const char* e = getenv("DFH_BATCH_BIG"); return e && e[0] == '0'; }();
-  if (off || a.nbatch <= 1 || a.M < 512 || a.N % 320 != 0) return false;
-  const long tiles = (long)((a.M + 255) / 256) * (a.N / 320) * a.nbatch, rem = tiles % 256;
-  return tiles >= 224 && (rem == 0 || rem >= 224 || tiles >= 1024);
-}
-
-bool gemm_out2_ok(GemmArgs a) {
-  if (a.rows_per_b <= 0) a.rows_per_b = a.M;
-  a.ksteps = gemm_count_ksteps(a);
-  int tile;
-  if (gemm_pick_split(a, &tile) != 1) return false;
-  return a.out2 != nullptr && a.n_split > 0 && a.n_split < a.N && a.n_split % kTiles[tile].bn == 0 && a.act != ACT_GEGLU &&
-         a.out_mode == OUT_BF16 && !a.resid;
-}
-
-bool gemm_ln_consumer_ok(GemmArgs a) {
-  if (a.rows_per_b <= 0) a.rows_per_b = a.M;
-  a.ksteps = gemm_count_ksteps(a);
-  int tile;
-  if (gemm_pick_split(a, &tile) != 1) return false;                     // the split-K reduce does not implement the fix-up
-  if (a.act == ACT_GEGLU && ((a.ld_out & 7) || a.N % 32)) return false;  // ... nor does the unstaged GEGLU branch
-  return a.ntaps == 0 && a.resid == nullptr && a.rowvec == nullptr;
-}
-
 int gemm_launch(GemmArgs a, hipStream_t stream, int force_tile, int force_split, int force_order, int* gstat_rows, int* rowstat_bn) {
   if (gstat_rows) *gstat_rows = 0;
   if (rowstat_bn) *rowstat_bn = 0;
-  DFH_REQUIRE(a.M > 0 && a.N > 0, "empty GEMM");
-  DFH_REQUIRE(a.N % 4 == 0, "N must be a multiple of 4");
-  DFH_REQUIRE(a.ntaps == 0 || a.ntaps == 9 || (a.ntaps == 4 && a.phase2x), "ntaps must be 0 or 9 (4 for the phase planes of an upsample conv)");
-  DFH_REQUIRE(a.ntaps + a.nplain >= 1, "no K segment");
-  DFH_REQUIRE(a.ntaps == 0 || a.conv_c % 8 == 0, "conv channels must be a multiple of 8");
-  for (int i = 0; i < a.nplain; ++i) DFH_REQUIRE(a.p_c[i] % 8 == 0, "segment length must be a multiple of 8");
-  DFH_REQUIRE(a.zero != nullptr, "zero page missing");
-  if (a.rows_per_b <= 0) a.rows_per_b = a.M;
+  FILE* const dump = plan_dump_file();
+  GemmArgs given;
+  if (dump) given = a;
+  GemmPlan p;
+  const int refused = gemm_plan(a, gemm_force_decode(force_tile, force_split, force_order), GemmKnobs::from_env(), p);
+  if (dump) {
+    char line[512];
+    gemm_plan_format(line, sizeof(line), given, refused ? nullptr : &p, refused ? last_error() : nullptr);
+    fprintf(dump, "%s\n", line); fflush(dump);
+  }
+  if (refused) return refused;
+  if (gstat_rows) *gstat_rows = p.gstat_rows;
+  if (rowstat_bn) *rowstat_bn = p.rowstat_bn;
 #ifdef DFH_PROBES
-  if (force_tile == 30) {           // probe kernel: the launch as a register-resident token linear (scripts/probes/kernels/token_linear.hip)
-    if (rowstat_bn && a.rowstat) *rowstat_bn = a.N;
-    return token_linear_from_gemm(a, stream);
-  }
+  if (p.kernel > GK_WIDE) return gemm_launch_probes(p, a, stream);      // scripts/probes/kernels/gemm_plan_probes.hip
 #endif
-  a.ksteps = gemm_count_ksteps(a);
-  int tile;
-  int split = gemm_pick_split(a, &tile);
-  // microbench / tests: tile id 6 = the 256 x 160 wide kernel, 7 = its 128 x 160 sibling
-  const bool force_deep = force_tile == 10;
-  if (force_deep) { tile = kEightWave; force_tile = 0; }
-  int force_wide = force_tile > kNumTiles ? force_tile - kNumTiles : 0;
-  if (force_wide) force_tile = 0;
-  if (force_tile > 0) { DFH_REQUIRE(force_tile <= kNumTiles, "unknown tile variant"); tile = force_tile - 1; }
-  if (force_split > 0) split = force_split;
-  if (a.act == ACT_GEGLU) {
-    DFH_REQUIRE(a.N % 32 == 0 && kTiles[tile].bn != 160 && split == 1,
-                "GEGLU needs N % 32 == 0, a 64/128-wide tile and no split-K");
-    DFH_REQUIRE(a.out_mode == OUT_BF16 && !a.resid && !a.rowvec, "GEGLU epilogue is bias-only, bf16 out");
-  }
-  split = std::min(split, a.ksteps);
-  a.ksplit = split;
-  {
-    double kk = (double)a.ntaps * a.conv_c;
-    for (int i = 0; i < a.nplain; ++i) kk += a.p_c[i];
-    const double w_bytes = (double)a.N * kk, a_bytes = (double)a.M * (a.ntaps ? (double)a.conv_c : kk);
-    // measured (scripts/gemm_nmajor_probe.py): +12 % / +6 % on the 16x16-level 3x3 convs, -4 % on the linear shapes -> convs only
-    // batched planes (Winograd): each plane is its own weight-heavy GEMM -- same rule (DFH_BATCH_NMAJOR=0: m-major, A/B)
-    static const bool bn_off = [] { const char* e = getenv("DFH_BATCH_NMAJOR"); return e && e[0] == '0'; }();
-    const bool conv_like = a.ntaps || (a.nbatch > 1 && !bn_off);
-    a.n_major = (force_order == 2 || (force_order < 0 && conv_like && w_bytes > a_bytes && a.N > 160)) ? 1 : 0;   // force_order 2 / 3 pin it (probe)
-    if (force_order == 3) a.n_major = 0;
-  }
-  if (a.nbatch > 1) {
-    // the split heuristic sees one plane's tiles: a batched launch has nbatch times as many, and its planes are independent problems
-    split = 1;
-    DFH_REQUIRE(((a.ntaps == 0 && a.nplain == 1) || (a.phase2x && a.nplain == 0)) && a.out_mode == OUT_BF16 && a.act != ACT_GEGLU &&
-                !a.resid && !a.rowvec && !a.out2 && !a.rowstat && !a.ln_stat && (a.N & 7) == 0 && (a.ld_out & 7) == 0 && force_split <= 1,
-                "batched launch: one plain segment (or the four phase planes of an upsample conv), plain bf16 row-major output, no split-K");
-    a.gstat = nullptr; a.ksplit = 1;
-    // one plane alone would pick the 256-row tile at the 8x8 level (M <= 1024): the planes together fill the chip with the 128-row tiles
-    if (force_tile == 0 && !force_deep) tile = (a.N % 160 == 0) ? kEightWave : 4;
-  }
-  DFH_REQUIRE(!a.phase2x || (a.nbatch == 4 && a.ntaps == 4 && a.stride == 1 && a.ups == 0 && !a.pad0 && a.Hin == a.Hout && a.Win == a.Wout &&
-                             a.M % (a.Hout * a.Wout) == 0), "phase planes of an upsample conv: four planes over the source image");
-  if (split > 1) DFH_REQUIRE(a.partial != nullptr, "split-K needs a partial buffer");
-  if (a.ln_stat) {
-    DFH_REQUIRE(split == 1 && a.ln_parts > 0 && a.ln_cnt > 0 && a.ln_s != nullptr && !a.rowvec && !a.resid,
-                "folded LayerNorm: single-pass launches without rowvec / residual only (gemm_ln_consumer_ok)");
-    DFH_REQUIRE(a.act != ACT_GEGLU || (a.ld_out & 7) == 0, "folded LayerNorm + GEGLU needs 16-byte aligned output rows");
-  }
-  if (a.w_img_bs) {
-    split = 1; a.ksplit = 1;
-    DFH_REQUIRE(a.ntaps == 0 && a.nbatch <= 1 && !a.w_blocked && a.rows_per_b % kTiles[tile].bm == 0 && a.M % a.rows_per_b == 0,
-                "per-image weights: plain segments, images of whole row tiles");
-  }
-  if (a.w_blocked) DFH_REQUIRE(lean_plain(a) && a.N % 16 == 0 && a.ldw % 64 == 0 && a.N % 160 == 0 && force_tile == 0 && split == 1,
-                               "blocked W: LEAN launches (plain 64-multiple segments) on the 128 x 160 / 256 x 320 tiles only");
-  if (a.out2) DFH_REQUIRE(split == 1 && a.n_split > 0 && a.n_split % kTiles[tile].bn == 0 && a.out_mode == OUT_BF16 && a.act != ACT_GEGLU &&
-                          !a.resid && force_tile == 0, "second destination: single pass, n_split a multiple of the column tile (gemm_out2_ok)");
-  if (a.resid) DFH_REQUIRE((double)a.M * a.ld_res * 2.0 < 4.0e9, "residual tensor must be smaller than 4 GB (32-bit lane offsets)");
   int rc;
   {
-    // algorithmic work of this launch: 2*M*N*K over the REAL K (padding excluded); bytes = each operand once + output
-    double kreal = (double)a.ntaps * a.conv_c;
-    double abytes = a.ntaps ? (double)(a.M / (a.Hout * a.Wout)) * a.Hin * a.Win * a.conv_c * 2.0 : 0.0;
-    for (int i = 0; i < a.nplain; ++i) { kreal += a.p_c[i]; abytes += (double)a.M * a.p_c[i] * 2.0; }
-    const double obytes = (double)a.M * (a.act == ACT_GEGLU ? a.N / 2 : a.N) * ((a.out_mode == OUT_F32 || a.out_mode == OUT_F32_T) ? 4.0 : 2.0) +
-                          (a.resid ? (double)a.M * a.N * 2.0 : 0.0) +     // the residual is an operand too: read once
-                          (a.pre_out ? (double)a.M * a.N * 2.0 : 0.0);
-    const double planes = a.nbatch > 1 ? (double)a.nbatch : 1.0;       // a phase launch reads its source image once for all four planes
-    // algorithmic multiply-adds = the reference algorithm's: the four phase planes of an upsample conv stand for the
-    // 3x3 conv over the upsampled image (9 taps per output pixel, of which the planes execute 4)
-    const double flops = a.prof_flops > 0.0 ? a.prof_flops : (a.phase2x ? 9.0 / 4.0 : 1.0) * planes * 2.0 * a.M * a.N * kreal;
-    prof_note_saved(flops - planes * 2.0 * a.M * a.N * kreal);
-    ProfScope ps((a.ntaps || a.prof_flops > 0.0) ? PC_CONV3 : PC_LINEAR, flops,
-                 (a.phase2x == 1 ? abytes : planes * abytes) + planes * ((double)a.N * kreal * 2.0 + obytes), stream);
-    const bool wide_ok0 = split == 1 && a.out2 == nullptr && a.out_mode == OUT_BF16 && (a.act != ACT_GEGLU || a.N % 160 == 0 || a.N % 128 == 0) && (a.N & 7) == 0 &&
-                         (a.ld_out & 7) == 0 && (!a.resid || (a.ld_res & 7) == 0);
-    const bool wide_ok = wide_ok0 && a.nbatch <= 1 && !a.w_img_bs;       // batched launches / per-image weights: gemm_bf16_kernel tiles only (the 256 x 320 one when pinned)
-    // tile id 21 pins the 256 x 320 tile (launches it cannot take -- fp32 / transposed outputs, GEGLU, N % 8 -- fall back to the
-    // heuristic tile, like the forced wide ids); otherwise gemm_big_pick decides
-    const bool force_big = force_wide == 16 ||     // id 21
-                           (a.nbatch > 1 && force_tile == 0 && force_wide == 0 && !force_deep && batched_big_pick(a));
-    if (force_big) force_wide = 0;
-    // tile id 23: the 256 x 256 GEGLU tile
-    const bool force_bigg = force_wide == 18;
-    if (force_bigg) force_wide = 0;
-    // tile id 24: the persistent 128 x 160 kernel (gemm_persist.hip) for every launch it can take; otherwise persist_pick decides
-    const bool force_persist = force_wide == 19;
-    if (force_persist) { force_wide = 0; tile = kEightWave; }
-    const bool pre = a.pre_out != nullptr;      // training GEGLU with its pre-activations as a second output: the 256 x 128 wide tile only
-    if (pre) DFH_REQUIRE(wide_ok && a.act == ACT_GEGLU && a.N % 128 == 0 && !a.ln_stat && !a.resid && !a.rowvec && (a.ld_pre & 7) == 0 && a.ld_pre >= a.N,
-                         "pre_out: GEGLU launches with N % 128 == 0, no split-K, no folded LayerNorm");
-    const bool bigg = !pre && wide_ok && !force_deep && !force_persist && a.act == ACT_GEGLU && a.N % 32 == 0 && !a.resid && !a.rowvec &&
-                      (force_bigg || (!force_wide && force_tile == 0 && force_split == 0 && gemm_big_geglu_pick(a)));
-    const bool big_ok = wide_ok0 && !force_deep && a.act != ACT_GEGLU && !a.ln_stat && (a.nbatch <= 1 || force_big) && !a.w_img_bs;
-    const bool big = big_ok && !force_persist && (force_big || (!force_wide && force_tile == 0 && force_split == 0 && gemm_big_pick(a)));
-    int wide = pre ? 5 : (!wide_ok || force_deep || big || force_big || bigg || force_bigg || force_persist) ? 0 : (force_wide ? force_wide : ((force_tile == 0 && force_split == 0) ? gemm_wide_pick(a) : 0));
-    int ws = 0; bool halo = false;
-#ifdef DFH_PROBES
-    // Probe builds only (scripts/probes/Makefile): tile ids 11 / 12 = the wave-specialised kernel (scripts/probes/kernels/gemm_ws.hip, opt-in
-    // DFH_GEMM_WS=1), tile id 20 = the halo-patch conv kernel (scripts/probes/kernels/gemm_halo.hip, DFH_GEMM_HALO=1).  Both lost their A/B
-    // (profiles/r02/gemm_ws_probe.txt; conv3x3 class 6.96 -> 6.93 ms) and are kept as measurements, not as product code.
-    static const bool ws_off = [] { const char* e = getenv("DFH_GEMM_WS"); return !(e && e[0] == '1'); }();
-    if (wide_ok && !force_deep) {
-      if (force_wide == 6 || force_wide == 7) ws = gemm_ws_pick(a, 1) ? (force_wide == 6 ? 160 : 128) : 0;
-      else if (!force_wide && force_tile == 0 && force_split == 0 && !ws_off) ws = gemm_ws_pick(a, 224);
-    }
-    static const bool halo_on = [] { const char* e = getenv("DFH_GEMM_HALO"); return e && e[0] == '1'; }();
-    halo = wide_ok && !force_deep && gemm_halo_eligible(a) && (force_wide == 15 || (wide == 1 && !force_wide && halo_on));
-#else
-    DFH_REQUIRE(force_wide != 6 && force_wide != 7 && force_wide != 15 && !(force_wide >= 8 && force_wide <= 14),
-                "tile ids 11-20 are probe kernels: build scripts/probes (make -C scripts/probes) and load it with DFH_LIB");
-#endif
-    if (bigg) gemm_pick_tile_order(a, split, 256, 256);
-    else if (big) gemm_pick_tile_order(a, split, 256, 320);
-    else if (ws) gemm_pick_tile_order(a, split, 256, ws);
-    else if (wide) gemm_pick_tile_order(a, split, wide == 2 ? 128 : 256, wide == 3 ? 320 : ((wide == 4 || wide == 5) ? 128 : 160));
-    else gemm_pick_tile_order(a, split, kTiles[tile].bm, kTiles[tile].bn);
-    if (force_wide == 6 || force_wide == 7) wide = 0;                      // not eligible (odd N, transposed / fp32 output): the default tile runs
-    if (force_wide == 15) wide = halo ? 1 : 0;
-    // output statistics for the consuming GroupNorm: the 256-row epilogues (256 x 160 wide, 256 x 320) and, since round 5, the staged
-    // epilogue of the eight-wave 128 x 160 tile write them, on full tiles inside one image; *gstat_rows = pixel rows per statistics chunk
-    const int gbn = big ? 320 : 160;
-    const bool gst256 = (halo || big || (wide == 1 && !ws)) && a.M % 256 == 0 && a.gstat_hw % 256 == 0 && a.gstat_hw / 256 <= (int)GN_MAX_CHUNKS;
-    static const bool gst128_off = [] { const char* e = getenv("DFH_GSTAT128"); return e && e[0] == '0'; }();      // A/B
-    const bool gst128 = !gst128_off && !halo && !big && !bigg && !wide && !ws && tile == kEightWave && split == 1 && a.out_mode == OUT_BF16 && (a.N & 7) == 0 &&
-                        (a.ld_out & 7) == 0 && a.M % 128 == 0 && a.gstat_hw % 128 == 0 && a.nbatch <= 1 && !a.phase2x &&
-                        a.gstat_hw / 128 <= (int)GN_MAX_CHUNKS &&
-                        a.out2 == nullptr;           // the transposed / out2 column tiles return before the statistics block
-    const bool gst_ok = a.gstat && (gst256 || gst128) && a.gstat_cpg > 0 && gbn % a.gstat_cpg == 0 && a.N % gbn == 0 &&
-                        a.N % a.gstat_cpg == 0 && a.act != ACT_GEGLU;
-    if (!gst_ok) a.gstat = nullptr;
-    else if (gstat_rows) *gstat_rows = gst256 ? 256 : 128;
-    // per-row output statistics for a LayerNorm folded into the consumer: the staged bf16 epilogue of gemm_bf16_kernel and the 256-row
-    // epilogue write them, on whole column tiles
-    {
-      const int bn = big ? 320 : (wide == 1 ? 160 : ((wide == 4 || wide == 5) ? 128 : (wide || ws ? 0 : kTiles[tile].bn)));
-      const bool staged_ok = split == 1 && a.out_mode == OUT_BF16 && a.act != ACT_GEGLU && (a.N & 7) == 0 && (a.ld_out & 7) == 0;
-      if (!(a.rowstat && bn > 0 && staged_ok && a.N % bn == 0 && !halo)) a.rowstat = nullptr;
-      else if (rowstat_bn) *rowstat_bn = bn;
-    }
-    bool persist = false;
-#ifdef DFH_PROBES
-    // Probe builds only: the persistent 128 x 160 kernel (scripts/probes/kernels/gemm_persist.hip; tile id 24, or DFH_PERSIST=1 / 2 for every
-    // eligible launch with >= 512 / >= 1 tiles).  Bit-identical to the tile kernel and 1.2-1.5 x slower: profiles/r06/persistent_lean_gemm.md.
-    static const int persist_mode = [] { const char* e = getenv("DFH_PERSIST"); return e ? atoi(e) : 0; }();
-    persist = !bigg && !big && !wide && !halo && !ws && tile == kEightWave && !force_deep && (force_tile == 0 || force_persist) &&
-              gemm_persist_ok(a) && (force_persist || (persist_mode != 0 && (long)(a.M / 128) * (a.N / 160) >= (persist_mode >= 2 ? 1 : 512)));
-    if (force_persist) DFH_REQUIRE(persist, "tile id 24: this launch cannot run on the persistent kernel (gemm_persist_ok)");
-#else
-    DFH_REQUIRE(!force_persist, "tile id 24 is a probe kernel: build scripts/probes (make -C scripts/probes) and load it with DFH_LIB");
-#endif
-#ifdef DFH_PROBES
-    if (halo) rc = gemm_halo_launch(a, stream);
-    else if (ws) rc = gemm_ws_launch(a, stream, ws);
-    else
-    if (bigg && force_tile == 0 && !force_bigg && gemm_geglu_rows_ok(a)) rc = gemm_geglu_rows_launch(a, stream);   // opt-in DFH_GEGLU_ROWS=1
-    else
-#endif
-    if (bigg) rc = launch_big_geglu(a, stream);
-    else if (big) rc = launch_big(a, stream);
-    else if (wide) rc = gemm_wide_launch(a, stream, wide);
-#ifdef DFH_PROBES
-    else if (persist) rc = gemm_persist_launch(a, stream);
-#endif
-    else rc = launch_variant(tile, a, stream);
-    if (persist) census(CK_GEMM_PERSIST);
-    census((big || bigg) ? CK_GEMM_ROW : wide ? CK_GEMM_WIDE : ((halo || ws) ? CK_GEMM_OTHER : (tile == kEightWave ? (lean_plain(a) ? CK_GEMM_LEAN : CK_GEMM_8WAVE) : CK_GEMM_OTHER)));
+    const GemmWork w = gemm_work(a);
+    prof_note_saved(w.saved);
+    ProfScope ps(w.cls, w.flops, w.bytes, stream);
+    rc = p.kernel == GK_WIDE ? gemm_wide_launch(a, stream, p.wide) : launch_planned(p, a, stream);
+    census(p.census);
     if (a.gstat) census(CK_GSTAT_WRITTEN);
     if (a.phase2x) census(CK_CONV_PHASE);
   }
   if (rc) return rc;
-  if (split > 1) {
+  if (p.split > 1) {
     const long total4 = ((long)a.M * a.N) / 4;
-    ProfScope ps(PC_SPLITK, 0.0, (double)split * a.M * a.N * 4.0 + (double)a.M * a.N * 2.0, stream);
+    ProfScope ps(PC_SPLITK, 0.0, (double)p.split * a.M * a.N * 4.0 + (double)a.M * a.N * 2.0, stream);
     census(CK_SPLITK);
     hipLaunchKernelGGL(gemm_splitk_reduce, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, stream, a);
     return check_launch("gemm_splitk_reduce");

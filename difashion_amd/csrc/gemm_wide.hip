@@ -354,48 +354,7 @@ __global__ __launch_bounds__(WN * 128, WN == 2 ? 2 : 1) void gemm_wide_kernel(co
 
 namespace dfh {
 
-int gemm_wide_ksteps(const GemmArgs& a) {
-  int n = a.ntaps * ((a.conv_c + BKW - 1) / BKW);
-  for (int i = 0; i < a.nplain; ++i) n += (a.p_c[i] + BKW - 1) / BKW;
-  return n;
-}
-
-// bf16 row-major output, no GEGLU / split-K, 16-byte aligned rows, and enough tiles to give every CU its two workgroups
-// 1 = 256 x 160, 4 = 256 x 128 (N a multiple of 128 but not of 160), 0 = not eligible; 2 / 3 are experiment variants
-int gemm_wide_pick(const GemmArgs& a) {
-  if (a.out_mode != OUT_BF16) return 0;
-  if (a.ln_stat && !(a.act == ACT_GEGLU && a.N % 128 == 0)) return 0;   // only the in-register GEGLU epilogue implements the LayerNorm fix-up
-  if (a.act == ACT_GEGLU && (a.resid || a.rowvec)) return 0;
-  if ((a.N & 7) || (a.ld_out & 7) || (a.resid && (a.ld_res & 7))) return 0;
-  // GEGLU: the 256 x 128 sibling keeps whole (value, gate) block pairs inside a wave -> epilogue in registers
-  if (a.act == ACT_GEGLU && a.N % 128 == 0) return (long)((a.M + 255) / 256) * (a.N / 128) >= 448 ? 4 : 0;
-  if (a.act == ACT_GEGLU && a.N % 160 != 0) return 0;
-  if (a.N % 160 != 0 && a.N % 128 == 0) {       // 128 / 256 / 512 / 1024 output channels (the VAE): the 256 x 128 sibling
-    return (long)((a.M + 255) / 256) * (a.N / 128) >= 448 ? 4 : 0;
-  }
-  if (a.N % 160 != 0 && a.N < 640) return 0;
-  // plain linears / 1x1 convs (no taps): the eight-wave 128 x 160 kernel of gemm.hip is as fast or faster since its epilogue
-  // stopped serialising the bias loads and its residual loads moved behind the prologue (scripts/gemm_shortk2_probe.py,
-  // profiles/r02/gemm_shortk2_probe.txt: 65536 x 960 x 320 72.7 -> 60.2 us, 65536 x 320 x 1280 + residual 75.3 -> 67.7 us,
-  // 16384 x 1920 x 640 63.4 -> 47.6 us); the 3x3 convs keep the wide tile, and so do the K = 320 linears with a residual, whose
-  // coalesced one-pass-ahead residual reads win (same-box A/B: 31.4 vs 33.7 us)
-  // (with row statistics for a folded LayerNorm the eight-wave kernel wins again: the 256-row epilogue pays ~4.5 us per launch for them)
-  if (a.ntaps == 0 && a.N % 160 == 0 && !(a.resid && a.nplain == 1 && a.p_c[0] <= 320 && !a.rowstat)) return 0;
-  const long nt = (a.N + 159) / 160;
-  // the 128-row sibling (variant 2) is kept for experiments only: at equal tile size the 64-deep two-stage kernel of
-  // gemm.hip wins (848 vs 724 TFLOP/s on conv 320->320 @64): the gain of this file is the larger tile
-  return (long)((a.M + 255) / 256) * nt >= 448 ? 1 : 0;
-}
-
-bool gemm_wide_eligible(const GemmArgs& a) {
-  if (a.out_mode != OUT_BF16) return false;
-  if (a.act == ACT_GEGLU && (a.N % 160 != 0 || a.resid || a.rowvec)) return false;
-  if ((a.N & 7) || (a.ld_out & 7) || (a.resid && (a.ld_res & 7))) return false;
-  if (a.N % 160 != 0 && a.N < 640) return false;
-  const long tiles = (long)((a.M + 255) / 256) * ((a.N + 159) / 160);
-  return tiles >= 448;
-}
-
+// (which launches come here: gemm_wide_pick, gemm_plan.hip)
 template <int BM, int BN, int WN, int NSTAGE, int ABL = 0>
 static int wide_launch_t(GemmArgs a, hipStream_t s) {
   constexpr int lds = NSTAGE * (BM + BN) * BKW * 2;

@@ -321,7 +321,11 @@ typedef struct dfh_gemm_desc {
   void* out; int ld_out; int out_mode;          /* 0 bf16 [M][ld] 1 bf16 [b][N][ld] 2 fp32 [M][ld] 3 fp32 [b][N][ld] */
   float* partial; size_t partial_floats;        /* split-K slabs (dfh_gemm_partial_floats) */
   const void* zero_page;                        /* >= 256 zero bytes */
-  int force_tile, force_split, force_order;     /* 0,0,-1 = heuristics; force_order 2 / 3 = tile ids n-major / m-major */
+  int force_tile, force_split, force_order;     /* 0,0,-1 = heuristics; force_order 2 / 3 = tile ids n-major / m-major.  force_tile (GemmForceTile,
+                                                 * gemm.h): 1-5 gemm_bf16_kernel tiles 256x160 / 256x128 / 128x64 / 128x160 / 128x128; 6 the wide
+                                                 * 256x160 kernel, 9 its 256x128 sibling; 10 the eight-wave 128x160 tile; 21 the 256x320 tile; 23 the
+                                                 * 256x256 GEGLU tile; probe library only (refused here): 7 / 8 wide experiment tiles, 11 / 12
+                                                 * wave-specialised, 13-18 k-loop ablations, 20 halo conv, 24 persistent 128x160, 30 token linear */
   float* gstat; int gstat_cpg, gstat_hw;        /* optional: GroupNorm statistics of the output for the consumer (channels per group,
                                                  * pixels per image): [image][group][hw / rows][2] sums / sums of squares, rows = 256
                                                  * or 128 (dfh_gemm_gstat reports which); only through dfh_gemm_gstat (dfh_gemm ignores the three fields) */
@@ -350,6 +354,33 @@ int dfh_gemm_wgrad(const dfh_gemm_desc* d, const void* dY, int ldy, float* dW, i
 size_t dfh_gemm_wgrad_partial_floats(const dfh_gemm_desc* d, int msplit);
 /* the decomposition that call would launch (host code, no GPU needed): output tiles, how many of them run whole, pixel slices of the rest */
 int dfh_gemm_wgrad_plan(const dfh_gemm_desc* d, int msplit, int* tiles, int* whole_tiles, int* slices);
+/* The launch dfh_gemm / dfh_gemm_gstat / dfh_gemm_ln / dfh_gemm_out2 / dfh_gemm_batched would make for d (host code, no GPU needed, nothing is
+ * launched; pointers of d are only tested for presence, W / out / zero_page / partial may be NULL): which kernel, tile, K split, tile order
+ * and statistics chunk.  x (may be NULL) carries what a descriptor cannot say; d->gstat_cpg / gstat_hw > 0 ask for GroupNorm statistics.
+ * Returns 0 and the plan, or the refusal the launch would meet (dfh_last_error); out->line holds either as the text line that
+ * DFH_GEMM_PLAN_DUMP=<file> appends per launch. */
+typedef struct dfh_gemm_plan_extra {
+  int nbatch;        /* > 1: planes of a batched launch (dfh_gemm_batched, the Winograd planes) */
+  int phase2x;       /* 1: the four phase planes of an upsample conv (dfh_conv_up2x); d describes the 3x3 conv over the SOURCE image */
+  int w_blocked;     /* W in 16 x 64 blocks (dfh_wino_blocked) */
+  int n_split;       /* > 0: a second destination from column n_split on (dfh_gemm_out2) */
+  int want_rowstat;  /* row statistics for a folded LayerNorm (dfh_gemm_ln as producer) */
+  int ln_cnt;        /* > 0: a folded-LayerNorm consumer whose producer wrote column tiles of ln_cnt (dfh_gemm_ln as consumer) */
+  int pre_out;       /* the GEGLU pre-activations as a second output (training walk) */
+} dfh_gemm_plan_extra;
+typedef struct dfh_gemm_plan_info {
+  int kernel;        /* 0 gemm_bf16_kernel tile, 1 its 256 x 320 tile, 2 its 256 x 256 GEGLU tile, 3 gemm_wide_kernel, 4.. probe kernels */
+  int tile;          /* gemm_bf16_kernel tile index (force_tile - 1; 5 = the eight-wave 128 x 160 tile) */
+  int bm, bn, stages, lean;
+  int wide;          /* gemm_wide_kernel variant (1 = 256 x 160, 4 = 256 x 128, 5 = 256 x 128 with pre_out) */
+  int split;         /* K slices; > 1: the split-K reduce follows */
+  int n_major, tm_xm, tm_gm;
+  int gstat_rows;    /* pixel rows per statistics chunk (dfh_gemm_gstat's *written), 0 = the kernel cannot write them */
+  int rowstat_bn;    /* dfh_gemm_ln's *rowstat_bn */
+  int census;        /* index of the dfh_census_* counter the launch bumps */
+  char line[512];
+} dfh_gemm_plan_info;
+int dfh_gemm_plan(const dfh_gemm_desc* d, const dfh_gemm_plan_extra* x, dfh_gemm_plan_info* out);
 /* out[g][n] += sum over the rows of group g of Y[m][n] (bias gradient: groups = 1; time-embedding gradient:
  * groups = batch, rows_per_group = H*W). */
 int dfh_colsum(const void* Y, int ldy, int N, int groups, int rows_per_group, float* out, int ld_out, void* stream);

@@ -1195,3 +1195,77 @@ def test_groupnorm_fold_into_projection_matches_torch(B, HW, C, pre):
     plain = gu.gemm(M=B * HW, N=C, W=w, ldw=C, a0=gn.reshape(B * HW, C), a0_c=C, bias=bias)
     torch.cuda.synchronize()
     assert gu.rel_err(out, ref) <= 1.5 * gu.rel_err(plain, ref) + 1e-3, (gu.rel_err(out, ref), gu.rel_err(plain, ref))
+
+
+# ----------------------------------------------------------------------------- the plan is the launch
+_PLAN_CASES = {   # kernel kind -> (shape, kernel, tile / wide variant, bm x bn, K slices): the smallest shapes at which the rules pick each kind
+    "eight_wave_gstat128": (dict(M=256, K=64, N=320, gstat_hw=128), 0, 5, (128, 160), 1),
+    "tile_128x64": (dict(M=128, K=64, N=8), 0, 2, (128, 64), 1),
+    "ring_256x160_splitk": (dict(conv=(1, 16, 512), N=320), 0, 0, (256, 160), 4),
+    "wide_256x160_gstat256": (dict(M=57344, K=64, N=320, resid=True, gstat_hw=4096), 3, 1, (256, 160), 1),
+    "big_256x320": (dict(conv=(14, 64, 128), N=320, gstat_hw=4096), 1, 5, (256, 320), 1),
+    "big_geglu_256x256": (dict(M=57344, K=64, N=256, act=4), 2, 4, (256, 256), 1),
+    "wide_256x128": (dict(M=57344, K=64, N=256), 3, 4, (256, 128), 1),
+    "batched_winograd": (dict(M=256, K=64, N=320, nbatch=16), 0, 5, (128, 160), 1),
+    "deep_ring": (dict(M=4096, K=320, N=320), 0, 5, (128, 160), 1),
+}
+
+
+@pytest.mark.parametrize("kind", list(_PLAN_CASES))
+def test_gemm_plan_is_the_launch_that_runs(kind):
+    """dfh_gemm_plan (host code) against the launch itself, one shape per kernel kind of the product build: the statistics chunk rows /
+    row-statistics column tile the entry point reports are the plan's, the census counter that rises is the plan's (plus splitk_reduce
+    for a split plan), and the output matches the fp32 reference within this file's GEMM tolerance (assert_close_bf16)."""
+    shape, kernel, sub, (bm, bn), split = _PLAN_CASES[kind]
+    N, act, nb = shape["N"], shape.get("act", 0), shape.get("nbatch", 0)
+    bias = rnd(N, seed=3)
+    if "conv" in shape:
+        B, H, Cin = shape["conv"]
+        M = B * H * H
+        x, w = bf(rnd(B, Cin, H, H, seed=1)), bf(rnd(N, Cin, 3, 3, seed=2, scale=0.05))
+        kw = dict(M=M, N=N, W=gu.pack_conv(w.float()), ldw=9 * Cin, conv_src=gu.nhwc(x), conv_c=Cin, batch=B, Hin=H, Win=H, bias=bias)
+        ref = gu.nhwc(F.conv2d(x.float(), w.float(), bias, padding=1)).view(M, N)
+    else:
+        M, K = shape["M"], shape["K"]
+        a, w = bf(rnd(max(nb, 1), M, K, seed=1)), bf(rnd(max(nb, 1), N, K, seed=2, scale=0.05))
+        res = bf(rnd(M, N, seed=4)) if shape.get("resid") else None
+        kw = dict(M=M, N=N, W=w, ldw=K, a0=a, a0_c=K, bias=bias, resid=res, act=act)
+        ref = a.float() @ w.float().transpose(1, 2) + bias + (res.float() if res is not None else 0)
+    out = torch.empty(max(nb, 1), M, N // 2 if act == 4 else N, dtype=torch.bfloat16, device=DEV)
+    d = gu.gemm_desc(out=out, ld_out=out.shape[-1], **kw)
+    hw = shape.get("gstat_hw", 0)
+    gst = torch.zeros(2 * (M // max(hw, 1)) * 32 * max(hw // 128, 1), dtype=torch.float32, device=DEV) if hw else None
+    if hw:
+        d.gstat, d.gstat_cpg, d.gstat_hw = gst.data_ptr(), N // 32, hw
+    x_ = _lib.GemmPlanExtra(nbatch=nb, want_rowstat=0 if (hw or nb) else 1)
+    info = _lib.GemmPlanInfo()
+    _lib.call("dfh_gemm_plan", C.byref(d), C.byref(x_), C.byref(info))
+    print(kind, info.line.decode())
+    assert (info.kernel, info.wide if kernel == 3 else info.tile, info.bm, info.bn, info.split) == (kernel, sub, bm, bn, split)
+    if kind in ("deep_ring", "batched_winograd", "eight_wave_gstat128"):
+        assert info.stages == 4 and info.lean == 1          # at most 320 workgroups: the deep-ring eight-wave instantiation
+    _lib.census_reset()
+    if nb:
+        _lib.call("dfh_gemm_batched", C.byref(d), nb, M * kw["a0_c"], N * kw["a0_c"], M * N, gu.stream())
+        assert info.gstat_rows == 0 and info.rowstat_bn == 0
+    elif hw:
+        written = C.c_int(-1)
+        _lib.call("dfh_gemm_gstat", C.byref(d), gu.stream(), C.byref(written))
+        assert written.value == info.gstat_rows
+    else:
+        st = torch.zeros(2 * M * max(N // 64, 1) + 16, dtype=torch.float32, device=DEV)
+        bn_ = C.c_int(-1)
+        _lib.call("dfh_gemm_ln", C.byref(d), _lib.ptr(st), C.byref(bn_), None, 0, 0, 0.0, None, gu.stream())
+        assert bn_.value == info.rowstat_bn
+    torch.cuda.synchronize()
+    census = {k: v for k, v in _lib.census().items() if v}
+    want = {_lib.raw().dfh_census_name(info.census).decode(): 1}
+    if info.split > 1:
+        want["splitk_reduce"] = 1
+    if info.gstat_rows:
+        want["gstat_written"] = 1
+    assert census == want
+    if act == 4:      # packed GEGLU rows: 16-column blocks of values and gates alternate (dfh_pack_matrix's interleave)
+        v, g = ref[0].view(M, N // 32, 2, 16).unbind(2)
+        ref = (v * F.gelu(g)).reshape(1, M, N // 2)
+    gu.assert_close_bf16(out, ref.view(out.shape), kind)
