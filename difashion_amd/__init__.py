@@ -14,13 +14,15 @@ from .schedulers import DDIMScheduler, PNDMScheduler
 from .training import EMAModel, FusedAdamW, clip_grad_norm_, train_step
 from .unet import UNet2DConditionModel, UNet2DConditionOutput
 from .vae import AutoencoderKL
-from .clip import CLIPTextModel
+from .clip import CLIPTextModel, CLIPTextModelOutput, CLIPTextModelWithProjection
 from .clip_vision import CLIPVisionModelOutput, CLIPVisionModelWithProjection
+from .evalscores import CLIPScore, CompatibilityEvaluator, FashionEvaluator, candidate_cosine, pair_cosine
 from .difashion import DiFashion
 
 __all__ = [
     "DfhError", "set_storage", "storage", "UNet2DConditionModel", "UNet2DConditionOutput", "DDIMScheduler", "PNDMScheduler",
     "MutualEncoder", "OutfitSampler", "sample_outfits", "train_forward", "guidance_plan", "sampling_tables", "training_tables",
     "FusedAdamW", "EMAModel", "clip_grad_norm_", "train_step", "AutoencoderKL", "CLIPTextModel", "DiFashion",
-    "CLIPVisionModelWithProjection", "CLIPVisionModelOutput",
+    "CLIPVisionModelWithProjection", "CLIPVisionModelOutput", "CLIPTextModelWithProjection", "CLIPTextModelOutput", "CLIPScore",
+    "CompatibilityEvaluator", "FashionEvaluator", "pair_cosine", "candidate_cosine",
 ]

@@ -153,6 +153,12 @@ SIGNATURES = {
     "dfh_clip_param_dim": (_i, [_vp, _i, _i]),
     "dfh_clip_workspace_bytes": (_sz, [_vp, _i, _i]),
     "dfh_clip_encode": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp, _vp, _i, _vp, _vp, _sz, _i, _i, _vp]),
+    "dfh_clip_text_embeds": (_i, [_vp, C.POINTER(_vp), _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _i, _i, _vp]),
+    "dfh_embed_pair_cosine": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp]),
+    "dfh_embed_candidates": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "dfh_compat_workspace_bytes": (_sz, [_i, _i, _i]),
+    "dfh_compat_score": (_i, [C.POINTER(_vp), _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "dfh_compat_pred_score": (_i, [C.POINTER(_vp), _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "dfh_clipv_create": (_i, [C.POINTER(CLIPVisionConfigC), C.POINTER(_vp)]),
     "dfh_clipv_destroy": (None, [_vp]),
     "dfh_clipv_num_params": (_i, [_vp]),

@@ -58,18 +58,16 @@ class CLIPTextModel(ClipTower):
         return super().load_state_dict(sd, strict=strict, **kw)
 
     # ------------------------------------------------------------------ text_encoder(input_ids)
-    @torch.no_grad()
-    def forward(self, input_ids: Optional[torch.Tensor] = None, attention_mask=None, position_ids=None, output_attentions=None,
-                output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None):
+    def _ids_on_device(self, what: str, input_ids, attention_mask, position_ids, output_attentions):
+        """The checks of ``forward`` that both text classes share -> (device, ids [B, T] int64 on it, B, T)."""
         if input_ids is None:
             raise ValueError("You have to specify input_ids")
         if attention_mask is not None or position_ids is not None or output_attentions:
             raise NotImplementedError("the reference calls text_encoder(input_ids) only (difashion.py:224,340): no padding mask, "
                                       "default positions, no attention maps on this path")
-        dev = self._require_hip_fp32("CLIPTextModel")
+        dev = self._require_hip_fp32(what)
         cfg = self.config
-        shape = tuple(input_ids.shape)
-        T = shape[-1]
+        T = tuple(input_ids.shape)[-1]
         if T > cfg["max_position_embeddings"]:
             raise ValueError(f"Sequence length must be less than max_position_embeddings (got `sequence length`: {T} and "
                              f"max_position_embeddings: {cfg['max_position_embeddings']}")
@@ -77,9 +75,15 @@ class CLIPTextModel(ClipTower):
         # ids that already sit on the GPU cost one sync, and the encoder runs once per run (PromptTable.build)
         lo, hi = int(input_ids.min()), int(input_ids.max())
         ids = input_ids.reshape(-1, T).to(device=dev, dtype=torch.int64).contiguous()
-        B = ids.shape[0]
         if lo < 0 or hi >= cfg["vocab_size"]:
             raise IndexError(f"input_ids out of range [0, {cfg['vocab_size']}): min {lo}, max {hi}")
+        return dev, ids, ids.shape[0], T
+
+    @torch.no_grad()
+    def forward(self, input_ids: Optional[torch.Tensor] = None, attention_mask=None, position_ids=None, output_attentions=None,
+                output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None):
+        dev, ids, B, T = self._ids_on_device("CLIPTextModel", input_ids, attention_mask, position_ids, output_attentions)
+        cfg = self.config
         arr, count = self._prepare(dev, B, T)
         D, L = cfg["hidden_size"], cfg["num_hidden_layers"]
         last = torch.empty((B, T, D), dtype=torch.float32, device=dev)
@@ -89,3 +93,69 @@ class CLIPTextModel(ClipTower):
                   _lib.ptr(hs), _lib.ptr(self._ws), self._ws.numel(), B, T, _lib.stream_ptr())
         out = BaseModelOutputWithPooling(last, pooled, tuple(hs[i] for i in range(L + 1)) if hs is not None else None)
         return out if return_dict is None or return_dict else out.to_tuple()
+
+
+class CLIPTextModelOutput(TupleOutput):
+    """transformers' output object: ``.text_embeds`` / ``[0]``, ``.last_hidden_state`` / ``[1]``, ``.hidden_states``; plus
+    ``.pooler_output`` (the final-LayerNorm row at the eos position that ``text_projection`` reads)."""
+    _fields = ("text_embeds", "last_hidden_state", "hidden_states")
+
+    def __init__(self, text_embeds, last_hidden_state, pooler_output, hidden_states=None):
+        self.text_embeds, self.last_hidden_state, self.pooler_output = text_embeds, last_hidden_state, pooler_output
+        self.hidden_states = hidden_states
+
+
+class CLIPTextModelWithProjection(CLIPTextModel):
+    """The text side of the evaluation's OpenCLIP ViT-H/14 (``encode_text``, Evaluation/eval_utils.py:101-114) under
+    the architecture and key names of ``transformers.CLIPTextModelWithProjection``: ``CLIPTextModel``'s tower, parameter table and
+    native object plus ``text_projection.weight`` (``dfh_clip_text_embeds``, csrc/clip.hip: final LayerNorm and projection on the pooled
+    rows only)."""
+    architecture = "CLIPTextModelWithProjection"
+
+    def __init__(self, projection_dim: int = 1024, init_seed: Optional[int] = 0, init_std: float = 0.02, **text_config):
+        super().__init__(init_seed=init_seed, init_std=init_std, **text_config)
+        if projection_dim < 1:
+            raise ValueError(f"projection_dim must be positive, got {projection_dim}")
+        self.register_to_config(projection_dim=projection_dim)
+        # not in the native table (dfh_clip_num_params is CLIPTextModel's): a parameter of its own, handed over as a separate pointer
+        self._build_parameters([("text_projection.weight", (projection_dim, self.config["hidden_size"]))], lambda name: False,
+                               None if init_seed is None else init_seed + 1, init_std, unseeded_zeros=True)
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        """``text_model.*`` + ``text_projection.weight``; the flattened tower keys of newer transformers releases are accepted too."""
+        own = lambda k: k.startswith(("text_model.", "text_projection."))
+        return ClipTower.load_state_dict(self, {k if own(k) else "text_model." + k: v for k, v in state_dict.items()}, strict=strict, **kw)
+
+    @torch.no_grad()
+    def forward(self, input_ids: Optional[torch.Tensor] = None, attention_mask=None, position_ids=None, output_attentions=None,
+                output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None):
+        dev, ids, B, T = self._ids_on_device("CLIPTextModelWithProjection", input_ids, attention_mask, position_ids, output_attentions)
+        cfg = self.config
+        arr, count = self._prepare(dev, B, T)
+        proj = self.text_projection.weight
+        if proj.device != dev or not proj.is_contiguous():
+            raise _lib.DfhError("all parameters must be contiguous and on one device")
+        D, L, Pd = cfg["hidden_size"], cfg["num_hidden_layers"], cfg["projection_dim"]
+        embeds = torch.empty((B, Pd), dtype=torch.float32, device=dev)
+        last = torch.empty((B, T, D), dtype=torch.float32, device=dev)
+        pooled = torch.empty((B, D), dtype=torch.float32, device=dev)
+        hs = torch.empty((L + 1, B, T, D), dtype=torch.float32, device=dev) if output_hidden_states else None
+        _lib.call("dfh_clip_text_embeds", self._ctx, arr, count, _lib.ptr(proj), Pd, _lib.ptr(ids), _lib.ptr(embeds), _lib.ptr(pooled),
+                  _lib.ptr(last), int(cfg["eos_token_id"]), _lib.ptr(hs), _lib.ptr(self._ws), self._ws.numel(), B, T, _lib.stream_ptr())
+        out = CLIPTextModelOutput(embeds, last, pooled, tuple(hs[i] for i in range(L + 1)) if hs is not None else None)
+        return out if return_dict is None or return_dict else out.to_tuple()
+
+    @torch.no_grad()
+    def encode_text(self, input_ids: torch.Tensor) -> torch.Tensor:
+        """``open_clip``'s name for the projected text embedding (what ``CLIPScore.calculate_clip_score`` calls): only the pooled rows
+        go through the final LayerNorm, ``last_hidden_state`` is not formed."""
+        dev, ids, B, T = self._ids_on_device("CLIPTextModelWithProjection", input_ids, None, None, None)
+        arr, count = self._prepare(dev, B, T)
+        proj = self.text_projection.weight
+        if proj.device != dev or not proj.is_contiguous():
+            raise _lib.DfhError("all parameters must be contiguous and on one device")
+        embeds = torch.empty((B, self.config["projection_dim"]), dtype=torch.float32, device=dev)
+        _lib.call("dfh_clip_text_embeds", self._ctx, arr, count, _lib.ptr(proj), self.config["projection_dim"], _lib.ptr(ids),
+                  _lib.ptr(embeds), None, None, int(self.config["eos_token_id"]), None, _lib.ptr(self._ws), self._ws.numel(), B, T,
+                  _lib.stream_ptr())
+        return embeds

@@ -282,31 +282,31 @@ int clip_layernorm(const float* x, long ldx, const float* g, const float* b, flo
 }
 }  // namespace dfh
 
-extern "C" {
+namespace {
 
-int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, const int64_t* input_ids, float* last_hidden_state,
-                    float* pooler_output, int eos_token_id, float* hidden_states, void* workspace, size_t workspace_bytes, int batch,
-                    int seq_len, void* stream) {
-  DFH_REQUIRE(c && master_params && input_ids && last_hidden_state && workspace, "null argument");
+// What the two text entry points share: the checks of an encode call, the embeddings and the pre-LN blocks over w.x (hidden_states taps
+// on the way).  Leaves the last block's output, not yet normalised, in w.x.  who: the entry point, for the messages.
+int clip_text_walk(const char* who, dfh_clip* c, const float* const* master_params, int count, const int64_t* input_ids,
+                   float* hidden_states, void* workspace, size_t workspace_bytes, int batch, int seq_len, hipStream_t s) {
+  auto refuse = [&](const char* msg) { dfh::set_error(std::string(who) + ": " + msg); return -1; };
   if (int rc = dfh::require_params(*c, master_params, count, "dfh_clip")) return rc;
-  DFH_REQUIRE(batch > 0 && seq_len > 0 && seq_len <= c->cfg.max_position_embeddings,
-              "sequence length must be in [1, max_position_embeddings] (CLIPTextEmbeddings raises too)");
-  DFH_REQUIRE(workspace_bytes >= dfh_clip_workspace_bytes(c, batch, seq_len), "workspace smaller than dfh_clip_workspace_bytes");
-  DFH_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
+  if (!(batch > 0 && seq_len > 0 && seq_len <= c->cfg.max_position_embeddings))
+    return refuse("sequence length must be in [1, max_position_embeddings] (CLIPTextEmbeddings raises too)");
+  if (workspace_bytes < dfh_clip_workspace_bytes(c, batch, seq_len)) return refuse("workspace smaller than dfh_clip_workspace_bytes");
+  if (((uintptr_t)workspace & 255) != 0) return refuse("workspace must be 256-byte aligned");
   const int T = seq_len, D = c->cfg.hidden_size, I = c->cfg.intermediate_size, H = c->cfg.num_attention_heads, d = D / H;
   const int M = batch * T;
   const size_t lds = ((size_t)T * (2 * d + 1) + 4 * d + 4 * 128) * sizeof(float);
-  DFH_REQUIRE(lds <= 64 * 1024, "head_dim x sequence length does not fit the attention kernel's LDS tile");
+  if (lds > 64 * 1024) return refuse("head_dim x sequence length does not fit the attention kernel's LDS tile");
   const dfh::ClipWorkspace w = c->workspace(workspace, batch, T);
   const float* const* P = master_params;
   const float eps = c->cfg.layer_norm_eps, scale = 1.0f / sqrtf((float)d);
   hipLaunchKernelGGL(clip_embed_kernel, dim3(M), dim3(256), 0, s, input_ids, P[c->tok], P[c->pos], w.x, T, D, c->cfg.vocab_size);
   if (int rc = dfh::check_launch("clip_embed_kernel")) return rc;
+  const std::string what = std::string(who) + ": hidden_states";
   // hidden_states[l]: slice l of one buffer
   auto tap = [&](int l, const float* src) {
-    return dfh::tower_copy(hidden_states ? hidden_states + l * (size_t)M * D : nullptr, src, (size_t)M * D * sizeof(float), s,
-                           "dfh_clip_encode: hidden_states");
+    return dfh::tower_copy(hidden_states ? hidden_states + l * (size_t)M * D : nullptr, src, (size_t)M * D * sizeof(float), s, what.c_str());
   };
   auto attention = [&](const float* qkv, float* att) {
     hipLaunchKernelGGL(clip_attention_kernel, dim3(H, batch), dim3(256), lds, s, qkv, att, T, D, d, scale);
@@ -314,13 +314,57 @@ int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, c
   };
   if (int rc = tap(0, w.x)) return rc;
   const dfh::ClipAccounting acct = {dfh::PC_OTHER, -1, -1, -1};
-  if (int rc = dfh::clip_blocks(P, c->layers, w, M, D, I, c->cfg.hidden_act, eps, acct, s, attention, tap)) return rc;
-  if (int rc = dfh::clip_layernorm(w.x, D, P[c->fw], P[c->fb], last_hidden_state, M, D, eps, s)) return rc;
+  return dfh::clip_blocks(P, c->layers, w, M, D, I, c->cfg.hidden_act, eps, acct, s, attention, tap);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, const int64_t* input_ids, float* last_hidden_state,
+                    float* pooler_output, int eos_token_id, float* hidden_states, void* workspace, size_t workspace_bytes, int batch,
+                    int seq_len, void* stream) {
+  DFH_REQUIRE(c && master_params && input_ids && last_hidden_state && workspace, "null argument");
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = clip_text_walk("dfh_clip_encode", c, master_params, count, input_ids, hidden_states, workspace, workspace_bytes, batch, seq_len, s))
+    return rc;
+  const int T = seq_len, D = c->cfg.hidden_size, M = batch * T;
+  const dfh::ClipWorkspace w = c->workspace(workspace, batch, T);
+  const float* const* P = master_params;
+  if (int rc = dfh::clip_layernorm(w.x, D, P[c->fw], P[c->fb], last_hidden_state, M, D, c->cfg.layer_norm_eps, s)) return rc;
   if (pooler_output) {
     hipLaunchKernelGGL(clip_pool_kernel, dim3(batch), dim3(256), 0, s, input_ids, last_hidden_state, pooler_output, T, D, eos_token_id);
     if (int rc = dfh::check_launch("clip_pool_kernel")) return rc;
   }
   return 0;
+}
+
+// CLIPTextModelWithProjection / open_clip's encode_text: the same walk, then the tail runs on the pooled rows alone.  LayerNorm is
+// row-local (one wave a row, the same kernel), so gather-then-normalise gives the bits normalise-then-gather gives in dfh_clip_encode.
+// The gathered rows and (when pooler_output is not asked for) the normalised rows live in the attention / ln regions of the workspace,
+// both free once the last block is done.
+int dfh_clip_text_embeds(dfh_clip* c, const float* const* master_params, int count, const float* text_projection, int projection_dim,
+                         const int64_t* input_ids, float* text_embeds, float* pooler_output, float* last_hidden_state, int eos_token_id,
+                         float* hidden_states, void* workspace, size_t workspace_bytes, int batch, int seq_len, void* stream) {
+  DFH_REQUIRE(c && master_params && text_projection && input_ids && text_embeds && workspace, "null argument");
+  DFH_REQUIRE(projection_dim > 0, "projection_dim must be positive");
+  DFH_REQUIRE(((uintptr_t)text_projection & 15) == 0, "text_projection must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = clip_text_walk("dfh_clip_text_embeds", c, master_params, count, input_ids, hidden_states, workspace, workspace_bytes, batch,
+                              seq_len, s)) return rc;
+  const int T = seq_len, D = c->cfg.hidden_size, M = batch * T;
+  const dfh::ClipWorkspace w = c->workspace(workspace, batch, T);
+  const float* const* P = master_params;
+  const float eps = c->cfg.layer_norm_eps;
+  if (last_hidden_state)
+    if (int rc = dfh::clip_layernorm(w.x, D, P[c->fw], P[c->fb], last_hidden_state, M, D, eps, s)) return rc;
+  float* rows = w.att;                                       // [batch][D]: the last block's output at the pooled positions
+  float* pooled = pooler_output ? pooler_output : w.ln;
+  hipLaunchKernelGGL(clip_pool_kernel, dim3(batch), dim3(256), 0, s, input_ids, w.x, rows, T, D, eos_token_id);
+  if (int rc = dfh::check_launch("clip_pool_kernel")) return rc;
+  if (int rc = dfh::clip_layernorm(rows, D, P[c->fw], P[c->fb], pooled, batch, D, eps, s)) return rc;
+  return dfh::clip_linear(pooled, D, text_projection, D, nullptr, nullptr, 0, text_embeds, projection_dim, batch, projection_dim,
+                          CLIP_ACT_NONE, dfh::PC_OTHER, s);
 }
 
 }  // extern "C"

@@ -259,6 +259,54 @@ size_t dfh_clip_workspace_bytes(const dfh_clip* c, int batch, int seq_len);
 int dfh_clip_encode(dfh_clip* c, const float* const* master_params, int count, const int64_t* input_ids, float* last_hidden_state,
                     float* pooler_output, int eos_token_id, float* hidden_states, void* workspace, size_t workspace_bytes, int batch,
                     int seq_len, void* stream);
+/* text_embeds = CLIPTextModelWithProjection(input_ids) = open_clip's encode_text (Evaluation/eval_utils.py:101-114):
+ * the walk of dfh_clip_encode over the same dfh_clip object and parameter table, then the pooled row of every sequence (the rule of
+ * pooler_output above, found on the device) is gathered from the last block's output, normalised by final_layer_norm -- those `batch`
+ * rows only -- and projected without bias.
+ *   text_projection   : [projection_dim][hidden_size] fp32, 16-byte aligned: a pointer of its own, not part of the parameter table
+ *   text_embeds       : [batch][projection_dim] fp32
+ *   pooler_output     : NULL, or [batch][hidden_size]: the bits dfh_clip_encode gives (LayerNorm is row-local)
+ *   last_hidden_state : NULL, or [batch][seq_len][hidden_size]: only then does the LayerNorm over all batch * seq_len rows run
+ *   hidden_states, workspace (>= dfh_clip_workspace_bytes): as in dfh_clip_encode */
+int dfh_clip_text_embeds(dfh_clip* c, const float* const* master_params, int count, const float* text_projection, int projection_dim,
+                         const int64_t* input_ids, float* text_embeds, float* pooler_output, float* last_hidden_state, int eos_token_id,
+                         float* hidden_states, void* workspace, size_t workspace_bytes, int batch, int seq_len, void* stream);
+
+/* ------------------------------------------------------------------ embedding-side metrics of the evaluation
+ * csrc/eval_scores.hip; fp32 in both storage builds, no atomics (reruns are bit-identical, a row does not depend on its batch).
+ *
+ * out[r] = scale * <a_r, b_r> / (|a_r| |b_r|): 100 * F.cosine_similarity of Evaluation/eval_utils.py:101-135 (CLIP score, CLIP image
+ * score) and :503-538 (personalisation similarity).  a, b [rows][dim] fp32 dense, out [rows]; no scratch.  A zero row gives NaN in its
+ * own score, as the reference's x / x.norm() does. */
+int dfh_embed_pair_cosine(const float* a, const float* b, float* out, int rows, int dim, float scale, void* stream);
+/* sims[r][k] = cos(gen_r, table[cand[r][k]]), pred[r] = argmax_k sims[r][k] (ties: the lowest k; a NaN counts as the maximum, as
+ * torch.argmax has it): the retrieval accuracy of eval_utils.py:652-723 (K = 5) and the ranking of :725-767 (K in the thousands).
+ * gen [rows][dim], table [table_rows][dim] fp32, cand [rows][K] int64 gathered in the kernel, sims [rows][K] fp32, pred [rows] int64.
+ * Ids outside [0, table_rows) are CLAMPED here; refusing them, as indexing does, is the caller's part (the Python side raises). */
+int dfh_embed_candidates(const float* gen, const float* table, const int64_t* cand, float* sims, int64_t* pred, int rows, int K, int dim,
+                         int table_rows, void* stream);
+
+/* The compatibility scorer: FashionEvaluator (Evaluation/compatibility_evaluator/compatibility_net.py:14-81) under the gather of
+ * CompatibilityEvaluator.evaluate_compatibility (eval_utils.py:574-588), all outfits of a call at once.  Inference: Dropout is the
+ * identity.  Linears on v_mfma_f32_16x16x4_f32, LayerNorm + ReLU fused per row.
+ *   params      : HOST array of DFH_COMPAT_NUM_PARAMS device pointers, fp32, 16-byte aligned, in the class's state-dict order:
+ *                 feat_layer.{weight,bias}, emb_layer.{0,1,4,5,8,9,12,13}.{weight,bias}, eval_layer.{0,1,4,5,8,9,12}.{weight,bias}
+ *   feat_dim    : cnn_feat_dim, a multiple of 4
+ *   feats_real  : [real_rows][feat_dim]; feats_gen: [gen_rows][feat_dim] or NULL (gen_rows = 0)
+ *   olists      : [outfits][items] int64: an id <= 0 reads feats_gen[-id], an id > 0 reads feats_real[id] (ids out of range are
+ *                 CLAMPED here, the Python side refuses them).  NULL: feats_real is the gathered [outfits][items][feat_dim] tensor
+ *   items       : 2 .. 8; all items (items - 1) / 2 pairs in itertools.combinations order
+ *   outfit_emb  : NULL, or [outfits][256];  logits, scores: NULL, or [outfits] (scores = sigmoid(logits))
+ *   workspace   : >= dfh_compat_workspace_bytes(outfits, items, feat_dim), 256-byte aligned */
+#define DFH_COMPAT_NUM_PARAMS 32
+size_t dfh_compat_workspace_bytes(int outfits, int items, int feat_dim);
+int dfh_compat_score(const float* const* params, int count, int feat_dim, const float* feats_real, int real_rows, const float* feats_gen,
+                     int gen_rows, const int64_t* olists, int outfits, int items, float* outfit_emb, float* logits, float* scores,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* FashionEvaluator.pred_score on its own: eval_layer over outfit_emb [outfits][256] -> logits, scores (either may be NULL).
+ * workspace: >= dfh_compat_workspace_bytes(outfits, 2, 4) */
+int dfh_compat_pred_score(const float* const* params, int count, const float* outfit_emb, int outfits, float* logits, float* scores,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ CLIP image encoder: vision tower + projection
  * Replaces (arithmetic) the OpenCLIP ViT-H/14 ``encode_image`` that the reference's Evaluation/ scripts call on every generated and
