@@ -128,6 +128,7 @@ SIGNATURES = {
     "dfh_census_count": (_i, []),
     "dfh_census_name": (C.c_char_p, [_i]),
     "dfh_census_get": (C.c_long, [_i]),
+    "dfh_walk_switches": (_sz, [C.c_char_p, _sz]),
     "dfh_unet_create": (_i, [C.POINTER(UNetConfigC), C.POINTER(_vp)]),
     "dfh_unet_destroy": (None, [_vp]),
     "dfh_unet_num_params": (_i, [_vp]),
@@ -283,7 +284,7 @@ _NO_STATUS = {"dfh_abi_version", "dfh_census_count", "dfh_unet_num_params", "dfh
 
 _lib = None
 _UNBOUND = set()
-ABI_VERSION = 7          # == DFH_ABI_VERSION of include/difashion_hip.h (checked when the library is loaded)
+ABI_VERSION = 8          # == DFH_ABI_VERSION of include/difashion_hip.h (checked when the library is loaded)
 
 
 def storage() -> str:
@@ -442,6 +443,14 @@ def census():
     """-> {kernel family: launches since census_reset()} (host-side counters of the launchers; test infrastructure)."""
     lib = raw()
     return {lib.dfh_census_name(i).decode(): int(lib.dfh_census_get(i)) for i in range(lib.dfh_census_count())}
+
+
+def walk_switches():
+    """-> {DFH_* name: value as text}: the walk and launcher switches as this process's library read them (no GPU needed)."""
+    lib = raw()
+    buf = C.create_string_buffer(lib.dfh_walk_switches(None, 0) + 1)
+    lib.dfh_walk_switches(buf, len(buf))
+    return dict(line.split("=", 1) for line in buf.value.decode().splitlines())
 
 
 def stream_ptr():

@@ -14,6 +14,7 @@
 #include "gemm_plan.h"
 #include "mlp_fused.h"
 #include "norm.h"
+#include "walk_knobs.h"
 #include "wgrad.h"
 #include "bwd_elementwise.h"
 
@@ -120,6 +121,7 @@ void dfh_census_reset(void) { std::memset(dfh::g_census, 0, sizeof(dfh::g_census
 int dfh_census_count(void) { return dfh::CK_COUNT; }
 const char* dfh_census_name(int i) { return (i >= 0 && i < dfh::CK_COUNT) ? dfh::kCensusNames[i] : ""; }
 long dfh_census_get(int i) { return (i >= 0 && i < dfh::CK_COUNT) ? dfh::g_census[i] : -1; }
+size_t dfh_walk_switches(char* buf, size_t cap) { return dfh::walk_switches_text(buf, cap); }
 const char* dfh_last_error(void) { return dfh::last_error(); }
 #define DFH_STR2(x) #x
 #define DFH_STR(x) DFH_STR2(x)

@@ -26,6 +26,7 @@
 //     conflict-free; the N x N score matrix never touches HBM.
 #include "dfh_common.h"
 #include "attention.h"
+#include "walk_knobs.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -309,7 +310,7 @@ int attention_launch(const AttnArgs& a, hipStream_t stream) {
   DFH_REQUIRE(a.ldvt >= ((a.Nk + 7) / 8) * 8, "V^T rows must be padded to a multiple of 8 keys");
   DFH_REQUIRE(a.O8 ? a.o_amax != nullptr : a.O != nullptr, "attention: no output (bf16 O, or e4m3 O8 with the per-batch maxima of V)");
   if (attention_fp8_eligible(a)) return attention_fp8_launch(a, stream);
-  static const bool x32_off = [] { const char* e = getenv("DFH_ATTN_X32"); return e && e[0] == '0'; }();   // A/B switch for the microbenchmarks
+  const bool x32_off = !WalkKnobs::get().attn_x32;   // DFH_ATTN_X32=0: A/B switch for the microbenchmarks
   if (!x32_off && attention_x32_eligible(a)) return attention_x32_launch(a, stream);
   census(CK_ATTN_16);
   switch (a.D) {

@@ -19,6 +19,7 @@
 #include <type_traits>
 #include "dfh_common.h"
 #include "attention.h"
+#include "walk_knobs.h"
 
 namespace {
 
@@ -475,7 +476,7 @@ int launch_bwd(const AttnBwdArgs& a, hipStream_t stream) {
     // PROBE builds only -- DFH_ATTN_BWD_X32: 1 = both passes with S / dP on 32x32x16 (48-deep instead of 64-deep: a quarter of their
     // matrix-pipe cycles, P / dS re-laid-out with v_permlane16_swap), 2 / 3 = only the dQ / the dK-dV pass.  Parity-green and SLOWER:
     // 1616 against 1575 us on the 64x64-level launch pair (profiles/r05/attn_bwd_x32_ab.txt) -- the passes are not matrix-pipe bound.
-    static const int x32 = [] { const char* e = getenv("DFH_ATTN_BWD_X32"); return e ? atoi(e) : 0; }();
+    const int x32 = dfh::WalkKnobs::get().attn_bwd_x32;
     if (int rc = (x32 == 1 || x32 == 2) ? launch_pass<D, false, 2, true>(a, stream) : launch_pass<D, false, 2>(a, stream)) return rc;
     return (x32 == 1 || x32 == 3) ? launch_pass<D, true, 2, true>(a, stream) : launch_pass<D, true, 2>(a, stream);
   }

@@ -36,6 +36,7 @@
 // staging) and s_setprio around the MFMA clusters were both measured and were not faster (555 / 475 vs 470 us).
 #include "dfh_common.h"
 #include "attention.h"
+#include "walk_knobs.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -884,14 +885,14 @@ bool attention_x32_eligible(const AttnArgs& a) {
 int attention_x32_launch(const AttnArgs& a, hipStream_t stream) {
   census(CK_ATTN_X32);
   // short key ranges (cross-attention): keys staged once, waves stream query blocks.  DFH_ATTN_XS=0 turns it off (A/B).
-  static const bool xs_off = [] { const char* e = getenv("DFH_ATTN_XS"); return e && e[0] == '0'; }();
+  const bool xs_off = !WalkKnobs::get().attn_xs;
   if (!xs_off && a.Nk <= 2 * KVT && a.lse == nullptr) {
     if (a.D == 40) return launch_xs<40, 2>(a, stream);
     if (a.D == 64) return launch_xs<64, 1>(a, stream);
     if (a.D == 80) return launch_xs<80, 1>(a, stream);
   }
 #ifdef DFH_PROBES   // experiment instantiations (one / four query blocks per wave, phase stamps): probe builds only (scripts/probes/Makefile)
-  static const int variant = [] { const char* e = getenv("DFH_ATTN_VARIANT"); return e ? atoi(e) : 0; }();   // experiments
+  const int variant = WalkKnobs::get().attn_variant;   // DFH_ATTN_VARIANT: experiments
   switch (a.D) {
     case 40:
       if (variant == 9) {      // diagnosis: one launch with the phase stamps, printed as per-phase cycle averages
@@ -928,7 +929,7 @@ int attention_x32_launch(const AttnArgs& a, hipStream_t stream) {
   switch (a.D) {
     case 40: return launch_x32<40, 2, 2>(a, stream);
     case 64: {
-      static const int qb64 = [] { const char* e = getenv("DFH_ATTN_QB64"); return e ? atoi(e) : 2; }();     // probe knob
+      const int qb64 = WalkKnobs::get().attn_qb64;     // DFH_ATTN_QB64: probe knob
       return qb64 == 1 ? launch_x32<64, 1, 2>(a, stream) : launch_x32<64, 2, 2>(a, stream);
     }
     case 80: return launch_x32<80, 1, 2>(a, stream);

@@ -33,6 +33,7 @@
 // pair leaves value and gate of hidden units 4 g + r in the same lane; two such pairs = 32 hidden units = one k-step of the second
 // GEMM, whose B operand (k-slot 8 g + q) is {units 4 g + q of pair 0, q < 4; units 16 + 4 g + (q - 4) of pair 1}: W2's columns are
 #include "mlp_fused.h"
+#include "walk_knobs.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -181,7 +182,7 @@ size_t mlp_fused_image_bytes() { return (size_t)IMG_BYTES; }
 bool mlp_fused_eligible(int C, long M) { return C == MC && M > 0 && M % 128 == 0; }
 // DFH_MLP_FUSED: 0 = the two-launch walk (A/B), 2 = this kernel (default); 1 = the first form (probe builds only, scripts/probes/kernels/mlp_fused_v1.hip)
 int mlp_fused_form() {
-  static const int form = [] { const char* e = getenv("DFH_MLP_FUSED"); return e ? atoi(e) : 2; }();
+  const int form = WalkKnobs::get().mlp_fused;
 #ifndef DFH_PROBES
   return form == 1 ? 2 : form;
 #else

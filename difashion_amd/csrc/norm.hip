@@ -11,6 +11,7 @@
 // octet below C0/8 comes from src0, the rest from src1.
 #include "dfh_common.h"
 #include "norm.h"
+#include "walk_knobs.h"
 #include <cstring>
 #include <cstdlib>
 
@@ -496,8 +497,7 @@ static void gn_geometry(GnArgs& a, int* block, int* achunks) {
   a.PL = PL;
   *block = ((C8 * PL + 63) / 64) * 64;
   // statistics: enough chunks to fill the chip, at most GN_MAX_CHUNKS (partial buffer size)
-  static const int env_sc = [] { const char* e = getenv("DFH_GN_SC"); return e ? atoi(e) : 512; }();    // probe knobs
-  static const int env_ac = [] { const char* e = getenv("DFH_GN_AC"); return e ? atoi(e) : 1024; }();
+  const int env_sc = WalkKnobs::get().gn_sc, env_ac = WalkKnobs::get().gn_ac;    // DFH_GN_SC / DFH_GN_AC: probe knobs
   int chunks = (env_sc + a.B - 1) / a.B;
   const int max_by_pix = (a.HW + PL - 1) / PL;
   chunks = std::max(1, std::min({chunks, max_by_pix, (int)GN_MAX_CHUNKS}));
@@ -535,7 +535,7 @@ int groupnorm_launch(GnArgs a, hipStream_t stream) {
     const int cpg = a.C / a.G;
     const long units = (long)a.HW * (cpg >> 2);
     const bool one_source_per_group = a.C1 == 0 || a.C0 % cpg == 0;
-    static const int small_max = [] { const char* e = getenv("DFH_GN_SMALL_MAX"); return e ? atoi(e) : 16; }();   // probe knob; > 16 units per thread (32x32 x 640) the two-kernel path is faster since its prologue fix: 25.6 -> 21.3 us
+    const int small_max = WalkKnobs::get().gn_small_max;   // DFH_GN_SMALL_MAX, probe knob; > 16 units per thread (32x32 x 640) the two-kernel path is faster since its prologue fix: 25.6 -> 21.3 us
     if ((cpg & 3) == 0 && units <= 256 * small_max && one_source_per_group && (long)a.B * a.G >= 64) {
       ProfScope ps(PC_GNORM, 0.0, (a.out8 ? 3.0 : 4.0) * a.B * (double)a.HW * a.C, stream);
       const dim3 grid(a.G, a.B);
@@ -551,7 +551,7 @@ int groupnorm_launch(GnArgs a, hipStream_t stream) {
     // channels): GQ adjacent groups per block.  Measured against the alternatives (scripts/norm_microbench.py): 24.4 -> 13.4 us
     // on 16x16 x (1280 + 640); where gn_small_kernel is eligible it is faster (its blocks are four waves, the reductions here
     // run across up to sixteen), and at 32x32 the two-kernel path is, so this is the fallback between them.
-    static const bool mid_off = [] { const char* e = getenv("DFH_GN_MID"); return e && e[0] == '0'; }();
+    const bool mid_off = !WalkKnobs::get().gn_mid;     // DFH_GN_MID=0
     const int cpg = a.C / a.G, upp = cpg >> 2;
     if (!mid_off && !a.out8 && (cpg & 3) == 0 && a.HW <= 256 && a.G % 2 == 0) {
       for (int gq = 4; gq >= 2; gq >>= 1) {

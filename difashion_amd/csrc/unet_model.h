@@ -6,6 +6,7 @@
 
 #include "walk_common.h"
 #include "gemm_plan.h"
+#include "walk_knobs.h"
 #include "elementwise.h"
 #include "mlp_fused.h"
 #ifdef DFH_PROBES
@@ -130,10 +131,7 @@ struct dfh_unet : ParamTable {
   // ---------------------------------------------------------------- build
   // largest image (pixels) whose wide resnet convs take Winograd: 256 = the 16x16 level (default); DFH_WINO_MAXHW=1024 adds the 32x32 level
   // (the A/B of profiles/r04: measured, not the default)
-  static int wino_max_hw() {
-    static const int v = [] { const char* e = getenv("DFH_WINO_MAXHW"); return e ? atoi(e) : 256; }();
-    return v;
-  }
+  static int wino_max_hw() { return dfh::WalkKnobs::get().wino_maxhw; }
   // res: side of the (square) image this resnet runs on
   void build_resnet(const std::string& pre, int cin, int cout, ResL& r, int res) {
     const int temb = cfg.block_out_channels[0] * 4;
@@ -346,7 +344,7 @@ struct dfh_unet : ParamTable {
       if (with_bias) { q.boff = a8; a8 += ((size_t)m.N * sizeof(float) + 255) & ~(size_t)255; }
     };
     // DFH_FP8_EXT=0: only the round-2 set (the LayerNorm-fed projections) -- A/B switch
-    static const bool ext_off = [] { const char* e = getenv("DFH_FP8_EXT"); return e && e[0] == '0'; }();
+    const bool ext_off = !dfh::WalkKnobs::get().fp8_ext;
     int idx = 0;
     for (AttL* a : all_att()) {
       a->idx = idx++;
@@ -355,8 +353,7 @@ struct dfh_unet : ParamTable {
       if (ext_off) continue;
       take(a->o1, a->o18); take(a->o2, a->o28); take(a->ff2, a->ff28); take(a->pout, a->pout8); take(a->pin, a->pin8, true);
       // opt-in (dfh_unet_enable_fp8_attention / DFH_FP8_ATTN=1): see fp8_attention above
-      static const bool attn_env = [] { const char* e = getenv("DFH_FP8_ATTN"); return e && e[0] == '1'; }();
-      const bool attn_off = !(fp8_attention || attn_env);
+      const bool attn_off = !(fp8_attention || dfh::WalkKnobs::get().fp8_attn);
       const int D = a->C / a->heads;
       const bool v_contig = a->v.off == a->qk.off + (size_t)2 * a->C * a->C && a->v.K == a->qk.K;
       if (!attn_off && v_contig && (D == 40 || D == 80 || D == 160)) {
@@ -433,8 +430,7 @@ struct dfh_unet : ParamTable {
     }
 #ifdef DFH_PROBES
     for (AttL* a : all_att()) {
-      static const bool tl_on = [] { const char* e = getenv("DFH_TOKEN_LINEAR"); return e && e[0] == '1'; }();
-      if (!tl_on || !a->has_tl || (fp8 && a->qk8.on)) continue;
+      if (!dfh::WalkKnobs::get().token_linear || !a->has_tl || (fp8 && a->qk8.on)) continue;
       const int C = a->C;
       if (int rc = dfh::token_linear_pack_launch(arena16 + a->pin.off, a->pin.K, fold_w() + a->tl_pin, s)) return rc;
       if (int rc = dfh::token_linear_pack_launch(arena16 + a->o1.off, a->o1.K, fold_w() + a->tl_o1, s)) return rc;
@@ -498,6 +494,7 @@ struct dfh_unet : ParamTable {
     // fp8 walk: per transformer layer and batch element the largest |V| of the self-attention (tracked by the V projection's epilogue,
     // zeroed at the start of the walk) and of the cross-attention (amax_slabs over the text V^T, once per forward or per run): [n_att][B]
     float* amax_self = nullptr; const float* amax_cross = nullptr;
+    const dfh::WalkKnobs& kn = dfh::WalkKnobs::get();
 
     // Ba: the batch every tensor is ALLOCATED for (the call's batch); B: the batch the launches run on.  They differ only inside the
     // shared prefix of a guidance batch whose last `dup` images repeat the inputs of the `dup` images before them (dfh_unet::dup_tail):
@@ -524,12 +521,11 @@ struct dfh_unet : ParamTable {
     void gemm(GemmArgs g, Tensor* o = nullptr, Bump* bump = nullptr, int* rs_bn = nullptr) {
       if (rs_bn) *rs_bn = 0;
       if (rc) return;
-      static const bool pre_off = [] { const char* e = getenv("DFH_GN_PRE"); return e && e[0] == '0'; }();
       float* gst = nullptr;
       const int G = groups;
       // the consumers take at most GN_MAX_CHUNKS chunks per (image, group): a level fits when its 256-row chunk count does; gemm_launch
       // refuses the 128-row writer by itself when HW / 128 would exceed it (96x96 latents: 36 chunks of 256 rows, 72 of 128)
-      if (o && bump && !pre_off && o->C % G == 0 && (dfh::gstat_chunks_fit(o->H * o->W, 256) || dfh::gstat_chunks_fit(o->H * o->W, 128))) {
+      if (o && bump && kn.gn_pre && o->C % G == 0 && (dfh::gstat_chunks_fit(o->H * o->W, 256) || dfh::gstat_chunks_fit(o->H * o->W, 128))) {
         gst = (float*)bump->alloc((size_t)Ba * G * ((o->H * o->W) / 128) * 2 * sizeof(float));      // same in the dry run; chunks of 256 or 128 pixel rows
         g.gstat = gst; g.gstat_cpg = o->C / G; g.gstat_hw = o->H * o->W;
       }
@@ -604,6 +600,7 @@ struct dfh_unet : ParamTable {
       if (x.gst && x.gst_cpg == x.C / a.G) { a.pre = x.gst; a.pre_chunks = x.gst_chunks; }
       rc = dfh::groupnorm_launch(a, s);
     }
+    // f8: operand factors of the fp8 attention products (AttL::f8a_off) or null
     void attention8(const bf16_t* Q, int ldq, const bf16_t* K, int ldk, const bf16_t* Vt, int ldvt, uint8_t* O8, const float* amax, int C,
                     int heads, int Nq, int Nk, long vt_bstride = 0, const float* f8 = nullptr) {
       if (rc || dry) return;
@@ -616,12 +613,10 @@ struct dfh_unet : ParamTable {
       if (rc || dry) return;
       rc = dfh::layernorm_launch(x, v32(w), v32(b), y, M, C, 1e-5f, s);
     }
-    // f8: operand factors of the fp8 attention products (AttL::f8a_off) or null
     void attention(const bf16_t* Q, int ldq, const bf16_t* K, int ldk, const bf16_t* Vt, int ldvt, bf16_t* O, int C,
-                   int heads, int Nq, int Nk, long vt_bstride = 0, const float* f8 = nullptr) {
+                   int heads, int Nq, int Nk, long vt_bstride = 0) {
       if (rc || dry) return;
       AttnArgs a = attn_args(Q, ldq, K, ldk, Vt, ldvt, C, heads, Nq, Nk, vt_bstride);
-      if (f8) { a.f8_rq = f8; a.f8_rk = f8 + C; a.f8_rv = f8 + 2 * C; a.f8_hs = f8 + 3 * C; }
       a.O = O;
       rc = dfh::attention_launch(a, s);
     }
@@ -633,8 +628,7 @@ struct dfh_unet : ParamTable {
       Tensor o = to_persist ? palloc(Ho, Wo, c.cout) : talloc(Ho, Wo, c.cout);
       // nearest-2x upsample + conv: four 2x2 convs over the source image with the summed taps (4/9 of the multiply-adds), one launch
       // over the four phase planes.  DFH_UPS_PHASE=0 keeps the 3x3 conv over the virtual upsampled image (A/B).
-      static const bool phase_off = [] { const char* e = getenv("DFH_UPS_PHASE"); return e && e[0] == '0'; }();
-      if (ups == 1 && c.has_ph && u->fold_valid && !phase_off && !dry && x.C == c.cin) {
+      if (ups == 1 && c.has_ph && u->fold_valid && kn.ups_phase && !dry && x.C == c.cin) {
         GemmArgs g = base(B * x.H * x.W, c.cout);
         g.conv_src = x.p; g.conv_c = x.C; g.ntaps = 4; g.phase2x = 1; g.nbatch = 4; g.w_bs = (long)c.cout * 4 * x.C;
         g.Hin = x.H; g.Win = x.W; g.Hout = x.H; g.Wout = x.W; g.stride = 1; g.rows_per_b = x.H * x.W;
@@ -693,25 +687,22 @@ struct dfh_unet : ParamTable {
       Tensor g1 = talloc(H, W, r.cin);
       Tensor h1 = talloc(H, W, r.cout);
       // DFH_WINO: 0 = direct implicit GEMM everywhere, 1 = Winograd at H * W <= 64 (the 8x8 level), 2 = also at H * W <= 256 (A/B)
-      static const int wino_mode = [] { const char* e = getenv("DFH_WINO"); return e ? atoi(e) : 2; }();
-      const bool wino = r.has_u && (dry || u->fold_valid) && ((wino_mode >= 1 && H * W <= 64) || (wino_mode >= 2 && H * W <= wino_max_hw()));
+      const bool wino = r.has_u && (dry || u->fold_valid) && ((kn.wino >= 1 && H * W <= 64) || (kn.wino >= 2 && H * W <= kn.wino_maxhw));
       if (wino) {
         // the GroupNorms in front of the two convs run inside the input transforms where the (image, group) slab fits the kernel
         // (DFH_WINO_GN=0: separate GroupNorm launches, A/B)
-        static const bool gn_off = [] { const char* e = getenv("DFH_WINO_GN"); return e && e[0] == '0'; }();
         const int G = u->cfg.norm_num_groups;
         // conv1 -> conv2: the tensor between them (conv1's output, GroupNorm 2's input) is rebuilt from conv1's transform-domain planes
         // inside conv2's input transform -- no output-transform launch, no round trip (DFH_WINO_CHAIN=0: materialise it, A/B)
-        static const bool chain_off = [] { const char* e = getenv("DFH_WINO_CHAIN"); return e && e[0] == '0'; }();
         const bf16_t* V1;
-        if (!gn_off && dfh::gn_wino_ok(x0.C, x1 ? x1->C : 0, G, H, W)) V1 = wino_in(x0, x1, &r.n1w, &r.n1b);
+        if (kn.wino_gn && dfh::gn_wino_ok(x0.C, x1 ? x1->C : 0, G, H, W)) V1 = wino_in(x0, x1, &r.n1w, &r.n1b);
         else {
           groupnorm(x0, x1, r.n1w, r.n1b, u->cfg.norm_eps, 1, g1);
           V1 = wino_in(g1, nullptr, nullptr, nullptr);
         }
         const bf16_t* M1 = wino_gemm(V1, H, W, r.cin, r.u1, r.cout);
-        const bool gn2 = !gn_off && dfh::gn_wino_ok(r.cout, 0, G, H, W);
-        const bool chain = gn2 && !chain_off;
+        const bool gn2 = kn.wino_gn && dfh::gn_wino_ok(r.cout, 0, G, H, W);
+        const bool chain = gn2 && kn.wino_chain;
         Tensor g2 = talloc(H, W, r.cout);
         const bf16_t* V2;
         if (chain) V2 = wino_in(h1, nullptr, &r.n2w, &r.n2b, M1, &r.b1, temb_all, r.temb_off);     // h1 only names the shape: it is never written
@@ -763,28 +754,64 @@ struct dfh_unet : ParamTable {
       return out;
     }
 
+    // ---- transformer block.  Its two forms -- transformer(): bf16 and the round-2 fp8 set; transformer_fp8(): every linear in e4m3 -- share
+    // the entry allocations, the shared-prefix bookkeeping, the attention scratch and the addressing of the text K / V^T: the helpers below.
+    //
     // pre_n > 0 (first transformer block of a guidance batch, dfh_unet::dup_tail): the last pre_n images have the same INPUT as the pre_n
     // before them and differ only in their text states, so everything up to the self-attention output is computed for B - pre_n images
     // and the repeated images' rows are copied; from the self-attention output projection on the block runs on the whole batch.
+    struct Block {
+      int C, N, Np, pre_n; bool pre;          // pre: inside the shared prefix (B is the call's batch less pre_n until prefix_end)
+      size_t mark; Tensor out, h0, n1, qk, at, h1, h2;
+      float* st;                              // row statistics of a folded LayerNorm's input: [C / bn][M][2], bn >= 64
+      uint8_t* n8; float* s8; bf16_t* vt;     // a LayerNorm's output as e4m3 + token scales (fp8 only); V^T [B][C][Np]
+    };
+    Block block_enter(const Tensor& x, int C, int pre_n) {
+      Block b{}; b.C = C; b.N = x.H * x.W; b.pre_n = pre_n;
+      b.out = palloc(x.H, x.W, C);
+      b.mark = temp.off;
+      b.pre = pre_n > 0 && !dry && 2 * pre_n <= B;
+      if (b.pre) B -= pre_n;
+      b.st = (float*)temp.alloc((size_t)Ba * b.N * ((C + 63) / 64) * 2 * sizeof(float));
+      b.h0 = talloc(x.H, x.W, C);
+      return b;
+    }
+    void block_scratch(Block& b, bool f8) {   // what the block needs from the self-attention on
+      const int H = b.out.H, W = b.out.W, C = b.C;
+      b.n1 = talloc(H, W, C);
+      b.n8 = f8 ? (uint8_t*)temp.alloc((size_t)Ba * b.N * C) : nullptr;
+      b.s8 = f8 ? (float*)temp.alloc((size_t)Ba * b.N * sizeof(float)) : nullptr;
+      b.qk = talloc(H, W, 2 * C);
+      b.Np = (b.N + 7) & ~7;                  // V^T rows padded to 8 keys (the 2x2 level of tiny configs has N = 4)
+      b.vt = (bf16_t*)temp.alloc((size_t)Ba * C * b.Np * 2);
+      b.at = talloc(H, W, C); b.h1 = talloc(H, W, C); b.h2 = talloc(H, W, C);
+    }
+    void prefix_end(Block& b) {               // the whole batch from here on; the caller copies what else it made for the prefix
+      B += b.pre_n;
+      dup_images(b.h0, b.pre_n);
+      dfh::census(dfh::CK_DUP_PREFIX);
+    }
+    Tensor block_leave(const Block& b) { temp.off = b.mark; return b.out; }
+    // text K / V^T of a layer live inside the batched projections computed once per forward
+    struct TextKV { const bf16_t* k; int ldk; const bf16_t* vt; int ldvt; long vt_bs; };
+    TextKV text_kv(const AttL& a, const bf16_t* kx, const bf16_t* vxt, int T) const {
+      const int Tp = (T + 7) & ~7, XT = u->x_total;
+      return {kx + a.x_off, XT, vxt + (size_t)a.x_off * Tp, Tp, (long)XT * Tp};
+    }
+
     Tensor transformer(const Tensor& x, const AttL& a, const bf16_t* kx, const bf16_t* vxt, int T, int pre_n = 0) {
+      if (use8(a.qk8) && a.pin8.on) return transformer_fp8(x, a, kx, vxt, T, pre_n);
       const int H = x.H, W = x.W, C = a.C, N = H * W;
-      const int Bfull = B;
-      int M = B * N;
-      Tensor out = palloc(H, W, C);
-      const size_t mark = temp.off;
       // LayerNorm folding (gemm.h, lnfold.hip): the GEMM that produces a LayerNorm's input leaves per-row statistics of its output, the
       // projections behind the LayerNorm run on the raw rows with gamma folded into their weights and fix the rows up in their
       // epilogue -- no layernorm_kernel launch, no normalised copy of the tensor.  Falls back to the LayerNorm kernel + plain weights
       // whenever the producer ran on a kernel that writes no statistics or a consumer would split K.  DFH_LN_FOLD=0 turns it off (A/B).
-      static const bool fold_off = [] { const char* e = getenv("DFH_LN_FOLD"); return e && e[0] == '0'; }();
-      const bool f8 = use8(a.qk8);                    // fp8 path: LayerNorm -> e4m3 + token scales -> block-scaled MFMA GEMM
-      // round 4: proj_in, both to_out, ff.net.2 and proj_out in e4m3 as well, every operand quantised by the kernel that produces it
-      const bool f8x = f8 && a.pin8.on;
-      const bool fold = u->fold_valid && !fold_off && !f8 && !dry;
-      const bool pre = pre_n > 0 && !dry && 2 * pre_n <= Bfull;
-      if (pre) { B = Bfull - pre_n; M = B * N; }
-      float* st = (float*)temp.alloc((size_t)Ba * N * ((C + 63) / 64) * 2 * sizeof(float));       // [C / bn][M][2], bn >= 64
-      int bn = 0;
+      const bool f8 = use8(a.qk8);                    // the round-2 fp8 set (DFH_FP8_EXT=0): LayerNorm -> e4m3 + token scales -> block-scaled MFMA GEMM
+      const bool fold = u->fold_valid && kn.ln_fold && !f8 && !dry;
+      Block b = block_enter(x, C, pre_n);
+      Tensor &out = b.out, &h0 = b.h0;
+      float* const st = b.st;
+      int M = B * N, bn = 0;
       auto try_folded = [&](std::initializer_list<GemmArgs> gs) {
         if (!fold || bn <= 0 || C % bn) return false;
         for (const GemmArgs& g : gs) if (!dfh::gemm_ln_consumer_ok(g)) return false;
@@ -798,8 +825,7 @@ struct dfh_unet : ParamTable {
       // launch at M = 65536, sampling step 15.7 -> 15.9 ms (profiles/r05/token_linear_ab.txt): one workgroup per CU leaves its prologue (row
       // loads, first weight slice) and epilogue exposed twice per launch, and every 128-token tile re-streams the whole 200-KB matrix
 #ifdef DFH_PROBES
-      static const bool tl_on = [] { const char* e = getenv("DFH_TOKEN_LINEAR"); return e && e[0] == '1'; }();
-      const bool tl = fold && tl_on && a.has_tl && dfh::token_linear_eligible(C, C, M);
+      const bool tl = fold && kn.token_linear && a.has_tl && dfh::token_linear_eligible(C, C, M);
       auto token_linear = [&](const bf16_t* xin, size_t img, const float* bias, const bf16_t* resid, const Fold* f, bf16_t* o, bool stats) {
         if (rc) return;
         TokLinArgs t; std::memset(&t, 0, sizeof(t));
@@ -813,63 +839,47 @@ struct dfh_unet : ParamTable {
       constexpr bool tl = false;
       auto token_linear = [](const bf16_t*, size_t, const float*, const bf16_t*, const Fold*, bf16_t*, bool) {};
 #endif
-      Tensor h0 = talloc(H, W, C);
-      uint8_t* a8 = f8x ? (uint8_t*)temp.alloc((size_t)Ba * N * C) : nullptr;          // e4m3 operand of proj_in, then of the two to_out
-      float* am_self = f8x ? amax_self + (size_t)a.idx * Ba : nullptr;
-      const float* am_cross = f8x ? amax_cross + (size_t)a.idx * Ba : nullptr;
-      if (f8x) {
-        groupnorm8(x, 1e-6f, a8);
-        Fp8GemmArgs g = args8(a8, M, a.pin8, nullptr, h0.p);
-        g.bias = (const float*)(u->arena8 + a.pin8.boff); g.sa_mul = dfh_unet::GN_Z / 448.0f;
-        gemm8(g);
-      } else {
-        // GroupNorm FOLDED into proj_in (norm.h GnFoldArgs): per-image weights W . gamma . rstd and a per-image row vector for the mean /
-        // beta terms, so proj_in reads the block input itself and the normalised copy (one read + one write of the tensor) is never made.
-        // Pays while the per-image weights (B x C x C) are small against the tensor: C <= DFH_GN_FOLD (default 320: the five 64x64-level
-        // blocks; 0 = off).  Same box, sampling step: off 15.97 / 15.93, 320: 15.83 / 15.78, 640: 15.86 / 15.90, 1280: 16.01 / 16.00 ms
-        // (profiles/r05/gn_fold_ab.txt).  The images must be whole 128-row tiles.
-        static const int gn_fold_max = [] { const char* e = getenv("DFH_GN_FOLD"); return e ? atoi(e) : 320; }();
-        const bool gfold = !tl && C <= gn_fold_max && N % 128 == 0 && a.pin.K == C && a.pin.N == C;
-        if (gfold) {
-          bf16_t* wimg = (bf16_t*)temp.alloc((size_t)Ba * C * C * 2);
-          float* rv = (float*)temp.alloc((size_t)Ba * C * sizeof(float));
-          if (!rc && !dry) {
-            GnFoldArgs f; std::memset(&f, 0, sizeof(f));
-            f.x = x.p; f.B = B; f.HW = N; f.C = C; f.G = u->cfg.norm_num_groups; f.eps = 1e-6f; f.gamma = v32(a.nw); f.beta = v32(a.nb);
-            if (x.gst && x.gst_cpg == C / f.G) { f.pre = x.gst; f.pre_chunks = x.gst_chunks; }
-            f.partial = gn_partial; f.W = w16(a.pin); f.ldw = a.pin.K; f.N = C; f.bias = v32(a.pinb); f.Wimg = wimg; f.rv = rv;
-            rc = dfh::groupnorm_fold_launch(f, s);
-          }
-          GemmArgs g = base(M, C);
-          g.p_src[0] = x.p; g.p_c[0] = C; g.nplain = 1;
-          g.W = wimg; g.ldw = C; g.w_img_bs = (long)C * C;
-          g.rowvec = rv; g.rv_ld = C; g.rv_off = 0; g.rows_per_b = N;
-          g.out = h0.p; g.rowstat = fold ? st : nullptr;
-          gemm(g, nullptr, nullptr, &bn);
-        } else {
-          Tensor gn = talloc(H, W, C);
-          groupnorm(x, nullptr, a.nw, a.nb, 1e-6f, 0, gn);
-          if (tl) token_linear(gn.p, a.tl_pin, v32(a.pinb), nullptr, nullptr, h0.p, true);
-          else linear(gn.p, M, C, a.pin, &a.pinb, ACT_NONE, nullptr, h0.p, C, OUT_BF16, -1, 0, nullptr, nullptr, fold ? st : nullptr, &bn);
+      // GroupNorm FOLDED into proj_in (norm.h GnFoldArgs): per-image weights W . gamma . rstd and a per-image row vector for the mean /
+      // beta terms, so proj_in reads the block input itself and the normalised copy (one read + one write of the tensor) is never made.
+      // Pays while the per-image weights (B x C x C) are small against the tensor: C <= DFH_GN_FOLD (default 320: the five 64x64-level
+      // blocks; 0 = off).  Same box, sampling step: off 15.97 / 15.93, 320: 15.83 / 15.78, 640: 15.86 / 15.90, 1280: 16.01 / 16.00 ms
+      // (profiles/r05/gn_fold_ab.txt).  The images must be whole 128-row tiles.
+      const bool gfold = !tl && C <= kn.gn_fold && N % 128 == 0 && a.pin.K == C && a.pin.N == C;
+      if (gfold) {
+        bf16_t* wimg = (bf16_t*)temp.alloc((size_t)Ba * C * C * 2);
+        float* rv = (float*)temp.alloc((size_t)Ba * C * sizeof(float));
+        if (!rc && !dry) {
+          GnFoldArgs f; std::memset(&f, 0, sizeof(f));
+          f.x = x.p; f.B = B; f.HW = N; f.C = C; f.G = u->cfg.norm_num_groups; f.eps = 1e-6f; f.gamma = v32(a.nw); f.beta = v32(a.nb);
+          if (x.gst && x.gst_cpg == C / f.G) { f.pre = x.gst; f.pre_chunks = x.gst_chunks; }
+          f.partial = gn_partial; f.W = w16(a.pin); f.ldw = a.pin.K; f.N = C; f.bias = v32(a.pinb); f.Wimg = wimg; f.rv = rv;
+          rc = dfh::groupnorm_fold_launch(f, s);
         }
+        GemmArgs g = base(M, C);
+        g.p_src[0] = x.p; g.p_c[0] = C; g.nplain = 1;
+        g.W = wimg; g.ldw = C; g.w_img_bs = (long)C * C;
+        g.rowvec = rv; g.rv_ld = C; g.rv_off = 0; g.rows_per_b = N;
+        g.out = h0.p; g.rowstat = fold ? st : nullptr;
+        gemm(g, nullptr, nullptr, &bn);
+      } else {
+        Tensor gn = talloc(H, W, C);
+        groupnorm(x, nullptr, a.nw, a.nb, 1e-6f, 0, gn);
+        if (tl) token_linear(gn.p, a.tl_pin, v32(a.pinb), nullptr, nullptr, h0.p, true);
+        else linear(gn.p, M, C, a.pin, &a.pinb, ACT_NONE, nullptr, h0.p, C, OUT_BF16, -1, 0, nullptr, nullptr, fold ? st : nullptr, &bn);
       }
       // --- self attention
-      Tensor n1 = talloc(H, W, C);
-      uint8_t* n8 = f8 ? (uint8_t*)temp.alloc((size_t)Ba * N * C) : nullptr;
-      float* s8 = f8 ? (float*)temp.alloc((size_t)Ba * N * sizeof(float)) : nullptr;
-      Tensor qk = talloc(H, W, 2 * C);
-      const int Np = (N + 7) & ~7;    // V^T rows padded to 8 keys (the 2x2 level of tiny configs has N = 4)
-      bf16_t* vt = (bf16_t*)temp.alloc((size_t)Ba * C * Np * 2);   // [B][C][Np]
+      block_scratch(b, f8);
+      Tensor &n1 = b.n1, &qk = b.qk, &at = b.at, &h1 = b.h1, &h2 = b.h2;
+      uint8_t* const n8 = b.n8; float* const s8 = b.s8; bf16_t* const vt = b.vt; const int Np = b.Np;
       // q | k and V^T from ONE launch (columns 2C .. 3C leave transposed into vt: GemmArgs::out2) wherever the column tile divides 2C;
       // DFH_QKV_MERGE=0 keeps the two launches (A/B)
-      static const bool merge_off = [] { const char* e = getenv("DFH_QKV_MERGE"); return e && e[0] == '0'; }();
       auto with_v = [&](GemmArgs g) {               // q | k launch -> q | k | v: same rows, N = 3C, the v columns into vt
         g.N = 3 * C; g.out2 = vt; g.ld_out2 = Np; g.n_split = 2 * C; g.rows_per_b = N;
         return g;
       };
       const bool v_contig = a.v.off == a.qk.off + (size_t)2 * C * C && a.v.K == a.qk.K;   // packed back to back (build_attn)
       bool done = false;
-      if (!f8 && !merge_off && !dry) {
+      if (!f8 && kn.qkv_merge && !dry) {
         GemmArgs gq = with_v(folded(h0.p, M, a.fqk, st, bn, ACT_NONE, qk.p, OUT_BF16, 2 * C, 0));
         if (dfh::gemm_out2_ok(gq)) done = try_folded({gq});
       }
@@ -879,7 +889,7 @@ struct dfh_unet : ParamTable {
         if (f8) layernorm8(h0.p, a.l1w, a.l1b, n8, s8, M, C);
         else layernorm(h0.p, a.l1w, a.l1b, n1.p, M, C);
         bool merged = false;
-        if (!f8 && !merge_off && !dry && v_contig) {
+        if (!f8 && kn.qkv_merge && !dry && v_contig) {
           GemmArgs g = base(M, 2 * C);
           g.p_src[0] = n1.p; g.p_c[0] = C; g.nplain = 1; g.W = w16(a.qk); g.ldw = C; g.out = qk.p; g.ld_out = 2 * C;
           g = with_v(g);
@@ -888,36 +898,18 @@ struct dfh_unet : ParamTable {
         if (!merged) {
           if (f8) linear8(n8, s8, M, a.qk8, nullptr, ACT_NONE, qk.p);
           else linear(n1.p, M, C, a.qk, nullptr, ACT_NONE, nullptr, qk.p, 2 * C);
-          if (f8) linear8(n8, s8, M, a.v8, nullptr, ACT_NONE, vt, OUT_BF16_T, Np, N, am_self);
+          if (f8) linear8(n8, s8, M, a.v8, nullptr, ACT_NONE, vt, OUT_BF16_T, Np, N);
           else linear(n1.p, M, C, a.v, nullptr, ACT_NONE, nullptr, vt, C, OUT_BF16_T, Np, N);
         }
       }
-      Tensor at = talloc(H, W, C);
-      Tensor h1 = talloc(H, W, C);
-      // self-attention products on the e4m3 MFMA where the layer has operand factors and the keys make whole 64-key tiles
-      const float* f8attn = (f8 && a.f8a && N % 64 == 0) ? (const float*)(u->arena8 + a.f8a_off) : nullptr;
-      if (f8x) {
-        attention8(qk.p, 2 * C, qk.p + C, 2 * C, vt, Np, a8, am_self, C, a.heads, N, N, 0, f8attn);
-        if (pre) {                                     // end of the shared prefix (e4m3 walk): rows, e4m3 attention output and its per-image max
-          B = Bfull; M = B * N;
-          dup_images(h0, pre_n); dup_bytes(a8, (size_t)N * C, pre_n); dup_bytes(am_self, sizeof(float), pre_n);
-          dfh::census(dfh::CK_DUP_PREFIX);
-        }
-        Fp8GemmArgs g = args8(a8, M, a.o18, &a.o1b, h1.p);
-        g.sA = am_self; g.sa_div = N; g.sa_mul = 1.0f / 448.0f; g.resid = h0.p; g.ld_res = C;
-        gemm8(g);
-      } else {
-        attention(qk.p, 2 * C, qk.p + C, 2 * C, vt, Np, at.p, C, a.heads, N, N, 0, f8attn);
-        if (pre) {                                     // end of the shared prefix: the whole batch from here on
-          B = Bfull; M = B * N;
-          dup_images(h0, pre_n); dup_images(at, pre_n);
-          dfh::census(dfh::CK_DUP_PREFIX);
-        }
-        if (tl) token_linear(at.p, a.tl_o1, v32(a.o1b), h0.p, nullptr, h1.p, true);
-        else linear(at.p, M, C, a.o1, &a.o1b, ACT_NONE, h0.p, h1.p, C, OUT_BF16, -1, 0, nullptr, nullptr, fold ? st : nullptr, &bn);
+      attention(qk.p, 2 * C, qk.p + C, 2 * C, vt, Np, at.p, C, a.heads, N, N);
+      if (b.pre) {                                     // end of the shared prefix: the whole batch from here on
+        prefix_end(b); dup_images(at, pre_n);
+        M = B * N;
       }
+      if (tl) token_linear(at.p, a.tl_o1, v32(a.o1b), h0.p, nullptr, h1.p, true);
+      else linear(at.p, M, C, a.o1, &a.o1b, ACT_NONE, h0.p, h1.p, C, OUT_BF16, -1, 0, nullptr, nullptr, fold ? st : nullptr, &bn);
       // --- cross attention over the T text tokens
-      const int Tp = (T + 7) & ~7;
       if (tl && bn > 0 && C % bn == 0) {
         token_linear(h1.p, a.tl_q2, nullptr, nullptr, &a.fq2, qk.p, false);
         dfh::census(dfh::CK_LN_FOLDED);
@@ -928,40 +920,11 @@ struct dfh_unet : ParamTable {
           linear(n1.p, M, C, a.q2, nullptr, ACT_NONE, nullptr, qk.p, C);
         }
       }
-      // text K / V^T of this layer live inside the batched projections computed once per forward
-      const int XT = u->x_total;
-      Tensor h2 = talloc(H, W, C);
-      if (f8x) {
-        attention8(qk.p, C, kx + a.x_off, XT, vxt + (size_t)a.x_off * Tp, Tp, a8, am_cross, C, a.heads, N, T, (long)XT * Tp);
-        Fp8GemmArgs g = args8(a8, M, a.o28, &a.o2b, h2.p);
-        g.sA = am_cross; g.sa_div = N; g.sa_mul = 1.0f / 448.0f; g.resid = h1.p; g.ld_res = C;
-        gemm8(g);
-      } else {
-        attention(qk.p, C, kx + a.x_off, XT, vxt + (size_t)a.x_off * Tp, Tp, at.p, C, a.heads, N, T, (long)XT * Tp);
-        if (tl) token_linear(at.p, a.tl_o2, v32(a.o2b), h1.p, nullptr, h2.p, true);
-        else linear(at.p, M, C, a.o2, &a.o2b, ACT_NONE, h1.p, h2.p, C, OUT_BF16, -1, 0, nullptr, nullptr, fold ? st : nullptr, &bn);
-      }
+      const TextKV t = text_kv(a, kx, vxt, T);
+      attention(qk.p, C, t.k, t.ldk, t.vt, t.ldvt, at.p, C, a.heads, N, T, t.vt_bs);
+      if (tl) token_linear(at.p, a.tl_o2, v32(a.o2b), h1.p, nullptr, h2.p, true);
+      else linear(at.p, M, C, a.o2, &a.o2b, ACT_NONE, h1.p, h2.p, C, OUT_BF16, -1, 0, nullptr, nullptr, fold ? st : nullptr, &bn);
       // --- GEGLU feed-forward
-      if (f8x) {
-        // hidden tensor in e4m3 with one E8M0 scale per token and 32 hidden units, written by the GEGLU epilogue and consumed by ff.net.2
-        // through the MFMA's scale operand; ff.net.2's output (+ bias + h2) likewise, consumed by proj_out (+ the block's residual)
-        uint8_t* ff8 = (uint8_t*)temp.alloc((size_t)M * 4 * C);
-        uint8_t* ffsx = (uint8_t*)temp.alloc((size_t)(4 * C / 32) * M + 256);
-        uint8_t* t8 = (uint8_t*)temp.alloc((size_t)M * C);
-        uint8_t* tsx = (uint8_t*)temp.alloc((size_t)(C / 32) * M + 256);
-        layernorm8(h2.p, a.l3w, a.l3b, n8, s8, M, C);
-        Fp8GemmArgs g1 = args8(n8, M, a.ff18, &a.ff1b, ff8);
-        g1.sA = s8; g1.act = ACT_GEGLU; g1.out_mode = OUT_FP8_MX; g1.ld_out = 4 * C; g1.out_sx = ffsx;
-        gemm8(g1);
-        Fp8GemmArgs g2 = args8(ff8, M, a.ff28, &a.ff2b, t8);
-        g2.sx = ffsx; g2.resid = h2.p; g2.ld_res = C; g2.out_mode = OUT_FP8_MX; g2.ld_out = C; g2.out_sx = tsx;
-        gemm8(g2);
-        Fp8GemmArgs g3 = args8(t8, M, a.pout8, &a.poutb, out.p);
-        g3.sx = tsx; g3.resid = x.p; g3.ld_res = C;
-        gemm8(g3);
-        temp.off = mark;
-        return out;
-      }
       // statistics of the block's output for the next GroupNorm, written by the fused kernel's epilogue in 128-token chunks (allocated in the
       // dry run as well: the unfused path plans 256-token chunks through gemm())
       const int G = u->cfg.norm_num_groups;
@@ -976,8 +939,7 @@ struct dfh_unet : ParamTable {
         ma.x = h2.p; ma.resid = x.p; ma.img = (const unsigned char*)(u->fold_w() + a.mlp_img);
         ma.ln_stat = st; ma.ln_parts = C / bn; ma.ln_cnt = bn; ma.ln_eps = 1e-5f;
         ma.bias = u->fold_v() + a.fffp.b; ma.out = out.p; ma.M = M;
-        static const bool pre_off = [] { const char* e = getenv("DFH_GN_PRE"); return e && e[0] == '0'; }();
-        if (dfh::mlp_fused_form() == 2 && mlp_gst && !pre_off) {
+        if (dfh::mlp_fused_form() == 2 && mlp_gst && kn.gn_pre) {
           ma.gstat = mlp_gst; ma.gstat_cpg = C / G; ma.gstat_hw = N;
           out.gst = mlp_gst; out.gst_cpg = C / G; out.gst_chunks = N / 128;
           dfh::census(dfh::CK_GSTAT_WRITTEN);
@@ -987,8 +949,7 @@ struct dfh_unet : ParamTable {
 #endif
         if (!rc) rc = dfh::mlp2_fused_launch(ma, s);
         dfh::census(dfh::CK_LN_FOLDED);                  // LayerNorm 3 is consumed folded here too
-        temp.off = mark;
-        return out;
+        return block_leave(b);
       }
       if (!try_folded({folded(h2.p, M, a.fff1, st, bn, ACT_GEGLU, ff.p, OUT_BF16, -1, 0)})) {
         if (f8) { layernorm8(h2.p, a.l3w, a.l3b, n8, s8, M, C); linear8(n8, s8, M, a.ff18, &a.ff1b, ACT_GEGLU, ff.p); }
@@ -997,21 +958,75 @@ struct dfh_unet : ParamTable {
           linear(n1.p, M, C, a.ff1, &a.ff1b, ACT_GEGLU, nullptr, ff.p, 8 * C);
         }
       }
-      static const bool ffp_off = [] { const char* e = getenv("DFH_FFP_FOLD"); return e && e[0] == '0'; }();      // A/B switch
       // ff.net.2 and proj_out as ONE linear over the two K segments [GEGLU output | h2] (AttL::fffp) + the block's residual
       GemmArgs gf = base(M, C);
       gf.p_src[0] = ff.p; gf.p_c[0] = 4 * C; gf.p_src[1] = h2.p; gf.p_c[1] = C; gf.nplain = 2;
       gf.ldw = 5 * C; gf.resid = x.p; gf.ld_res = C; gf.out = out.p;
       if (dry) gemm(gf);                                                   // planning: its split-K slabs, whichever path runs later
-      if (u->fold_valid && !ffp_off && !dry) {
+      if (u->fold_valid && kn.ffp_fold && !dry) {      // DFH_FFP_FOLD=0: the two linears (A/B)
         gf.W = u->fold_w() + a.fffp.w; gf.bias = u->fold_v() + a.fffp.b;
         gemm(gf, &out, &persist);                                          // feeds the next block's GroupNorm
       } else {
         linear(ff.p, M, 4 * C, a.ff2, &a.ff2b, ACT_NONE, h2.p, h0.p, C);   // h0 is dead by now: reuse
         linear(h0.p, M, C, a.pout, &a.poutb, ACT_NONE, x.p, out.p, C, OUT_BF16, -1, 0, &out, &persist);   // feeds the next block's GroupNorm
       }
-      temp.off = mark;
-      return out;
+      return block_leave(b);
+    }
+
+    // The all-e4m3 block (round 4: proj_in, both to_out, ff.net.2 and proj_out in e4m3 as well as the LayerNorm-fed projections), every
+    // operand quantised by the kernel that produces it.  One straight line: none of the bf16 block's choices exists here.
+    Tensor transformer_fp8(const Tensor& x, const AttL& a, const bf16_t* kx, const bf16_t* vxt, int T, int pre_n) {
+      const int C = a.C, N = x.H * x.W;
+      Block b = block_enter(x, C, pre_n);
+      uint8_t* a8 = (uint8_t*)temp.alloc((size_t)Ba * N * C);          // e4m3 operand of proj_in, then of the two to_out
+      block_scratch(b, true);       // b.st, b.n1 and b.at are never touched here: they keep the workspace plan of an fp8 context what it was
+      float* am_self = amax_self + (size_t)a.idx * Ba;
+      const float* am_cross = amax_cross + (size_t)a.idx * Ba;
+      int M = B * N;
+      groupnorm8(x, 1e-6f, a8);
+      Fp8GemmArgs g = args8(a8, M, a.pin8, nullptr, b.h0.p);
+      g.bias = (const float*)(u->arena8 + a.pin8.boff); g.sa_mul = dfh_unet::GN_Z / 448.0f;
+      gemm8(g);
+      // --- self attention: q | k and V^T (with the largest |V| per image), products on the e4m3 MFMA where the layer has operand factors
+      // and the keys make whole 64-key tiles
+      layernorm8(b.h0.p, a.l1w, a.l1b, b.n8, b.s8, M, C);
+      linear8(b.n8, b.s8, M, a.qk8, nullptr, ACT_NONE, b.qk.p);
+      linear8(b.n8, b.s8, M, a.v8, nullptr, ACT_NONE, b.vt, OUT_BF16_T, b.Np, N, am_self);
+      const float* f8attn = (a.f8a && N % 64 == 0) ? (const float*)(u->arena8 + a.f8a_off) : nullptr;
+      attention8(b.qk.p, 2 * C, b.qk.p + C, 2 * C, b.vt, b.Np, a8, am_self, C, a.heads, N, N, 0, f8attn);
+      if (b.pre) {                                     // end of the shared prefix: rows, e4m3 attention output and its per-image max
+        prefix_end(b); dup_bytes(a8, (size_t)N * C, pre_n); dup_bytes(am_self, sizeof(float), pre_n);
+        M = B * N;
+      }
+      g = args8(a8, M, a.o18, &a.o1b, b.h1.p);
+      g.sA = am_self; g.sa_div = N; g.sa_mul = 1.0f / 448.0f; g.resid = b.h0.p; g.ld_res = C;
+      gemm8(g);
+      // --- cross attention over the T text tokens
+      layernorm8(b.h1.p, a.l2w, a.l2b, b.n8, b.s8, M, C);
+      linear8(b.n8, b.s8, M, a.q28, nullptr, ACT_NONE, b.qk.p);
+      const TextKV t = text_kv(a, kx, vxt, T);
+      attention8(b.qk.p, C, t.k, t.ldk, t.vt, t.ldvt, a8, am_cross, C, a.heads, N, T, t.vt_bs);
+      g = args8(a8, M, a.o28, &a.o2b, b.h2.p);
+      g.sA = am_cross; g.sa_div = N; g.sa_mul = 1.0f / 448.0f; g.resid = b.h1.p; g.ld_res = C;
+      gemm8(g);
+      // --- GEGLU feed-forward: the hidden tensor in e4m3 with one E8M0 scale per token and 32 hidden units, written by the GEGLU epilogue
+      // and consumed by ff.net.2 through the MFMA's scale operand; ff.net.2's output (+ bias + h2) likewise, consumed by proj_out (+ the
+      // block's residual)
+      uint8_t* ff8 = (uint8_t*)temp.alloc((size_t)M * 4 * C);
+      uint8_t* ffsx = (uint8_t*)temp.alloc((size_t)(4 * C / 32) * M + 256);
+      uint8_t* t8 = (uint8_t*)temp.alloc((size_t)M * C);
+      uint8_t* tsx = (uint8_t*)temp.alloc((size_t)(C / 32) * M + 256);
+      layernorm8(b.h2.p, a.l3w, a.l3b, b.n8, b.s8, M, C);
+      g = args8(b.n8, M, a.ff18, &a.ff1b, ff8);
+      g.sA = b.s8; g.act = ACT_GEGLU; g.out_mode = OUT_FP8_MX; g.ld_out = 4 * C; g.out_sx = ffsx;
+      gemm8(g);
+      g = args8(ff8, M, a.ff28, &a.ff2b, t8);
+      g.sx = ffsx; g.resid = b.h2.p; g.ld_res = C; g.out_mode = OUT_FP8_MX; g.ld_out = C; g.out_sx = tsx;
+      gemm8(g);
+      g = args8(t8, M, a.pout8, &a.poutb, b.out.p);
+      g.sx = tsx; g.resid = x.p; g.ld_res = C;
+      gemm8(g);
+      return block_leave(b);
     }
   };
 
@@ -1106,8 +1121,7 @@ struct dfh_unet : ParamTable {
     if (dup && !r.rc) {
       // DFH_CHECK_DUP=1 (debugging a caller): verify what the hint claims -- the repeated images' inputs equal the ones they repeat --
       // with a synchronous compare of the converted input rows; a wrong hint is an error, not a silently different result
-      static const bool check = [] { const char* e = getenv("DFH_CHECK_DUP"); return e && e[0] == '1'; }();
-      if (check) {
+      if (dfh::WalkKnobs::get().check_dup) {
         const size_t per = (size_t)S * S * conv_in.cin * 2, n = (size_t)dup * per;
         std::vector<char> a(n), b(n);
         if (hipStreamSynchronize(s) != hipSuccess || hipMemcpy(a.data(), (char*)x.p + (size_t)(B - 2 * dup) * per, n, hipMemcpyDeviceToHost) != hipSuccess ||

@@ -97,7 +97,7 @@ struct dfh_unet::TrainRun : WalkBase {
     // launch reads, and at the end of every tape entry (gradient ranges are handed out / temporaries are reused per entry).
     double kreal = (double)f.ntaps * f.conv_c + f.p_c[0] + (f.nplain > 1 ? f.p_c[1] : 0);
     // DFH_TRAIN_SIDE_MIN_FLOP: smaller launches stay on the main stream (two event operations cost more than their tail); tests set it to 0
-    static const double side_min = [] { const char* e = getenv("DFH_TRAIN_SIDE_MIN_FLOP"); return e ? atof(e) : 2e10; }();
+    const double side_min = dfh::WalkKnobs::get().train_side_min_flop;
     if (s2 && 2.0 * f.M * f.N * kreal >= side_min) {
       (void)hipEventRecord(u->ev_fork, s);                     // everything dY depends on
       (void)hipStreamWaitEvent(s2, u->ev_fork, 0);
@@ -244,7 +244,7 @@ struct dfh_unet::TrainRun : WalkBase {
 
   GT conv(const GT& x, const ConvL& c, int stride, int ups) {
     // DFH_TRAIN_UPS_PHASE=0: the upsample convs as one 3x3 conv over the virtual upsampled image + 2x2 sum pool in the backward (A/B)
-    static const bool ph_off = [] { const char* e = getenv("DFH_TRAIN_UPS_PHASE"); return e && e[0] == '0'; }();
+    const bool ph_off = !dfh::WalkKnobs::get().train_ups_phase;
     if (ups == 1 && !ph_off && x.C % 8 == 0 && c.cout % 8 == 0 && x.C == c.cin) return conv_up_phase(x, c);
     const int Ho = ups ? x.H * 2 : (stride == 2 ? x.H / 2 : x.H);
     const int Wo = ups ? x.W * 2 : (stride == 2 ? x.W / 2 : x.W);
@@ -368,7 +368,7 @@ struct dfh_unet::TrainRun : WalkBase {
     GT ff = act(H, W, 4 * C);
     // ff.net.0: the GEMM epilogue gates (value x exact-erf GELU(gate)) into ff AND writes the bias-added pre-activations the backward
     // needs as a second output -- a separate gating pass read the 8C-wide tensor back (DFH_TRAIN_GEGLU_FUSED=0: the two-launch form, A/B)
-    static const bool geglu_split = [] { const char* e = getenv("DFH_TRAIN_GEGLU_FUSED"); return e && e[0] == '0'; }();
+    const bool geglu_split = !dfh::WalkKnobs::get().train_geglu_fused;
     GemmArgs f_ff1;
     if (!geglu_split && (8 * C) % 128 == 0) {
       f_ff1 = linear_desc(n3.p, M, C, a.ff1, &a.ff1b, nullptr, ff.p, 8 * C);
@@ -658,7 +658,7 @@ int dfh_unet::backward_begin(const float* d_out, float* d_sample, size_t bucket_
   DFH_REQUIRE(bucket_floats > 0, "bucket size must be positive");
   TrainRun& r = *tr;
   r.s = s; r.d_out = d_out; r.d_sample = d_sample;
-  static const bool side_off = [] { const char* e = getenv("DFH_TRAIN_SIDE"); return e && e[0] == '0'; }();     // A/B
+  const bool side_off = !dfh::WalkKnobs::get().train_side;     // DFH_TRAIN_SIDE=0: A/B
   if (!side_off && !side_stream) {
     if (hipStreamCreateWithFlags(&side_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming) != hipSuccess ||

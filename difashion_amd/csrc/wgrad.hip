@@ -13,6 +13,7 @@
 // one n = 16 contiguous bytes of the packed fp32 gradient.  M is split over blockIdx.z with fp32 atomics.
 #include "gemm.h"
 #include "wgrad.h"
+#include "walk_knobs.h"
 
 namespace {
 
@@ -368,7 +369,7 @@ static int wgrad_plan(WgradArgs& a) {
   // rounds of 512 -- a last round of <= 256 blocks has a CU to itself per block and takes 0.8 of a full one; a 32-row stage of a block
   // takes 0.85 us with the chip full (~0.98 PFLOP/s); a block costs 5 us of pipeline fill and epilogue; a slab slot 0.04 us (100 KB
   // written and read back).
-  static const int mode = [] { const char* e = getenv("DFH_WGRAD_PLAN"); return e ? atoi(e) : 2; }();     // 1: round-4 candidates (1 or multiples of 8)
+  const int mode = WalkKnobs::get().wgrad_plan;     // 1: round-4 candidates (1 or multiples of 8)
   constexpr double stage_us = 0.85, lone = 0.8, fill_us = 5.0, slot_us = 0.04;
   auto rounds_of = [&](long b) { const long full = b / SLOTS, rem = b % SLOTS; return full + (rem == 0 ? 0.0 : rem <= SLOTS / 2 ? lone : 1.0); };
   auto stages_of = [&](int ms) { return (double)(((a.M + ms - 1) / ms + BM - 1) / BM); };

@@ -29,7 +29,7 @@ extern "C" {
 /* Bumped whenever an entry point, a struct layout or the meaning of an argument changes (round 4: 4).  The Python host side
  * (difashion_amd/_lib.py ABI_VERSION) refuses a library that reports another number: a stale .so next to new Python, or the reverse,
  * fails at load time instead of at a symbol lookup or silently. */
-#define DFH_ABI_VERSION 7
+#define DFH_ABI_VERSION 8
 #define DFH_MAX_BLOCKS 4
 
 /* ------------------------------------------------------------------ library */
@@ -58,6 +58,10 @@ void dfh_census_reset(void);
 int dfh_census_count(void);
 const char* dfh_census_name(int i);
 long dfh_census_get(int i);
+/* The DFH_* switches of the model walks and the launchers as this process read them (host code, no GPU needed): one
+ * NAME=value line per switch, on/off switches as 1 / 0.  The environment is read once per process, at the first use of any switch.
+ * Writes at most cap - 1 characters and a NUL into buf (buf may be NULL with cap 0); returns the length of the whole text. */
+size_t dfh_walk_switches(char* buf, size_t cap);
 
 /* ------------------------------------------------------------------ U-Net context
  * Replaces: diffusers UNet2DConditionModel as constructed at df.py:77-93 (in_channels widened to

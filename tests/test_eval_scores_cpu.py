@@ -66,13 +66,13 @@ def test_score_fixture_checksums():
 
 def test_new_symbols_in_header_library_and_binding():
     src = open(os.path.join(ROOT, "include", "difashion_hip.h")).read()
-    assert "#define DFH_ABI_VERSION 7" in src and "#define DFH_COMPAT_NUM_PARAMS 32" in src
+    assert "#define DFH_ABI_VERSION 8" in src and "#define DFH_COMPAT_NUM_PARAMS 32" in src
     decl = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     lib = _lib.raw()
     for n in NEW_SYMBOLS:
         assert re.search(r"\b%s\s*\(" % n, decl), n
         assert hasattr(lib, n) and n in _lib.SIGNATURES, n
-    assert lib.dfh_abi_version() == 7
+    assert lib.dfh_abi_version() == 8
     f16 = C.CDLL(os.path.join(_lib.CSRC, "libdifashion_hip_f16.so"))
     assert all(hasattr(f16, n) for n in NEW_SYMBOLS)
     # the size query is host-only work
