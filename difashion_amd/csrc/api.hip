@@ -169,11 +169,8 @@ static int fill_wgrad(const dfh_gemm_desc* d, const void* dY, int ldy, float* dW
   if (!tmp.W) tmp.W = &dummy;
   if (!tmp.out) tmp.out = &dummy;
   if (int rc = fill_gemm(&tmp, &g)) return rc;
-  std::memset(&w, 0, sizeof(w));
-  w.conv_src = g.conv_src; w.conv_c = g.conv_c; w.ntaps = g.ntaps;
-  w.Hin = g.Hin; w.Win = g.Win; w.Hout = g.Hout; w.Wout = g.Wout; w.stride = g.stride; w.ups = g.ups;
-  w.p_src[0] = g.p_src[0]; w.p_src[1] = g.p_src[1]; w.p_c[0] = g.p_c[0]; w.p_c[1] = g.p_c[1]; w.nplain = g.nplain;
-  w.dY = (const bf16_t*)dY; w.ldy = ldy; w.zero = g.zero; w.M = g.M; w.N = g.N; w.dW = dW; w.ldw = ldw; w.msplit = msplit;
+  w = WgradArgs(g);
+  w.dY = (const bf16_t*)dY; w.ldy = ldy; w.dW = dW; w.ldw = ldw; w.msplit = msplit;
   w.partial = d->partial; w.partial_cap = d->partial_floats;
   return 0;
 }

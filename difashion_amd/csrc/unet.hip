@@ -1,5 +1,6 @@
-// Host-side runtime of the conditional U-Net: parameter table, weight-packing plan, workspace
-// planning and the forward walk that strings the gfx950 kernels together.
+// C entry points of the conditional U-Net's host-side runtime (struct dfh_unet, unet_model.h): parameter table and weight-packing plan
+// (unet_build.hip), derived weights (unet_derive.hip), workspace planning and the forward walk that strings the gfx950 kernels
+// together (unet_walk.hip).
 //
 // Replaces (arithmetic): diffusers 0.18.2 UNet2DConditionModel.forward as used by the reference at
 // DiFashion/models/difashion.py:249-253 (training) and :518-523 (sampling), topology per SURVEY.md
@@ -51,14 +52,14 @@ size_t dfh_unet_arena32_bytes(const dfh_unet* u) { return u->arena32_bytes(); }
 size_t dfh_unet_workspace_bytes(dfh_unet* u, int batch) {
   if (batch <= 0) return 0;
   u->run(nullptr, 0, nullptr, nullptr, 0, nullptr, batch, nullptr, /*dry=*/true);
-  return u->plan_total;
+  return u->plan_total();
 }
 
 int dfh_unet_bind(dfh_unet* u, void* arena16, void* arena32, void* workspace, size_t workspace_bytes, int max_batch) {
   DFH_REQUIRE(u && arena16 && arena32 && workspace, "null argument");
   DFH_REQUIRE(((uintptr_t)arena16 | (uintptr_t)arena32 | (uintptr_t)workspace) % 256 == 0, "buffers must be 256-byte aligned");
   u->run(nullptr, 0, nullptr, nullptr, 0, nullptr, max_batch, nullptr, /*dry=*/true);
-  DFH_REQUIRE(workspace_bytes >= u->plan_total, "workspace smaller than dfh_unet_workspace_bytes(max_batch)");
+  DFH_REQUIRE(workspace_bytes >= u->plan_total(), "workspace smaller than dfh_unet_workspace_bytes(max_batch)");
   u->arena16 = (bf16_t*)arena16; u->arena32 = (float*)arena32;
   u->ws = (char*)workspace; u->ws_bytes = workspace_bytes; u->max_batch = max_batch;
   return 0;
@@ -107,8 +108,6 @@ int dfh_unet_forward(dfh_unet* u, const void* sample, int sample_bf16, const flo
   DFH_REQUIRE(u->ws != nullptr, "dfh_unet_bind not called");
   DFH_REQUIRE(batch > 0 && batch <= u->max_batch, "batch exceeds the bound max_batch");
   DFH_REQUIRE(!u->fp8 || u->arena8, "fp8 enabled but dfh_unet_bind_fp8 not called");
-  if (batch != u->plan_batch) u->run(nullptr, 0, nullptr, nullptr, 0, nullptr, batch, nullptr, true);
-  DFH_REQUIRE(u->plan_total <= u->ws_bytes, "workspace too small for this batch");
   return u->run(sample, sample_bf16, timestep, ehs, ehs_bf16, out, batch, (hipStream_t)stream, false);
 }
 
@@ -139,8 +138,6 @@ int dfh_unet_forward_cached(dfh_unet* u, const void* sample, int sample_bf16, co
   DFH_REQUIRE(batch > 0 && batch <= u->max_batch, "batch exceeds the bound max_batch");
   DFH_REQUIRE(t_index >= 0 && t_index < n_timesteps, "timestep index outside the cached schedule");
   DFH_REQUIRE(!u->fp8 || u->arena8, "fp8 enabled but dfh_unet_bind_fp8 not called");
-  if (batch != u->plan_batch) u->run(nullptr, 0, nullptr, nullptr, 0, nullptr, batch, nullptr, true);
-  DFH_REQUIRE(u->plan_total <= u->ws_bytes, "workspace too small for this batch");
   dfh_unet::RunCache rc;
   rc.kx = (const bf16_t*)cache;
   rc.vxt = (const bf16_t*)((const char*)cache + dfh_unet::cache_kx_bytes(*u, batch));

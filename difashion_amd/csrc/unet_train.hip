@@ -31,7 +31,7 @@ struct GT { bf16_t* p = nullptr; bf16_t* g = nullptr; int H = 0, W = 0, C = 0; i
 struct dfh_unet::TrainRun : WalkBase {
   dfh_unet* u;
   // persist: every activation of the step and the gradients that cross layers; temp: layer-internal gradient buffers, a stack
-  float* partial2 = nullptr;                                   // slab region of the weight-gradient launches on the side stream
+  // partial2 (WalkBase): slab region of the weight-gradient launches on the side stream
   hipStream_t s2 = nullptr; bool forked = false;               // see wgrad() / join()
   TrainRun(dfh_unet* u_, int B_, hipStream_t s_, bool dry_) : WalkBase(*u_, u_->cfg.norm_num_groups, B_, s_, dry_), u(u_) {}
   std::vector<std::function<void()>> tape;
@@ -77,12 +77,9 @@ struct dfh_unet::TrainRun : WalkBase {
   // dW (packed fp32 gradient of the matrix at arena16 + w_off) += dY^T . A, A described by the forward descriptor
   void wgrad(const GemmArgs& f, const bf16_t* dY, int ldy, size_t w_off, const Vec* bias = nullptr) {
     if (rc) return;
-    WgradArgs w; std::memset(&w, 0, sizeof(w));
-    w.conv_src = f.conv_src; w.conv_c = f.conv_c; w.ntaps = f.ntaps;
-    w.Hin = f.Hin; w.Win = f.Win; w.Hout = f.Hout; w.Wout = f.Wout; w.stride = f.stride; w.ups = f.ups;
-    w.p_src[0] = f.p_src[0]; w.p_src[1] = f.p_src[1]; w.p_c[0] = f.p_c[0]; w.p_c[1] = f.p_c[1]; w.nplain = f.nplain;
-    w.dY = dY; w.ldy = ldy; w.zero = zero; w.M = f.M; w.N = f.N;
-    w.dW = u->grad16 + w_off; w.ldw = f.ldw; w.msplit = 0;
+    WgradArgs w(f);
+    w.dY = dY; w.ldy = ldy; w.zero = zero;                 // (the saved descriptor never saw the zero page: gemm() fills its own copy)
+    w.dW = u->grad16 + w_off;
     w.dbias = bias ? g32(*bias) : nullptr;
     w.overwrite = 1;          // every packed matrix has exactly one weight-gradient launch per backward: no memset, no RMW
     w.partial = partial; w.partial_cap = partial_cap / sizeof(float);     // shares the split-K slab region of the GEMMs
@@ -219,11 +216,10 @@ struct dfh_unet::TrainRun : WalkBase {
     tape.push_back([=] {
       TR_OP(dfh::phase_gather_launch(o.g, dyp, B, H, W, Co, s));
       for (int p = 0; p < 4 && !rc; ++p) {
-        WgradArgs w; std::memset(&w, 0, sizeof(w));
-        w.conv_src = x.p; w.conv_c = Ci; w.ntaps = 4; w.tap2 = 1; w.tap_py = p >> 1; w.tap_px = p & 1;
-        w.Hin = H; w.Win = W; w.Hout = H; w.Wout = W; w.stride = 1;
-        w.dY = dyp + (size_t)p * M * Co; w.ldy = Co; w.zero = zero; w.M = M; w.N = Co;
-        w.dW = dwp + (size_t)p * Co * 4 * Ci; w.ldw = 4 * Ci; w.overwrite = 1; w.dbias = g32(cp->b);
+        WgradArgs w(f);                 // the forward's four taps over the source image, one plane at a time
+        w.tap2 = 1; w.tap_py = p >> 1; w.tap_px = p & 1;
+        w.dY = dyp + (size_t)p * M * Co; w.ldy = Co; w.zero = zero;
+        w.dW = dwp + (size_t)p * Co * 4 * Ci; w.overwrite = 1; w.dbias = g32(cp->b);
         w.partial = partial; w.partial_cap = partial_cap / sizeof(float);
         if (dry) { partial_need = std::max(partial_need, dfh::wgrad_partial_floats(w) * sizeof(float)); continue; }
         rc = dfh::wgrad_launch(w, s);
@@ -290,13 +286,7 @@ struct dfh_unet::TrainRun : WalkBase {
     GT g2 = act(H, W, r.cout);
     float* st2 = fbuf((size_t)B * G * 2);
     groupnorm(h1, nullptr, r.n2w, r.n2b, u->cfg.norm_eps, 1, g2.p, st2);
-    GemmArgs f2 = conv_desc(g2.p, r.cout, H, W, H, W, 1, 0, r.w2, r.b2);
-    if (r.shortcut) {
-      f2.p_src[0] = x0.p; f2.p_c[0] = x0.C; f2.nplain = 1;
-      if (has1) { f2.p_src[1] = x1.p; f2.p_c[1] = x1.C; f2.nplain = 2; }
-    } else {
-      f2.resid = x0.p; f2.ld_res = r.cout;
-    }
+    GemmArgs f2 = conv2_desc(g2.p, H, W, r.cout, r.w2, r.b2, r.shortcut, x0.p, x0.C, has1 ? x1.p : nullptr, x1.C);
     f2.out = out.p;
     gemm(f2);
     temp.off = mark;
@@ -542,102 +532,28 @@ dfh_unet::~dfh_unet() {
   if (sq_scratch) (void)hipFree(sq_scratch);
 }
 
-// ------------------------------------------------------------------------------------------- build / plan
-int dfh_unet::build_train() {
-  if (train_built) return 0;
-  std::map<std::string, int> idx;
-  for (int i = 0; i < (int)params.size(); ++i) idx[params[i].name] = i;
-  auto talloc = [&](int N, int K) { Mat m; m.N = N; m.K = K; m.off = a16t; a16t += ((size_t)N * K + 127) & ~(size_t)127; return m; };
-  auto tmat = [&](const std::string& name, int N, int K, const Mat& dst, int t_row_off, int t_col_off, int geglu) {
-    tpacks.push_back({idx.at(name), 0, dst.off, N, K, dst.K, t_row_off, t_col_off, geglu, 0});
-  };
-  auto tconv = [&](const std::string& name, int cout, int cin, const Mat& dst, int o_pad) {
-    tpacks.push_back({idx.at(name), 1, dst.off, cout, cin, dst.K, 0, 0, 0, o_pad});
-  };
-  const int temb = cfg.block_out_channels[0] * 4;
-  tprojt = talloc(temb, temb_total);
-  te2t = talloc(temb, temb);
-  tmat("time_embedding.linear_2.weight", temb, temb, te2t, 0, 0, 0);
-  auto res = [&](ResL& r) {
-    r.w1t = talloc(r.cin, 9 * r.cout);
-    tconv(r.pre + ".conv1.weight", r.cout, r.cin, r.w1t, r.cout);
-    r.w2t = talloc(r.cout, 9 * r.cout);
-    tconv(r.pre + ".conv2.weight", r.cout, r.cout, r.w2t, r.cout);
-    if (r.shortcut) {
-      r.wst = talloc(r.cin, r.cout);
-      tmat(r.pre + ".conv_shortcut.weight", r.cout, r.cin, r.wst, 0, 0, 0);
-    }
-    tmat(r.pre + ".time_emb_proj.weight", r.cout, temb, tprojt, 0, r.temb_off, 0);
-  };
-  auto att = [&](AttL& a) {
-    const int C = a.C;
-    const std::string tb = a.pre + ".transformer_blocks.0";
-    a.pint = talloc(C, C); tmat(a.pre + ".proj_in.weight", C, C, a.pint, 0, 0, 0);
-    a.qkvt = talloc(C, 3 * C);
-    tmat(tb + ".attn1.to_q.weight", C, C, a.qkvt, 0, 0, 0);
-    tmat(tb + ".attn1.to_k.weight", C, C, a.qkvt, 0, C, 0);
-    tmat(tb + ".attn1.to_v.weight", C, C, a.qkvt, 0, 2 * C, 0);
-    a.o1t = talloc(C, C); tmat(tb + ".attn1.to_out.0.weight", C, C, a.o1t, 0, 0, 0);
-    a.q2t = talloc(C, C); tmat(tb + ".attn2.to_q.weight", C, C, a.q2t, 0, 0, 0);
-    a.o2t = talloc(C, C); tmat(tb + ".attn2.to_out.0.weight", C, C, a.o2t, 0, 0, 0);
-    a.ff1t = talloc(C, 8 * C); tmat(tb + ".ff.net.0.proj.weight", 8 * C, C, a.ff1t, 0, 0, 1);
-    a.ff2t = talloc(4 * C, C); tmat(tb + ".ff.net.2.weight", C, 4 * C, a.ff2t, 0, 0, 0);
-    a.poutt = talloc(C, C); tmat(a.pre + ".proj_out.weight", C, C, a.poutt, 0, 0, 0);
-  };
-  auto cv = [&](ConvL& c, int real_cin) {
-    const int op = (c.cout + 7) & ~7;
-    c.wt = talloc(c.cin, 9 * op);                  // rows beyond real_cin / columns beyond cout stay zero (zero-filled arena)
-    tconv(c.pre + ".weight", c.cout, real_cin, c.wt, op);
-  };
-  cv(conv_in, cfg.in_channels);
-  cv(conv_out, conv_out.cin);
-  for (auto& v : down_res) for (auto& r : v) res(r);
-  for (auto& v : up_res) for (auto& r : v) res(r);
-  res(mid_res[0]); res(mid_res[1]);
-  for (auto& v : down_att) for (auto& a : v) att(a);
-  for (auto& v : up_att) for (auto& a : v) att(a);
-  att(mid_att);
-  for (int i = 0; i + 1 < cfg.num_blocks; ++i) { cv(down_samp[i], down_samp[i].cin); cv(up_samp[i], up_samp[i].cin); }
-  train_built = true;
-  return 0;
+// ------------------------------------------------------------------------------------------- plan
+// the dry walk of a training step: the forward, then the tape from the back, which also records the gradient ranges each entry writes
+static std::unique_ptr<dfh_unet::TrainRun> dry_train(dfh_unet* u, int B) {
+  auto r = std::make_unique<dfh_unet::TrainRun>(u, B, nullptr, true);
+  r->walk(nullptr, 0, nullptr, nullptr, 0, nullptr);
+  for (int i = (int)r->tape.size() - 1; i >= 0; --i) { r->cur_entry = i; r->tape[i](); }
+  return r;
 }
-
 // the training head has two slab regions: the main stream's and the side stream's (TrainRun::wgrad)
-static size_t head_bytes_for(int B, size_t partial) { return WorkspaceHead(nullptr, B, partial, 2).bytes; }
-
-size_t dfh_unet::plan_train(int B) {
-  build_train();
-  TrainRun r(this, B, nullptr, true);
-  r.walk(nullptr, 0, nullptr, nullptr, 0, nullptr);
-  for (auto it = r.tape.rbegin(); it != r.tape.rend(); ++it) (*it)();
-  const size_t partial = (r.partial_need + 255) & ~(size_t)255;
-  tplan_total = head_bytes_for(B, partial) + ((r.persist.peak + 255) & ~(size_t)255) + ((r.temp.peak + 255) & ~(size_t)255) + 256;
-  tplan_batch = B;
-  return tplan_total;
-}
+WorkspacePlan dfh_unet::plan_train(int B) { build_train(); return dry_train(this, B)->plan(2); }
 
 int dfh_unet::forward_train(const void* sample, int sample_bf16, const float* timestep, const void* ehs, int ehs_bf16, float* out,
                             int B, hipStream_t s) {
   // size the regions for this batch with a dry walk, then lay them out in the bound workspace
-  TrainRun plan(this, B, nullptr, true);
-  plan.walk(nullptr, 0, nullptr, nullptr, 0, nullptr);
-  for (int i = (int)plan.tape.size() - 1; i >= 0; --i) { plan.cur_entry = i; plan.tape[i](); }
-  const size_t partial = (plan.partial_need + 255) & ~(size_t)255;
-  const size_t persist_bytes = (plan.persist.peak + 255) & ~(size_t)255, gtemp_bytes = (plan.temp.peak + 255) & ~(size_t)255;
-  const size_t head = head_bytes_for(B, partial);
-  DFH_REQUIRE(head + persist_bytes + gtemp_bytes <= tws_bytes, "training workspace too small for this batch");
+  const auto plan = dry_train(this, B);
   delete tr;
   tr = new TrainRun(this, B, s, false);
   TrainRun& r = *tr;
-  const WorkspaceHead hd(tws, B, partial, 2);
-  r.bind_head(hd);
-  r.partial2 = hd.slab[1];
-  r.persist.base = tws + head;
-  r.temp.base = tws + head + persist_bytes;
-  (void)hipMemsetAsync(r.zero, 0, 256, s);
+  if (!r.bind(tws, tws_bytes, plan->plan(2))) return r.rc;
   r.walk(sample, sample_bf16, timestep, ehs, ehs_bf16, out);
-  r.writes = std::move(plan.writes);          // same walk, same tape: entry i of the dry tape is entry i of this one
-  DFH_REQUIRE(r.rc || r.tape.size() == plan.tape.size(), "dry and real tape differ");
+  r.writes = std::move(plan->writes);         // same walk, same tape: entry i of the dry tape is entry i of this one
+  DFH_REQUIRE(r.rc || r.tape.size() == plan->tape.size(), "dry and real tape differ");
   return r.rc;
 }
 
@@ -713,9 +629,7 @@ int dfh_unet::backward_finish(float* const* master_grads, int count, hipStream_t
   for (const PackOp& op : packs) {
     float* g = master_grads ? master_grads[op.param] : nullptr;
     if (!g) continue;
-    if (op.kind == PK_VEC) tab_unpack.add(g, TAB_UNPACK_VEC, (long)op.dst, op.N, 0, 0, op.geglu, overwrite, 0, 0, op.N);
-    else if (op.kind == PK_MAT) tab_unpack.add(g, TAB_UNPACK_MAT, (long)op.dst, op.N, op.K, op.ldw, op.row_off, op.col_off, op.geglu, overwrite, (long)op.N * op.K);
-    else tab_unpack.add(g, TAB_UNPACK_CONV, (long)op.dst, op.N, op.K, op.ldw, overwrite, op.col_off, 0, op.cin_pad, (long)op.N * op.K * 9);
+    tab_unpack.add(g, op, overwrite);
   }
   if (!grad_sumsq_out) return tab_unpack.launch(grad32, grad16, s);
   // the partials / ticket scratch are sized and zeroed when the output is registered (dfh_unet_grad_sumsq); the partial buffer only
@@ -739,64 +653,6 @@ int dfh_unet::backward_finish(float* const* master_grads, int count, hipStream_t
   return dfh::table_sq_reduce_launch(sq_partials, (long)tab_unpack.blocks, sq_scratch, grad_sumsq_out, s);
 }
 
-int dfh_unet::pack_train(const float* const* master, int count, hipStream_t s) {
-  DFH_REQUIRE(count == (int)params.size(), "parameter count mismatch");
-  DFH_REQUIRE(arena16t != nullptr, "training arenas not bound");
-  tab_packt.clear();
-  for (const TPackOp& op : tpacks) {
-    void* src = (void*)master[op.param];
-    DFH_REQUIRE(src != nullptr, "null master parameter: " + params[op.param].name);
-    if (op.conv) tab_packt.add(src, TAB_PACKT_CONV, (long)op.dst, op.N, op.K, op.ldt, 0, op.t_col_off, 0, op.o_pad, (long)op.N * op.K * 9);
-    else tab_packt.add(src, TAB_PACKT_MAT, (long)op.dst, op.N, op.K, op.ldt, op.t_row_off, op.t_col_off, op.geglu, 0, (long)op.N * op.K);
-  }
-  return tab_packt.launch(nullptr, arena16t, s);
-}
-
-// pack() + pack_train() of a training step in one pass over the masters: every weight that has exactly one plain and one transposed pack
-// goes through a PACK2 op (read once, written to arena16 AND arena16t); vectors, the few weights packed more than once and the
-// accumulating biases keep their own ops.  Same bytes in both arenas as the two separate calls (tests/test_gpu_train.py).
-int dfh_unet::pack_all(const float* const* master, int count, hipStream_t s) {
-  DFH_REQUIRE(count == (int)params.size(), "parameter count mismatch");
-  DFH_REQUIRE(arena16 && arena32 && arena16t, "arenas not bound");
-  std::vector<int> n_plain(params.size(), 0), n_tr(params.size(), 0), tr_at(params.size(), -1);
-  for (const PackOp& op : packs) if (op.kind != PK_VEC) ++n_plain[op.param];
-  for (size_t i = 0; i < tpacks.size(); ++i) { ++n_tr[tpacks[i].param]; tr_at[tpacks[i].param] = (int)i; }
-  tab_pack2.clear(); tab_pack_acc.clear(); tab_packt.clear();
-  for (const PackOp& op : packs) {
-    void* src = (void*)master[op.param];
-    DFH_REQUIRE(src != nullptr, "null master parameter: " + params[op.param].name);
-    if (op.kind == PK_VEC) {
-      (op.accumulate ? tab_pack_acc : tab_pack2).add(src, TAB_PACK_VEC, (long)op.dst, op.N, 0, 0, op.geglu, op.accumulate, 0, 0, op.N);
-      continue;
-    }
-    const bool twin = n_plain[op.param] == 1 && n_tr[op.param] == 1;
-    const TPackOp* t = twin ? &tpacks[tr_at[op.param]] : nullptr;
-    if (t && t->N == op.N && t->K == op.K && (t->conv != 0) == (op.kind != PK_MAT) && t->geglu == op.geglu) {
-      if (op.kind == PK_MAT)
-        tab_pack2.add2(src, TAB_PACK2_MAT, (long)op.dst, op.N, op.K, op.ldw, op.row_off, op.col_off, op.geglu, 0, (long)t->dst, t->ldt, t->t_row_off, t->t_col_off, 0);
-      else
-        tab_pack2.add2(src, TAB_PACK2_CONV, (long)op.dst, op.N, op.K, op.ldw, 0, op.col_off, 0, op.cin_pad, (long)t->dst, t->ldt, 0, t->t_col_off, t->o_pad);
-      n_tr[op.param] = -1;                      // its transposed pack is done
-    } else if (op.kind == PK_MAT) {
-      tab_pack2.add(src, TAB_PACK_MAT, (long)op.dst, op.N, op.K, op.ldw, op.row_off, op.col_off, op.geglu, 0, (long)op.N * op.K);
-    } else {
-      tab_pack2.add(src, TAB_PACK_CONV, (long)op.dst, op.N, op.K, op.ldw, 0, op.col_off, 0, op.cin_pad, (long)op.N * op.K * 9);
-    }
-  }
-  for (const TPackOp& op : tpacks) {            // transposed packs without a twin
-    if (n_tr[op.param] < 0) continue;
-    void* src = (void*)master[op.param];
-    if (op.conv) tab_packt.add(src, TAB_PACKT_CONV, (long)op.dst, op.N, op.K, op.ldt, 0, op.t_col_off, 0, op.o_pad, (long)op.N * op.K * 9);
-    else tab_packt.add(src, TAB_PACKT_MAT, (long)op.dst, op.N, op.K, op.ldt, op.t_row_off, op.t_col_off, op.geglu, 0, (long)op.N * op.K);
-  }
-  if (int rc = tab_pack2.launch(arena32, arena16, s, arena16t)) return rc;
-  if (int rc = tab_pack_acc.launch(arena32, arena16, s)) return rc;
-  if (int rc = tab_packt.launch(nullptr, arena16t, s)) return rc;
-  if (int rc = quantize_fp8(s)) return rc;
-  fold_valid = false; fold_dirty = true;
-  return 0;
-}
-
 // ------------------------------------------------------------------------------------------- C ABI
 extern "C" {
 
@@ -807,7 +663,7 @@ size_t dfh_unet_grad32_bytes(const dfh_unet* u) { DFH_BF16_ONLY_TRAINING_SIZE; r
 size_t dfh_unet_train_workspace_bytes(dfh_unet* u, int batch) {
   DFH_BF16_ONLY_TRAINING_SIZE;
   if (batch <= 0) return 0;
-  return u->plan_train(batch);
+  return u->plan_train(batch).total() + 256;
 }
 
 int dfh_unet_bind_train(dfh_unet* u, void* arena16t, void* grad16, void* grad32, void* workspace, size_t workspace_bytes,
@@ -817,7 +673,7 @@ int dfh_unet_bind_train(dfh_unet* u, void* arena16t, void* grad16, void* grad32,
   DFH_REQUIRE(((uintptr_t)arena16t | (uintptr_t)grad16 | (uintptr_t)grad32 | (uintptr_t)workspace) % 256 == 0,
               "buffers must be 256-byte aligned");
   DFH_REQUIRE(u->arena16 && u->arena32, "dfh_unet_bind must come first (weights are shared with the inference path)");
-  DFH_REQUIRE(workspace_bytes >= u->plan_train(max_batch), "workspace smaller than dfh_unet_train_workspace_bytes(max_batch)");
+  DFH_REQUIRE(workspace_bytes >= u->plan_train(max_batch).total() + 256, "workspace smaller than dfh_unet_train_workspace_bytes(max_batch)");
   u->arena16t = (bf16_t*)arena16t; u->grad16 = (float*)grad16; u->grad32 = (float*)grad32;
   u->tws = (char*)workspace; u->tws_bytes = workspace_bytes; u->train_max_batch = max_batch;
   return 0;

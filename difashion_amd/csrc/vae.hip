@@ -174,9 +174,7 @@ struct dfh_vae : ParamTable {
       Tensor g2 = talloc(H, W, r.cout);
       groupnorm(h1, r.n2w, r.n2b, 1, g2);
       {
-        GemmArgs g = conv_desc(g2.p, r.cout, H, W, H, W, 1, 0, r.w2, r.b2);
-        if (r.shortcut) { g.p_src[0] = x.p; g.p_c[0] = x.C; g.nplain = 1; }
-        else { g.resid = x.p; g.ld_res = r.cout; }
+        GemmArgs g = conv2_desc(g2.p, H, W, r.cout, r.w2, r.b2, r.shortcut, x.p, x.C, nullptr, 0);
         g.out = out.p;
         gemm(g);
       }
@@ -234,15 +232,8 @@ struct dfh_vae : ParamTable {
   // plan + layout shared by encode / decode
   int run(bool encode, const float* in, float* out, int B, int size, hipStream_t s, bool dry, size_t* need) {
     Run r(this, B, s, dry);
-    // region sizes come from a dry pass of the same walk (plan_* below)
-    const WorkspaceHead head(dry ? nullptr : ws, B, dry ? 0 : plan_partial);
-    r.bind_head(head);
-    const size_t head_bytes = head.bytes;
-    if (!dry) {
-      r.persist.base = ws + head_bytes; r.temp.base = ws + head_bytes + plan_persist;
-      if (head_bytes + plan_persist + plan_temp > ws_bytes) { dfh::set_error("VAE workspace too small"); return -1; }
-      (void)hipMemsetAsync(r.zero, 0, 256, s);
-    }
+    // region sizes come from a dry pass of the same walk (plan below)
+    if (!dry && !r.bind(ws, ws_bytes, plan)) return r.rc;
     const int nb = cfg.num_blocks, L = cfg.layers_per_block;
     if (encode) {
       Tensor x = r.palloc(size, size, e_in.cin);
@@ -275,15 +266,10 @@ struct dfh_vae : ParamTable {
       r.groupnorm(h, d_nw, d_nb, 1, g);
       r.conv(g, d_out, 0, true, out);                               // fp32 NCHW, out_channels padded to 4
     }
-    if (dry) {
-      plan_persist = (r.persist.peak + 255) & ~(size_t)255;
-      plan_temp = (r.temp.peak + 255) & ~(size_t)255;
-      plan_partial = (r.partial_need + 255) & ~(size_t)255;
-      if (need) *need = WorkspaceHead(nullptr, B, plan_partial).bytes + plan_persist + plan_temp;
-    }
+    if (dry) { plan = r.plan(); if (need) *need = plan.total(); }
     return r.rc;
   }
-  size_t plan_persist = 0, plan_temp = 0, plan_partial = 0;
+  WorkspacePlan plan;
 };
 
 // ------------------------------------------------------------------------------------------- C ABI

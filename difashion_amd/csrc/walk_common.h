@@ -1,6 +1,6 @@
-// What the three model walks share (the U-Net inference walk of unet_model.h, the training walk of unet_train.hip, the VAE of vae.hip):
-// the plain types, the parameter table with its packing plan (ParamTable), the layout of the head of a workspace (WorkspaceHead) and the
-// launch context of a walk (WalkBase: arenas, allocators, split-K slab planning, the descriptor fills every walk repeats).
+// What the three model walks share (the U-Net inference walk of unet_walk.hip, the training walk of unet_train.hip, the VAE of vae.hip):
+// the plain types, the parameter table with its packing plan (ParamTable), the layout of a workspace (WorkspaceHead, WorkspacePlan) and the
+// launch context of a walk (WalkBase: arenas, bounded allocators, split-K slab planning, the descriptor fills every walk repeats).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -20,7 +20,8 @@ namespace dfhm {
 struct Mat { size_t off = 0; int N = 0, K = 0; };    // bf16 [N][K] at arena16 + off (elements)
 struct Vec { size_t off = 0; int N = 0; };           // fp32 [N] at arena32 + off (elements)
 
-enum PackKind { PK_VEC = 0, PK_MAT = 1, PK_CONV3 = 2 };
+enum PackKind { PK_VEC = 0, PK_MAT = 1, PK_CONV3 = 2 };      // in the order of TabKind's PACK_* and UNPACK_* triples (OpTable::add)
+struct TPackOp;
 struct PackOp {
   int param, kind;
   size_t dst;
@@ -35,11 +36,16 @@ struct Tensor {
   const float* gst = nullptr; int gst_cpg = 0, gst_chunks = 0;
 };
 
+// A region of a workspace handed out front to back.  A planning (dry) walk leaves it unbounded and reads `peak`; WalkBase::bind gives the
+// region of a real walk its planned size (cap) and the walk's error slot (rc): an allocation past the cap is refused there, and with rc
+// set the walk launches nothing further.
 struct Bump {
   char* base = nullptr; size_t cap = 0, off = 0, peak = 0;
+  const char* name = ""; int* rc = nullptr;          // rc != null: bounded by cap
   void* alloc(size_t bytes) {
     off = (off + 255) & ~(size_t)255;
-    char* p = base + off;
+    if (rc && off + bytes > cap) { dfh::set_error(std::string("workspace region too small: ") + name); *rc = -1; return base; }
+    char* p = (char*)((uintptr_t)base + off);        // (planning arithmetic runs on a null base: WorkspaceHead)
     off += bytes;
     if (off > peak) peak = off;
     return p;
@@ -57,6 +63,15 @@ struct OpTable {
     blocks += dfh::tab_blocks(kind, N, K);
     host.push_back(op);
   }
+  // a PackOp as the table op of its kind.  unpack < 0: the pack (master -> arena); 0 / 1: the un-pack of its gradient (arena -> master),
+  // added onto / overwriting the master's
+  void add(void* src, const PackOp& op, int unpack = -1) {
+    const int k = unpack < 0 ? TAB_PACK_VEC : TAB_UNPACK_VEC, flag = unpack < 0 ? op.accumulate : unpack;
+    if (op.kind == PK_VEC) add(src, k + PK_VEC, (long)op.dst, op.N, 0, 0, op.geglu, flag, 0, 0, op.N);
+    else if (op.kind == PK_MAT) add(src, k + PK_MAT, (long)op.dst, op.N, op.K, op.ldw, op.row_off, op.col_off, op.geglu, unpack < 0 ? 0 : unpack, (long)op.N * op.K);
+    else add(src, k + PK_CONV3, (long)op.dst, op.N, op.K, op.ldw, unpack < 0 ? 0 : unpack, op.col_off, 0, op.cin_pad, (long)op.N * op.K * 9);
+  }
+  void add(void* src, const TPackOp& op);            // the transposed pack of the training path (unet_model.h, where TPackOp lives)
   // a PACK2 op: the plain pack (dst .. p3 as in add) and the transposed pack (dst2, ld2, q0 = t_row_off, q1 = t_col_off, q3 = o_pad) of one master
   void add2(void* master, int kind, long dst, int N, int K, int ld, int p0, int p1, int p2, int p3, long dst2, int ld2, int q0, int q1, int q3) {
     add(master, kind, dst, N, K, ld, p0, p1, p2, p3, 0);
@@ -132,9 +147,7 @@ struct ParamTable : dfh::ParamList {
     for (const PackOp& op : packs) {
       void* src = (void*)master[op.param];
       DFH_REQUIRE(src != nullptr, "null master parameter: " + params[op.param].name);
-      if (op.kind == PK_VEC) (op.accumulate ? tab_pack_acc : tab_pack).add(src, TAB_PACK_VEC, (long)op.dst, op.N, 0, 0, op.geglu, op.accumulate, 0, 0, op.N);
-      else if (op.kind == PK_MAT) tab_pack.add(src, TAB_PACK_MAT, (long)op.dst, op.N, op.K, op.ldw, op.row_off, op.col_off, op.geglu, 0, (long)op.N * op.K);
-      else tab_pack.add(src, TAB_PACK_CONV, (long)op.dst, op.N, op.K, op.ldw, 0, op.col_off, 0, op.cin_pad, (long)op.N * op.K * 9);
+      (op.kind == PK_VEC && op.accumulate ? tab_pack_acc : tab_pack).add(src, op);
     }
     if (int rc = tab_pack.launch(arena32, arena16, s)) return rc;
     return tab_pack_acc.launch(arena32, arena16, s);
@@ -161,6 +174,13 @@ struct WorkspaceHead {
   }
 };
 
+// What a planning (dry) walk found a workspace needs behind its head: the two allocator regions and the split-K slab bytes (each rounded
+// to 256), for which batch, and how many slab regions the head holds (2: the training walk's side stream has its own).
+struct WorkspacePlan {
+  size_t persist = 0, temp = 0, slab = 0; int batch = 0, nslab = 1;
+  size_t total() const { return batch ? WorkspaceHead(nullptr, batch, slab, nslab).bytes + persist + temp : 0; }
+};
+
 // Launch context of one walk over a model: the batch, the stream, dry (planning: allocate and size, launch nothing), the first error, the
 // two bump allocators, and the split-K slab region with the size the dry run found it needs.
 struct WalkBase {
@@ -168,10 +188,33 @@ struct WalkBase {
   int B; hipStream_t s; bool dry;
   Bump persist, temp; size_t partial_need = 0;
   float* partial = nullptr; size_t partial_cap = 0;
+  float* partial2 = nullptr;                   // the second slab region of a two-slab head (else null)
   float* gn_partial = nullptr; bf16_t* zero = nullptr;
   int rc = 0;
-  WalkBase(const ParamTable& pt_, int groups_, int B_, hipStream_t s_, bool dry_) : pt(pt_), groups(groups_), B(B_), s(s_), dry(dry_) {}
-  void bind_head(const WorkspaceHead& h) { zero = h.zero; gn_partial = h.gn_partial; partial = h.slab[0]; partial_cap = h.slab_bytes; }
+  WalkBase(const ParamTable& pt_, int groups_, int B_, hipStream_t s_, bool dry_) : pt(pt_), groups(groups_), B(B_), s(s_), dry(dry_) {
+    // a planning walk hands out addresses that are never dereferenced: from a made-up base, so that offsets from them are defined
+    if (dry) persist.base = temp.base = (char*)(uintptr_t)(1 << 20);
+  }
+  WalkBase(const WalkBase&) = delete;          // the allocators of a bound walk point at its rc
+
+  // what this (dry) walk needs
+  WorkspacePlan plan(int nslab = 1) const {
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    WorkspacePlan p; p.persist = up(persist.peak); p.temp = up(temp.peak); p.slab = up(partial_need); p.batch = B; p.nslab = nslab;
+    return p;
+  }
+  // A real walk over [base, base + bytes): head | persist | temp as planned, both allocators bounded by their planned sizes, the zero
+  // page cleared on the stream.  Refuses (rc, false) a plan for another batch and a workspace smaller than the plan.
+  bool bind(char* base, size_t bytes, const WorkspacePlan& p) {
+    if (B != p.batch) { dfh::set_error("walk batch differs from the planned batch"); rc = -1; return false; }
+    if (p.total() > bytes) { dfh::set_error("workspace too small"); rc = -1; return false; }
+    const WorkspaceHead h(base, B, p.slab, p.nslab);
+    zero = h.zero; gn_partial = h.gn_partial; partial = h.slab[0]; partial2 = h.slab[1]; partial_cap = h.slab_bytes;
+    persist = Bump{base + h.bytes, p.persist, 0, 0, "persist", &rc};
+    temp = Bump{base + h.bytes + p.persist, p.temp, 0, 0, "temp", &rc};
+    if (hipMemsetAsync(zero, 0, 256, s) != hipSuccess) { dfh::set_error("hipMemsetAsync failed (zero page)"); rc = -2; }
+    return rc == 0;
+  }
 
   bf16_t* w16(const Mat& m) const { return pt.arena16 + m.off; }
   float* v32(const Vec& v) const { return pt.arena32 + v.off; }
@@ -214,6 +257,21 @@ struct WalkBase {
   GemmArgs conv_desc(const bf16_t* src, int C, int Hin, int Win, int Hout, int Wout, int stride, int ups, const Mat& W, const Vec& bias) const {
     GemmArgs g = conv_desc(src, C, Hin, Win, Hout, Wout, stride, ups, W.N);
     g.W = w16(W); g.ldw = W.K; g.bias = v32(bias);
+    return g;
+  }
+  // The second conv of a resnet over the normalised g2 ([cout] channels).  The block input x0 (| x1: the channel concatenation) rides along
+  // as K segments under the 1x1-shortcut columns of w2 -- or, without a shortcut, is the residual.  g2 null: the shortcut GEMM alone, no
+  // bias (the Winograd walk, whose output transform adds it to the conv)
+  GemmArgs conv2_desc(const bf16_t* g2, int H, int W, int cout, const Mat& w2, const Vec& b2, bool shortcut, const bf16_t* x0, int c0,
+                      const bf16_t* x1, int c1) const {
+    GemmArgs g = g2 ? conv_desc(g2, cout, H, W, H, W, 1, 0, w2, b2) : base(B * H * W, cout);
+    if (!g2) { g.W = w16(w2) + 9 * cout; g.ldw = w2.K; }
+    if (shortcut) {
+      g.p_src[0] = x0; g.p_c[0] = c0; g.nplain = 1;
+      if (x1) { g.p_src[1] = x1; g.p_c[1] = c1; g.nplain = 2; }
+    } else {
+      g.resid = x0; g.ld_res = cout;
+    }
     return g;
   }
   // GroupNorm (+SiLU) over x0 (| x1: the channel concatenation of the two) into out; statistics inputs / outputs are the caller's

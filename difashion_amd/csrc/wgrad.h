@@ -1,6 +1,8 @@
 #pragma once
 #include "dfh_common.h"
+#include "gemm.h"
 #include <algorithm>
+#include <cstring>
 
 struct WgradArgs {
   // forward A operand, same K-segment description as GemmArgs
@@ -22,6 +24,16 @@ struct WgradArgs {
   // the 3x3-tap position (tap_py + (s >> 1), tap_px + (s & 1)); dY = the plane's rows of the output gradient (gathered phase-major);
   // dW = the gradient of the plane's SUMMED weights [N][4 * conv_c] (un-folded onto the 3x3 taps by ups_phase_unfold)
   int tap2, tap_py, tap_px;
+
+  WgradArgs() = default;
+  // the A operand (K segments), M, N, row length of the weights and zero page of a forward launch; everything else zero
+  explicit WgradArgs(const GemmArgs& f) {
+    std::memset(this, 0, sizeof(*this));
+    conv_src = f.conv_src; conv_c = f.conv_c; ntaps = f.ntaps;
+    Hin = f.Hin; Win = f.Win; Hout = f.Hout; Wout = f.Wout; stride = f.stride; ups = f.ups;
+    p_src[0] = f.p_src[0]; p_src[1] = f.p_src[1]; p_c[0] = f.p_c[0]; p_c[1] = f.p_c[1]; nplain = f.nplain;
+    zero = f.zero; M = f.M; N = f.N; ldw = f.ldw;
+  }
 };
 
 namespace dfh {

@@ -7,7 +7,9 @@
 
 A run is the smallest config of tests/test_gpu_unet.py with attention at more than one level (GLUE_CFG): one bf16 forward at B = 2, one
 forward with the dup-tail hint at B = 4 / dup = 1, one forward after enable_fp8(), one training step (forward + backward) -- and, because
-GLUE_CFG's first block is 32 wide and has no e4m3 copy, the dup-tail forward of TINY after enable_fp8().  It writes the GEMM plan dump
+GLUE_CFG's first block is 32 wide and has no e4m3 copy, the dup-tail forward of TINY after enable_fp8().  Two more legs cover the run
+cache (a GLUE_CFG forward at B = 2 through prepare_run over three timesteps) and the VAE (the smallest of tests/test_gpu_vae.py: encode
+at B = 3 / 32x32, decode of its latents).  It writes the GEMM plan dump
 (DFH_GEMM_PLAN_DUMP), the census of every leg and the sha256 of every output tensor; gradients of vectors (biases, norm scales) are
 summed with float atomics and are kept as values instead (compared as tests/test_gpu_train.py does: rtol 1e-5, atol 1e-6 of the largest)."""
 import hashlib
@@ -58,6 +60,29 @@ def run(out_dir):
     mt = hip_unet(unet_ref.TINY, unet_ref.init_params(unet_ref.TINY, seed=5, w_std=0.05, affine_jitter=0.1), max_batch=4)
     mt.enable_fp8()
     forward("tiny_fp8_dup_tail_B4_dup1", mt, unet_ref.TINY, 4, dup=1)
+
+    m = hip_unet(GLUE_CFG, params, max_batch=4)
+    x, e = (t.to(DEV) for t in inputs(GLUE_CFG, 2, 23))
+    steps = [981, 501, 21]
+    with torch.no_grad():
+        m(x, steps[0], e)                                  # packs and derives the weights
+        m.prepare_run(e, steps)
+        _lib.census_reset()
+        outs = {f"out_t{t}": sha(m(x, t, e).sample) for t in steps}
+        torch.cuda.synchronize()
+        rec["run_cache_B2"] = {"census": {k: v for k, v in _lib.census().items() if v}, "sha256": {"out": outs[f"out_t{steps[-1]}"], **outs}}
+        m.end_run()
+
+    from oracle import vae_ref
+    from tests.test_gpu_vae import hip_vae
+    v = hip_vae(vae_ref.TINY_VAE, vae_ref.init_params(vae_ref.TINY_VAE, seed=2, w_std=0.05, affine_jitter=0.1))
+    img = (torch.rand(3, 3, 32, 32, generator=torch.Generator().manual_seed(3)) * 2 - 1).to(DEV)
+    with torch.no_grad():
+        _lib.census_reset()
+        dist = v.encode(img).latent_dist
+        dec = v.decode(dist.mean, return_dict=False)[0]
+    torch.cuda.synchronize()
+    rec["vae_tiny_B3"] = {"census": {k: v_ for k, v_ in _lib.census().items() if v_}, "sha256": {"out": sha(dec), "moments": sha(dist.parameters)}}
 
     m = hip_unet(GLUE_CFG, params, max_batch=4).train()
     x, e = inputs(GLUE_CFG, 3, 11)
