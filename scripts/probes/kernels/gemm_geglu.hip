@@ -146,16 +146,16 @@ __global__ __launch_bounds__(NWV * 64, 1) void gemm_geglu_rows_kernel(const Gemm
       const unsigned char* Bs = As + A_BYTES;
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        bf16x8_t af[FM], bfr[FN];
+        h16x8_t af[FM], bfr[FN];
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
           const int row = wm * TM + i * 16 + fr;
-          af[i] = *(const bf16x8_t*)(As + row * 128 + (((ks * 4 + fg) ^ ((row >> 1) & 7)) << 4));
+          af[i] = *(const h16x8_t*)(As + row * 128 + (((ks * 4 + fg) ^ ((row >> 1) & 7)) << 4));
         }
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
           const int row = wn * TN + j * 16 + fr;
-          bfr[j] = *(const bf16x8_t*)(Bs + row * 128 + (((ks * 4 + fg) ^ ((row >> 1) & 7)) << 4));
+          bfr[j] = *(const h16x8_t*)(Bs + row * 128 + (((ks * 4 + fg) ^ ((row >> 1) & 7)) << 4));
         }
 #pragma unroll
         for (int i = 0; i < FM; ++i)

@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void gemm_halo_kernel(const GemmArgs a) {
       asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(a0));
 #define HROW(i, ar)                                                                                                   \
       _Pragma("unroll") for (int j = 0; j < FN; ++j)                                                                  \
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, b[j]), __builtin_bit_cast(bf16x8_t, ar), \
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(h16x8_t, b[j]), __builtin_bit_cast(h16x8_t, ar), \
                                                             acc[i][j], 0, 0, 0);
 #define HNEXT(rd, i, wt) { const unsigned ad = a_addr(i, tbase); HRD(rd, ad, 0); } asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(wt));
       HROW(0, a0) HNEXT(a2, 2, a1)

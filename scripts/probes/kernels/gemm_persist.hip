@@ -195,11 +195,11 @@ __global__ __launch_bounds__(PNWV * 64, 2) void gemm_persist_kernel(const GemmAr
     const unsigned char* Bs_ = As_ + P_A_BYTES;                                                                                               \
     _Pragma("unroll") for (int i = 0; i < PFM; ++i) {                                                                                         \
       const int row = wm * PTM + i * 16 + fr;                                                                                                 \
-      AF[i] = *(const bf16x8_t*)(As_ + row * 128 + ((((KS) * 4 + fg) ^ ((row >> 1) & 7)) << 4));                                               \
+      AF[i] = *(const h16x8_t*)(As_ + row * 128 + ((((KS) * 4 + fg) ^ ((row >> 1) & 7)) << 4));                                               \
     }                                                                                                                                         \
     _Pragma("unroll") for (int jj = 0; jj < PFN; ++jj) {                                                                                      \
       const int row = wn * PTN + jj * 16 + fr;                                                                                                \
-      BF[jj] = *(const bf16x8_t*)(Bs_ + row * 128 + ((((KS) * 4 + fg) ^ ((row >> 1) & 7)) << 4));                                              \
+      BF[jj] = *(const h16x8_t*)(Bs_ + row * 128 + ((((KS) * 4 + fg) ^ ((row >> 1) & 7)) << 4));                                              \
     }                                                                                                                                         \
   } while (0)
 #define DFH_MFMAS(AF, BF)                                                                                                                      \
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(PNWV * 64, 2) void gemm_persist_kernel(const GemmAr
   int t = 0, buf = 0;
   int m0 = 0, n0 = 0, nt_ = 0, tb_ = 0;
   bool part2 = false, tr = false;
-  bf16x8_t afA[PFM], bfA[PFN], afB[PFM], bfB[PFN];      // fragment sets of the two halves of a k-step: one is read while the other feeds the MFMAs
+  h16x8_t afA[PFM], bfA[PFN], afB[PFM], bfB[PFN];      // fragment sets of the two halves of a k-step: one is read while the other feeds the MFMAs
 
   // pipeline fill, once per launch: all three ring slots, then the first half-step's fragments
   if (G > 0) DFH_ISSUE_STAGE();

@@ -201,11 +201,11 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(const GemmArgs a) {
       const unsigned char* S = smem + buf * STAGE;
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        bf16x8_t xf[2], wf[NCB];
+        h16x8_t xf[2], wf[NCB];
 #pragma unroll
-        for (int pj = 0; pj < 2; ++pj) xf[pj] = *(const bf16x8_t*)(S + x_row + pj * 32 * 128 + foff[ks]);
+        for (int pj = 0; pj < 2; ++pj) xf[pj] = *(const h16x8_t*)(S + x_row + pj * 32 * 128 + foff[ks]);
 #pragma unroll
-        for (int ci = 0; ci < NCB; ++ci) wf[ci] = *(const bf16x8_t*)(S + w_row + ci * 32 * 128 + foff[ks]);
+        for (int ci = 0; ci < NCB; ++ci) wf[ci] = *(const h16x8_t*)(S + w_row + ci * 32 * 128 + foff[ks]);
 #pragma unroll
         for (int ci = 0; ci < NCB; ++ci)
 #pragma unroll

@@ -98,7 +98,7 @@ DFH_DEVICE void fence() { __builtin_amdgcn_sched_barrier(0); }
 struct MlpState {
   f32x16_t d1[2][2];          // [chunk parity][tile]: first-GEMM accumulators (VGPRs: the GEGLU reads them)
   f32x16_t d2[CT];            // output accumulators (AGPRs)
-  bf16x8_t xf[KS1];           // X fragments (AGPRs)
+  h16x8_t xf[KS1];           // X fragments (AGPRs)
   uint32_t hreg[2][4];        // B operand of the second GEMM: the gated hidden units of the previous chunk, two 16-unit tiles
   float rstd, ms;             // LayerNorm statistics of this lane's token: rstd, -mean * rstd
   GeluK gk;
@@ -196,9 +196,9 @@ DFH_DEVICE void mlp_iter(MlpState& st, const unsigned char* smem, const unsigned
     asm volatile("" : "+s"(base));
     return *(gptr16_t)(base + lane16);
   };
-  bf16x8_t fr[WIN];
+  h16x8_t fr[WIN];
 #pragma unroll
-  for (int i = 0; i < WIN; ++i) fr[i] = *(const bf16x8_t*)(fl + g1_off(i));
+  for (int i = 0; i < WIN; ++i) fr[i] = *(const h16x8_t*)(fl + g1_off(i));
   if (PREV) pair_consts<PP>(st, smem, vec_lane, 0);
   fence();
 #pragma unroll
@@ -213,8 +213,8 @@ DFH_DEVICE void mlp_iter(MlpState& st, const unsigned char* smem, const unsigned
     }
     fence();
     // refill the window: the rest of this GEMM's fragments, then the first ones of the second GEMM
-    if (i + WIN < 40) fr[i % WIN] = *(const bf16x8_t*)(fl + g1_off(i + WIN));
-    else if (PREV) fr[i % WIN] = *(const bf16x8_t*)(fl + g2_off(i + WIN - 40));
+    if (i + WIN < 40) fr[i % WIN] = *(const h16x8_t*)(fl + g1_off(i + WIN));
+    else if (PREV) fr[i % WIN] = *(const h16x8_t*)(fl + g2_off(i + WIN - 40));
     if (PREV) geglu_slice<PP>(st, smem, vec_lane, i / 5, i % 5);
     // pieces 0..7: requested behind MFMAs 0..7, written to LDS behind MFMAs 16..23; pieces 8..15: requested there, written behind 32..39
     if (i < 8) sg[i] = stage_ld(i);
@@ -231,9 +231,9 @@ DFH_DEVICE void mlp_iter(MlpState& st, const unsigned char* smem, const unsigned
     for (int j = 0; j < 20; ++j) {
       const int t2 = j / CT, ct = j % CT;
       const uint4 hb = uint4{st.hreg[t2][0], st.hreg[t2][1], st.hreg[t2][2], st.hreg[t2][3]};
-      asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(st.d2[ct]) : "v"(fr[(40 + j) % WIN]), "v"(__builtin_bit_cast(bf16x8_t, hb)));
+      asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(st.d2[ct]) : "v"(fr[(40 + j) % WIN]), "v"(__builtin_bit_cast(h16x8_t, hb)));
         fence();
-      if (j + WIN < 20) fr[(40 + j) % WIN] = *(const bf16x8_t*)(fl + g2_off(j + WIN));
+      if (j + WIN < 20) fr[(40 + j) % WIN] = *(const h16x8_t*)(fl + g2_off(j + WIN));
       fence();
     }
   }
@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const MlpArgs a) {
   {
     const bf16_t* xr = a.x + (long)m * MC + 8 * h;
 #pragma unroll
-    for (int ks = 0; ks < KS1; ++ks) st.xf[ks] = *(const bf16x8_t*)(xr + 16 * ks);
+    for (int ks = 0; ks < KS1; ++ks) st.xf[ks] = *(const h16x8_t*)(xr + 16 * ks);
   }
   // LayerNorm statistics of the token from its producer's per-column-tile records (gemm.h ln_row_stats)
   {

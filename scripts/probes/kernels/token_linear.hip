@@ -34,7 +34,7 @@ __global__ __launch_bounds__(512, 2) void token_linear_kernel(const TokLinArgs a
   {
     const bf16_t* xr = a.x + (long)m * MC + 8 * g;
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) st.xf[ks] = *(const bf16x8_t*)(xr + 32 * ks);
+    for (int ks = 0; ks < KS; ++ks) st.xf[ks] = *(const h16x8_t*)(xr + 32 * ks);
   }
   st.rstd = 1.f; st.ms = 0.f;
   if (a.ln_stat) {

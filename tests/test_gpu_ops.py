@@ -618,6 +618,26 @@ def test_attention_x32_running_max_moves(d, gain):
     gu.assert_close_bf16(o, ref, f"x32 rescale d={d} gain={gain}", rel=1.5e-2, max_rel=6e-2 if gain == 1.0 else 0.12)
 
 
+@pytest.mark.parametrize("d", [40, 80])
+def test_attention_x32_poisoned_fast_pass_is_repeated(d):
+    """One key of a tile after the first scores more than 100 log2 units above everything the first tile held: the fast pass's
+    unchecked exp leaves a denominator of >= 2^100, the workgroup raises its poison flag and repeats the pass in the exact
+    deferred-max form (attention_x32.hip, `pass`).  The precondition is checked on the CPU in float64 before the kernel runs."""
+    B, heads, N = 1, 2, 512
+    Cc = d * heads
+    q, k, v = bf(rnd(B, N, Cc, seed=63)), bf(rnd(B, N, Cc, seed=64)), bf(rnd(B, N, Cc, seed=65))
+    k[:, 300] = q[:, 7] * 16.0         # key 300 (tile 4) aligned with query 7, both heads
+    s7 = torch.einsum("hd,nhd->hn", q[0, 7].double().cpu().view(heads, d), k[0].double().cpu().view(N, heads, d)) \
+        * d ** -0.5 * math.log2(math.e)
+    jump = s7[:, 300] - s7[:, :64].max(dim=1).values
+    assert (jump > 100).all(), f"planted score only {jump.tolist()} log2 units above tile 0: the fast pass would not be poisoned"
+    o = _attention(q, k, v, heads)
+    assert torch.isfinite(o.float()).all()
+    qh, kh, vh = (t.float().view(B, -1, heads, d).transpose(1, 2) for t in (q, k, v))
+    ref = F.scaled_dot_product_attention(qh, kh, vh).transpose(1, 2).reshape(B, N, Cc)
+    gu.assert_close_bf16(o, ref, f"x32 poison re-run d={d}", rel=1.5e-2, max_rel=0.12)
+
+
 def test_attention_x32_matches_the_16x16_kernel_lse():
     """Training reads the forward's log-sum-exp: both kernels must report the same one."""
     B, heads, d, N = 1, 2, 40, 512
