@@ -16,7 +16,8 @@ from .unet import UNet2DConditionModel, UNet2DConditionOutput
 from .vae import AutoencoderKL
 from .clip import CLIPTextModel, CLIPTextModelOutput, CLIPTextModelWithProjection
 from .clip_vision import CLIPVisionModelOutput, CLIPVisionModelWithProjection
-from .evalscores import CLIPScore, CompatibilityEvaluator, FashionEvaluator, candidate_cosine, pair_cosine
+from .image_processor import CLIPImageProcessor
+from .evalscores import CLIPScore, CompatibilityEvaluator, FashionEvaluator, candidate_cosine, extract_image_features, pair_cosine
 from .difashion import DiFashion
 
 __all__ = [
@@ -24,5 +25,5 @@ __all__ = [
     "MutualEncoder", "OutfitSampler", "sample_outfits", "train_forward", "guidance_plan", "sampling_tables", "training_tables",
     "FusedAdamW", "EMAModel", "clip_grad_norm_", "train_step", "AutoencoderKL", "CLIPTextModel", "DiFashion",
     "CLIPVisionModelWithProjection", "CLIPVisionModelOutput", "CLIPTextModelWithProjection", "CLIPTextModelOutput", "CLIPScore",
-    "CompatibilityEvaluator", "FashionEvaluator", "pair_cosine", "candidate_cosine",
+    "CompatibilityEvaluator", "FashionEvaluator", "pair_cosine", "candidate_cosine", "CLIPImageProcessor", "extract_image_features",
 ]

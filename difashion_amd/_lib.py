@@ -63,6 +63,10 @@ class CLIPVisionConfigC(C.Structure):
                 ("hidden_act", C.c_int), ("layer_norm_eps", C.c_float)]
 
 
+class ImgProcConfigC(C.Structure):
+    _fields_ = [("shortest_edge", C.c_int), ("crop_height", C.c_int), ("crop_width", C.c_int), ("resample", C.c_int)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [
         ("conv_src", C.c_void_p), ("conv_c", C.c_int), ("conv", C.c_int),
@@ -169,6 +173,19 @@ SIGNATURES = {
     "dfh_clipv_workspace_bytes": (_sz, [_vp, _i]),
     "dfh_clipv_encode": (_i, [_vp, C.POINTER(_vp), _i, _vp, _i, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
     "dfh_clipv_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "dfh_imgproc_create": (_i, [C.POINTER(ImgProcConfigC), _i, _i, _i, C.POINTER(_vp)]),
+    "dfh_imgproc_destroy": (None, [_vp]),
+    "dfh_imgproc_resized_height": (_i, [_vp]),
+    "dfh_imgproc_resized_width": (_i, [_vp]),
+    "dfh_imgproc_out_height": (_i, [_vp]),
+    "dfh_imgproc_out_width": (_i, [_vp]),
+    "dfh_imgproc_crop_top": (_i, [_vp]),
+    "dfh_imgproc_crop_left": (_i, [_vp]),
+    "dfh_imgproc_ksize_x": (_i, [_vp]),
+    "dfh_imgproc_ksize_y": (_i, [_vp]),
+    "dfh_imgproc_table_bytes": (_sz, [_vp]),
+    "dfh_imgproc_fill_tables": (_i, [_vp, _vp, _sz]),
+    "dfh_imgproc_run": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "dfh_vae_create": (_i, [C.POINTER(VAEConfigC), C.POINTER(_vp)]),
     "dfh_vae_destroy": (None, [_vp]),
     "dfh_vae_num_params": (_i, [_vp]),
@@ -280,7 +297,9 @@ SIGNATURES = {
 }
 _NO_STATUS = {"dfh_abi_version", "dfh_census_count", "dfh_unet_num_params", "dfh_unet_param_ndim", "dfh_unet_param_dim", "dfh_vae_num_params",
               "dfh_vae_param_ndim", "dfh_vae_param_dim", "dfh_clip_num_params", "dfh_clip_param_ndim", "dfh_clip_param_dim",
-              "dfh_clipv_num_params", "dfh_clipv_param_ndim", "dfh_clipv_param_dim"}
+              "dfh_clipv_num_params", "dfh_clipv_param_ndim", "dfh_clipv_param_dim",
+              "dfh_imgproc_resized_height", "dfh_imgproc_resized_width", "dfh_imgproc_out_height", "dfh_imgproc_out_width", "dfh_imgproc_crop_top",
+              "dfh_imgproc_crop_left", "dfh_imgproc_ksize_x", "dfh_imgproc_ksize_y"}
 
 _lib = None
 _UNBOUND = set()

@@ -6,7 +6,8 @@ What the reference's evaluation scripts require of the image side of their OpenC
 This class is that shared feature extractor under the architecture and the state-dict key names of
 ``transformers.CLIPVisionModelWithProjection`` (``vision_model.*`` with transformers' own ``pre_layrnorm`` spelling,
 ``visual_projection.weight``); ``open_clip`` checkpoints must be exported under those names first.  Resizing /
-normalising the images and the metrics computed from the embeddings stay with the caller.
+normalising the images is ``CLIPImageProcessor`` (image_processor.py, row f7); the metrics computed from the embeddings are row f6
+(evalscores.py).
 
 All arithmetic runs in the kernel library (``dfh_clipv_encode``, csrc/clip_vision.hip) in fp32 on the fp32 matrix instruction, in
 both storage builds.  The fp32 ``nn.Parameter``s are read in place (no packed copy).  No PyTorch / CPU fallback.

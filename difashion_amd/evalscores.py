@@ -78,6 +78,25 @@ def candidate_cosine(gen: torch.Tensor, table: torch.Tensor, candidates: torch.T
     return sims, preds
 
 
+@torch.no_grad()
+def extract_image_features(image_model, processor, images, batch_size: int = 200) -> torch.Tensor:
+    """The reference's ``extract_cnn_features`` (Evaluation/extract_hist_embs.py:81-103) without the DataLoader worker: ``processor``
+    (``CLIPImageProcessor``) then ``image_model.encode_image`` batch by batch -> [N, projection_dim] fp32 on the model's device.
+    ``images``: a device tensor in one of the processor's forms, or a sequence of PIL images / HWC uint8 arrays."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be positive, got {batch_size}")
+    n = images.shape[0] if isinstance(images, torch.Tensor) else len(images)
+    if n < 1:
+        raise ValueError("images holds no image")
+    feats = []
+    for i in range(0, n, batch_size):
+        batch = images[i:i + batch_size]
+        pixels = processor(images=batch if isinstance(batch, torch.Tensor) else list(batch), return_tensors="pt",
+                           device=image_model.device).pixel_values
+        feats.append(image_model.encode_image(pixels))
+    return torch.cat(feats)
+
+
 class FashionEvaluator(nn.Module):
     """compatibility_net.py's class under its own state-dict names (``feat_layer.*``, ``emb_layer.{0,1,4,5,8,9,12,13}.*``,
     ``eval_layer.{0,1,4,5,8,9,12}.*``), inference only: Dropout is the identity, every outfit of a call runs together."""

@@ -319,7 +319,7 @@ int dfh_compat_pred_score(const float* const* params, int count, const float* ou
  * library's own spelling).  fp32 end to end in both storage builds (csrc/clip_vision.hip): patch embedding as im2col + GEMM, the
  * linears and LayerNorms of the text tower, and a bidirectional attention kernel that streams K / V through LDS in key tiles
  * (online softmax), so the sequence length is not bounded by LDS.  Master parameters are read in place: no arenas, no pack step.
- * Image resize / normalisation and the metrics computed from the embeddings stay outside the library. */
+ * Image resize / normalisation is the dfh_imgproc family below (row f7); the metrics computed from the embeddings are row f6. */
 typedef struct dfh_clipv_config {
   int hidden_size;                 /* 1024 (ViT-L/14) / 1280 (ViT-H/14) */
   int intermediate_size;           /* 4096 / 5120 */
@@ -356,6 +356,47 @@ int dfh_clipv_encode(dfh_clipv* c, const float* const* master_params, int count,
  * mask.  qkv [batch * T][3 * heads * head_dim] fp32 (q | k | v, heads contiguous inside each), out [batch * T][heads * head_dim];
  * head_dim a multiple of 4 up to 128, any T >= 1. */
 int dfh_clipv_attention(const float* qkv, float* out, int batch, int T, int heads, int head_dim, float scale, void* stream);
+
+/* ------------------------------------------------------------------ CLIP image preprocessing
+ * Replaces (arithmetic) open_clip's / transformers' image transform in front of the tower (Evaluation/extract_hist_embs.py:83-100,
+ * evaluate_gor.py:193-236): PIL's antialiased 8-bit resize (horizontal pass, then vertical pass, integer arithmetic over 22-bit
+ * coefficient tables computed in double, the intermediate image clipped to uint8), a floor-centred crop and a 3 x 256 fp32 lookup
+ * ((v / 255 - mean) / std).  csrc/image_processor.hip: ONE launch does all three, the intermediate image lives in LDS; integers and
+ * fp32 only, the same in both storage builds, no atomics (reruns are bit-identical).
+ * A plan is host-only: the geometry of one (input size, sheet) under one config, and the coefficient tables the launch reads. */
+typedef struct dfh_imgproc_config {
+  int shortest_edge;               /* 224: the shorter edge goes here, the other to (int)(shortest_edge * long / short) */
+  int crop_height;                 /* 224; 0 (with crop_width 0): no crop, the output is the resized image */
+  int crop_width;                  /* 224; top = (h - crop_height) / 2, left = (w - crop_width) / 2 (transformers' rounding) */
+  int resample;                    /* PIL numbering: 3 bicubic (a = -0.5) / 2 bilinear */
+} dfh_imgproc_config;
+typedef struct dfh_imgproc dfh_imgproc;
+#define DFH_IMGPROC_SRC_U8_HWC 0   /* uint8 [items][in_h][in_w][3], what np.asarray(pil_image) gives */
+#define DFH_IMGPROC_SRC_F32_CHW 1  /* fp32 [items][3][in_h][in_w] in [-1, 1] (vae.decode): quantised as x / 2 + 0.5, clamp to [0, 1], * 255,
+                                      round half to even -- difashion.postprocess(.., "pil"); a NaN becomes 0 */
+/* in_h, in_w: the size of one source item.  grid_n = 0: every item is an image of its own.  grid_n = n >= 1: output image b reads the
+ * virtual g x g sheet (g = ceil(sqrt(n)), row-major, white in the empty cells) of items b * n .. b * n + n - 1 (evalio.image_grid);
+ * the sheet is resolved when a pixel is fetched and never materialised.  Refused: an unsupported filter, sizes < 1, a resized image
+ * smaller than the crop, a shape whose one-row band does not fit the LDS budget of the kernel. */
+int dfh_imgproc_create(const dfh_imgproc_config* cfg, int in_h, int in_w, int grid_n, dfh_imgproc** out);
+void dfh_imgproc_destroy(dfh_imgproc* p);
+int dfh_imgproc_resized_height(const dfh_imgproc* p);
+int dfh_imgproc_resized_width(const dfh_imgproc* p);
+int dfh_imgproc_out_height(const dfh_imgproc* p);        /* crop_height, or the resized height without a crop */
+int dfh_imgproc_out_width(const dfh_imgproc* p);
+int dfh_imgproc_crop_top(const dfh_imgproc* p);
+int dfh_imgproc_crop_left(const dfh_imgproc* p);
+int dfh_imgproc_ksize_x(const dfh_imgproc* p);           /* taps a row of the horizontal table holds */
+int dfh_imgproc_ksize_y(const dfh_imgproc* p);
+size_t dfh_imgproc_table_bytes(const dfh_imgproc* p);
+/* host_buffer (>= table_bytes) receives int32: bounds_x [resized_w][2] (first tap, tap count), coef_x [resized_w][ksize_x], bounds_y
+ * [resized_h][2], coef_y [resized_h][ksize_y]; every |coefficient| < 2^23.  The caller copies it to the device and keeps it. */
+int dfh_imgproc_fill_tables(const dfh_imgproc* p, void* host_buffer, size_t buffer_bytes);
+/* pixel_values [batch][3][out_h][out_w] fp32 = lut[c][resized, cropped uint8]; out_u8 [batch][out_h][out_w][3] = that uint8 image.
+ * Either may be NULL, not both; lut_dev (3 x 256 fp32) may be NULL without pixel_values.  src holds batch * max(grid_n, 1) items.
+ * tables_dev, lut_dev, src, pixel_values: 16-byte aligned device pointers.  Nothing is allocated here. */
+int dfh_imgproc_run(const dfh_imgproc* p, const void* tables_dev, const float* lut_dev, const void* src, int src_kind, int batch,
+                    float* pixel_values, uint8_t* out_u8, void* stream);
 
 /* ------------------------------------------------------------------ op-level entry points (tests, profiling)
  * ResnetBlock2D conv3x3 / Downsample2D / Upsample2D / 1x1 conv / Linear, as one implicit GEMM:
