@@ -17,7 +17,9 @@ from .vae import AutoencoderKL
 from .clip import CLIPTextModel, CLIPTextModelOutput, CLIPTextModelWithProjection
 from .clip_vision import CLIPVisionModelOutput, CLIPVisionModelWithProjection
 from .image_processor import CLIPImageProcessor
-from .evalscores import CLIPScore, CompatibilityEvaluator, FashionEvaluator, candidate_cosine, extract_image_features, pair_cosine
+from .evalscores import (CLIPScore, CompatibilityEvaluator, FashionEvaluator, candidate_cosine, extract_image_features, lpips_given_data,
+                         lpips_retrieval, pair_cosine)
+from .lpips import LPIPS
 from .difashion import DiFashion
 
 __all__ = [
@@ -26,4 +28,5 @@ __all__ = [
     "FusedAdamW", "EMAModel", "clip_grad_norm_", "train_step", "AutoencoderKL", "CLIPTextModel", "DiFashion",
     "CLIPVisionModelWithProjection", "CLIPVisionModelOutput", "CLIPTextModelWithProjection", "CLIPTextModelOutput", "CLIPScore",
     "CompatibilityEvaluator", "FashionEvaluator", "pair_cosine", "candidate_cosine", "CLIPImageProcessor", "extract_image_features",
+    "LPIPS", "lpips_given_data", "lpips_retrieval",
 ]

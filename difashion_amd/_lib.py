@@ -67,6 +67,10 @@ class ImgProcConfigC(C.Structure):
     _fields_ = [("shortest_edge", C.c_int), ("crop_height", C.c_int), ("crop_width", C.c_int), ("resample", C.c_int)]
 
 
+class LpipsConfigC(C.Structure):
+    _fields_ = [("net", C.c_int)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [
         ("conv_src", C.c_void_p), ("conv_c", C.c_int), ("conv", C.c_int),
@@ -186,6 +190,21 @@ SIGNATURES = {
     "dfh_imgproc_table_bytes": (_sz, [_vp]),
     "dfh_imgproc_fill_tables": (_i, [_vp, _vp, _sz]),
     "dfh_imgproc_run": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "dfh_lpips_create": (_i, [C.POINTER(LpipsConfigC), C.POINTER(_vp)]),
+    "dfh_lpips_destroy": (None, [_vp]),
+    "dfh_lpips_num_params": (_i, [_vp]),
+    "dfh_lpips_param_name": (C.c_char_p, [_vp, _i]),
+    "dfh_lpips_param_ndim": (_i, [_vp, _i]),
+    "dfh_lpips_param_dim": (_i, [_vp, _i, _i]),
+    "dfh_lpips_packed_bytes": (_sz, [_vp]),
+    "dfh_lpips_pack": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp]),
+    "dfh_lpips_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "dfh_lpips_forward": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "dfh_lpips_group_argmin": (_i, [_vp, _vp, _i, _i, _vp]),
+    "dfh_lpips_prep": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "dfh_lpips_conv3x3_relu": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "dfh_lpips_maxpool2x2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "dfh_lpips_layer_score": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "dfh_vae_create": (_i, [C.POINTER(VAEConfigC), C.POINTER(_vp)]),
     "dfh_vae_destroy": (None, [_vp]),
     "dfh_vae_num_params": (_i, [_vp]),
@@ -297,7 +316,7 @@ SIGNATURES = {
 }
 _NO_STATUS = {"dfh_abi_version", "dfh_census_count", "dfh_unet_num_params", "dfh_unet_param_ndim", "dfh_unet_param_dim", "dfh_vae_num_params",
               "dfh_vae_param_ndim", "dfh_vae_param_dim", "dfh_clip_num_params", "dfh_clip_param_ndim", "dfh_clip_param_dim",
-              "dfh_clipv_num_params", "dfh_clipv_param_ndim", "dfh_clipv_param_dim",
+              "dfh_clipv_num_params", "dfh_clipv_param_ndim", "dfh_clipv_param_dim", "dfh_lpips_num_params", "dfh_lpips_param_ndim", "dfh_lpips_param_dim",
               "dfh_imgproc_resized_height", "dfh_imgproc_resized_width", "dfh_imgproc_out_height", "dfh_imgproc_out_width", "dfh_imgproc_crop_top",
               "dfh_imgproc_crop_left", "dfh_imgproc_ksize_x", "dfh_imgproc_ksize_y"}
 

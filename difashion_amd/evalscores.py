@@ -7,6 +7,9 @@ What the reference computes from the CLIP embeddings once ``encode_image`` / ``e
     and an argmax;
   * ``CompatibilityEvaluator.evaluate_compatibility`` (:574-588) over ``FashionEvaluator``
     (Evaluation/compatibility_evaluator/compatibility_net.py:14-81), which the reference runs one outfit at a time.
+And, over images and not embeddings:
+  * ``calculate_lpips_given_data`` (:473-501) and the two ``calculate_lpips_retrieval_acc_given_data*`` (:769-821) over an ``LPIPS`` model
+    (lpips.py): ``lpips_given_data`` and ``lpips_retrieval`` below, batch by batch without the DataLoader.
 
 All arithmetic runs in the kernel library (csrc/eval_scores.hip: ``dfh_embed_pair_cosine``, ``dfh_embed_candidates``,
 ``dfh_compat_score``) in fp32, in both storage builds.  The ``nn.Linear`` / ``nn.LayerNorm`` modules of ``FashionEvaluator`` only HOLD
@@ -95,6 +98,45 @@ def extract_image_features(image_model, processor, images, batch_size: int = 200
                            device=image_model.device).pixel_values
         feats.append(image_model.encode_image(pixels))
     return torch.cat(feats)
+
+
+def _image_batches(images, batch_size: int, what: str):
+    """Batches of a device tensor, or of a list of per-image device tensors (stacked a batch at a time)."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be positive, got {batch_size}")
+    n = images.shape[0] if isinstance(images, torch.Tensor) else len(images)
+    if n < 1:
+        raise ValueError(f"{what} holds no image")
+    for i in range(0, n, batch_size):
+        batch = images[i:i + batch_size]
+        yield batch if isinstance(batch, torch.Tensor) else torch.stack(list(batch))
+
+
+@torch.no_grad()
+def lpips_given_data(model, gen, grd, batch_size: int = 64) -> torch.Tensor:
+    """The per-pair scores ``[N]`` of ``calculate_lpips_given_data`` (eval_utils.py:473-501); the reference's number is their mean.
+    ``gen`` / ``grd``: device tensors in one of ``LPIPS.forward``'s input forms, or lists of per-image device tensors."""
+    n0 = gen.shape[0] if isinstance(gen, torch.Tensor) else len(gen)
+    n1 = grd.shape[0] if isinstance(grd, torch.Tensor) else len(grd)
+    if n0 != n1:
+        raise ValueError(f"gen holds {n0} images, grd {n1}")
+    return torch.cat([model(a, b).reshape(-1) for a, b in zip(_image_batches(gen, batch_size, "gen"), _image_batches(grd, batch_size, "grd"))])
+
+
+@torch.no_grad()
+def lpips_retrieval(model, gen, candidates, K: int = 5, batch_size: int = 64):
+    """``calculate_lpips_retrieval_acc_given_data`` (eval_utils.py:796-821): ``gen`` and ``candidates`` hold ``rows * K`` images each,
+    row-major, a row's first candidate being the ground truth.  Returns ``(scores [rows, K], preds [rows], accuracy)``: ``preds`` is
+    ``torch.argmin`` over a row on the HIP path, the accuracy the share of ``preds == 0``."""
+    from .lpips import group_argmin
+    if K < 1:
+        raise ValueError(f"K must be positive, got {K}")
+    scores = lpips_given_data(model, gen, candidates, batch_size)
+    if scores.numel() % K:
+        raise ValueError(f"{scores.numel()} pairs do not make whole rows of K={K}")
+    scores = scores.reshape(-1, K)
+    preds = group_argmin(scores)
+    return scores, preds, int((preds == 0).sum()) / scores.shape[0]
 
 
 class FashionEvaluator(nn.Module):

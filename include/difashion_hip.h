@@ -398,6 +398,66 @@ int dfh_imgproc_fill_tables(const dfh_imgproc* p, void* host_buffer, size_t buff
 int dfh_imgproc_run(const dfh_imgproc* p, const void* tables_dev, const float* lut_dev, const void* src, int src_kind, int batch,
                     float* pixel_values, uint8_t* out_u8, void* stream);
 
+/* ------------------------------------------------------------------ LPIPS on VGG16
+ * Replaces (arithmetic) lpips.LPIPS(net="vgg", version="0.1", spatial=False) as Evaluation/eval_utils.py:473-501 and :769-821 call it:
+ * the ScalingLayer, torchvision's vgg16().features up to relu5_3 (thirteen 3x3 convolutions with ReLU, four 2x2 max-pools), per tap
+ * layer the unit-normalised squared difference under the 1x1 "lin" weights and its spatial mean, and the sum of the five layers.
+ * csrc/lpips.hip: fp32 end to end, the same in both storage builds, convolutions on v_mfma_f32_16x16x4_f32 as an implicit GEMM over
+ * NHWC activations; no atomics, nothing allocated; a pair's result does not depend on the batch it rides in.
+ * The convolution adds up one input-channel chunk of 32 (x 9 taps) in fresh accumulators and adds that to the running sum.
+ * Parameters, DFH_LPIPS_NUM_PARAMS = 33, in this order (the names of the lpips package's state dict):
+ *   scaling_layer.shift, scaling_layer.scale                                    [1][3][1][1]
+ *   net.slice{1..5}.{0,2 | 5,7 | 10,12,14 | 17,19,21 | 24,26,28}.{weight,bias}  [C_out][C_in][3][3], [C_out]
+ *   lin{0..4}.model.1.weight                                                    [1][C][1][1], C = 64, 128, 256, 512, 512 */
+#define DFH_LPIPS_NUM_PARAMS 33
+#define DFH_LPIPS_NUM_LAYERS 5
+#define DFH_LPIPS_PARTIALS 256     /* partial sums a (pair, layer) in the workspace */
+#define DFH_LPIPS_NET_VGG16 0
+#define DFH_LPIPS_SRC_U8_HWC 0     /* uint8 [n][H][W][3]: lut[v] = float32(float64(v) / 127.5 - 1.0) (im2tensor_lpips), 256 fp32 */
+#define DFH_LPIPS_SRC_F32_CHW 1    /* fp32 [n][3][H][W] in [-1, 1], the lpips input form; normalize != 0: 2 x - 1 first ([0, 1] input) */
+typedef struct dfh_lpips_config {
+  int net;                         /* DFH_LPIPS_NET_VGG16; every other network is refused */
+} dfh_lpips_config;
+typedef struct dfh_lpips dfh_lpips;
+int dfh_lpips_create(const dfh_lpips_config* cfg, dfh_lpips** out);   /* host-only work */
+void dfh_lpips_destroy(dfh_lpips* c);
+int dfh_lpips_num_params(const dfh_lpips* c);
+const char* dfh_lpips_param_name(const dfh_lpips* c, int i);
+int dfh_lpips_param_ndim(const dfh_lpips* c, int i);
+int dfh_lpips_param_dim(const dfh_lpips* c, int i, int d);
+/* The packed conv weights, [chunk][tap][channel][C_out] a layer (chunks of 32 input channels; the first layer is one chunk of 4, its
+ * fourth channel 0): 4 * sum over the thirteen convs of 9 * C_in_padded * C_out bytes = 58 844 160. */
+size_t dfh_lpips_packed_bytes(const dfh_lpips* c);
+int dfh_lpips_pack(dfh_lpips* c, const float* const* params, int count, void* packed, void* stream);
+/* Two ping-pong activation buffers of 2 * pairs images at the widest level (64 channels at H x W) + the partial sums:
+ *   4 * (2 * (2 * pairs * H * W * 64) + pairs * DFH_LPIPS_NUM_LAYERS * DFH_LPIPS_PARTIALS) + 256 bytes; 0 for H or W outside [16, 8192] */
+size_t dfh_lpips_workspace_bytes(const dfh_lpips* c, int pairs, int H, int W);
+/* distance[p] = lpips(in0[p], in1[p]), p < pairs; per_layer: NULL, or [pairs][5], distance[p] = per_layer[p][0] + ... + [4] in that order.
+ *   params   : HOST array of `count` device pointers to the fp32 parameters, table order, each 16-byte aligned
+ *   packed   : what dfh_lpips_pack wrote (>= dfh_lpips_packed_bytes)
+ *   in0, in1 : `pairs` images each in the form src_kind; lut: the 256-entry table of the uint8 form, else NULL
+ *   workspace: >= dfh_lpips_workspace_bytes(pairs, H, W), 256-byte aligned
+ * Refused on the host before any HIP call, with a message each: a wrong count; a null pointer and a pointer that is not 16-byte
+ * aligned, by name; H or W below 16 (the fifth level would be empty); a workspace that is too small. */
+int dfh_lpips_forward(dfh_lpips* c, const float* const* params, int count, const void* packed, const void* in0, const void* in1, int src_kind,
+                      const float* lut, int normalize, int pairs, int H, int W, float* distance, float* per_layer, void* workspace,
+                      size_t workspace_bytes, void* stream);
+/* pred[r] = argmin_k scores[r * K + k] in torch.argmin's order: a NaN is the minimum, the lowest index wins among equals */
+int dfh_lpips_group_argmin(const float* scores, int64_t* pred, int rows, int K, void* stream);
+/* The kernels of the walk on their own (tests, microbenchmarks).  Activations are NHWC fp32.
+ * prep: out [n][H][W][4] = ((x - shift[c]) / scale[c], 0), bit for bit torch's ops.
+ * conv3x3_relu: out [n][H][W][C_out] = relu(conv2d(x [n][H][W][C_in], weight [C_out][w_cin][3][3], bias, padding=1)); C_in is 4 or a
+ *   multiple of 32, C_out a multiple of 64, input channels from w_cin up carry zero weights; packed: 9 * C_in * C_out floats.
+ * maxpool2x2: out [n][H/2][W/2][C], floor mode, a NaN propagates.
+ * layer_score: out[p] = mean over the pixels of sum_c w_c (x_c / (|x| + 1e-10) - y_c / (|y| + 1e-10))^2 for x = feat[p], y = feat[pairs + p],
+ *   feat [2 pairs][H][W][C], C <= 512; partial: pairs * DFH_LPIPS_PARTIALS floats. */
+int dfh_lpips_prep(const void* src, int src_kind, const float* lut, const float* shift, const float* scale, int normalize, float* out, int n,
+                   int H, int W, void* stream);
+int dfh_lpips_conv3x3_relu(const float* x, const float* weight, int w_cin, const float* bias, float* packed, float* out, int n, int H, int W,
+                           int C_in, int C_out, void* stream);
+int dfh_lpips_maxpool2x2(const float* x, float* out, int n, int H, int W, int C, void* stream);
+int dfh_lpips_layer_score(const float* feat, const float* lin_weight, int pairs, int H, int W, int C, float* partial, float* out, void* stream);
+
 /* ------------------------------------------------------------------ op-level entry points (tests, profiling)
  * ResnetBlock2D conv3x3 / Downsample2D / Upsample2D / 1x1 conv / Linear, as one implicit GEMM:
  *   out[M][N] = act( conv3x3(x) (+ a0 . W[:, k0:] + a1 . W[:, k1:]) + bias + rowvec[b] ) + resid */
