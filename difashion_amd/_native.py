@@ -59,6 +59,32 @@ def read_checkpoint_config(cls, path: str, subfolder: Optional[str] = None):
     return d, {k: v for k, v in cfg.items() if not k.startswith("_")}
 
 
+def grow_buffer(holder, attr: str, nbytes: int, dev: torch.device) -> torch.Tensor:
+    """The uint8 device block ``holder.<attr>``, reused unless it is missing, on another device or smaller than ``nbytes``."""
+    buf = getattr(holder, attr)
+    if buf is None or buf.device != dev or buf.numel() < nbytes:
+        setattr(holder, attr, None)                      # release the old block before asking for the larger one
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        setattr(holder, attr, buf)
+    return buf
+
+
+def require_params_on(dev: torch.device, params) -> None:
+    """The kernels read the parameters in place through raw pointers."""
+    if any(p.device != dev or not p.is_contiguous() for p in params):
+        raise _lib.DfhError("all parameters must be contiguous and on one device")
+
+
+def require_hip_fp32(what: str, params, fp32_rule: str) -> torch.device:
+    """The device of ``params``' first tensor, or a refusal: it is not on the GPU, or one of ``params`` is not fp32."""
+    dev = params[0].device
+    if dev.type != "cuda":
+        raise _lib.DfhError(f"{what} runs only on the MI355X HIP path: move it to 'cuda' (no CPU fallback)")
+    if any(p.dtype != torch.float32 for p in params):
+        raise _lib.DfhError(fp32_rule)
+    return dev
+
+
 class NativeModule(nn.Module):
     family: str = ""                     # entry-point prefix: dfh_<family>_*
     config_name = "config.json"
@@ -174,12 +200,7 @@ class NativeModule(nn.Module):
         return next(self.parameters()).dtype
 
     def _require_hip_fp32(self, what: str) -> torch.device:
-        dev = self.device
-        if dev.type != "cuda":
-            raise _lib.DfhError(f"{what} runs only on the MI355X HIP path: move it to 'cuda' (no CPU fallback)")
-        if self.dtype != torch.float32:
-            raise _lib.DfhError(self._fp32_rule)
-        return dev
+        return require_hip_fp32(what, [next(self.parameters())], self._fp32_rule)
 
 
 class TupleOutput:
@@ -227,13 +248,9 @@ class ClipTower(NativeModule):
         (pointer array, count) for the encode call."""
         if self._ctx is None:
             self._ctx = self._make_ctx()
-        need = self._entry("workspace_bytes")(self._ctx, *batch_args)
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
-            self._ws = None                              # release the old block before asking for the larger one
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        grow_buffer(self, "_ws", self._entry("workspace_bytes")(self._ctx, *batch_args), dev)
         plist = self._plist()
-        if any(p.device != dev or not p.is_contiguous() for p in plist):
-            raise _lib.DfhError("all parameters must be contiguous and on one device")
+        require_params_on(dev, plist)
         return self._pointers(plist), len(plist)
 
     # ------------------------------------------------------------------ checkpoints (transformers directory layout)

@@ -18,7 +18,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._native import ClipTower, TupleOutput
+from ._native import ClipTower, TupleOutput, require_params_on
 
 
 class BaseModelOutputWithPooling(TupleOutput):
@@ -133,8 +133,7 @@ class CLIPTextModelWithProjection(CLIPTextModel):
         cfg = self.config
         arr, count = self._prepare(dev, B, T)
         proj = self.text_projection.weight
-        if proj.device != dev or not proj.is_contiguous():
-            raise _lib.DfhError("all parameters must be contiguous and on one device")
+        require_params_on(dev, [proj])
         D, L, Pd = cfg["hidden_size"], cfg["num_hidden_layers"], cfg["projection_dim"]
         embeds = torch.empty((B, Pd), dtype=torch.float32, device=dev)
         last = torch.empty((B, T, D), dtype=torch.float32, device=dev)
@@ -152,8 +151,7 @@ class CLIPTextModelWithProjection(CLIPTextModel):
         dev, ids, B, T = self._ids_on_device("CLIPTextModelWithProjection", input_ids, None, None, None)
         arr, count = self._prepare(dev, B, T)
         proj = self.text_projection.weight
-        if proj.device != dev or not proj.is_contiguous():
-            raise _lib.DfhError("all parameters must be contiguous and on one device")
+        require_params_on(dev, [proj])
         embeds = torch.empty((B, self.config["projection_dim"]), dtype=torch.float32, device=dev)
         _lib.call("dfh_clip_text_embeds", self._ctx, arr, count, _lib.ptr(proj), self.config["projection_dim"], _lib.ptr(ids),
                   _lib.ptr(embeds), None, None, int(self.config["eos_token_id"]), None, _lib.ptr(self._ws), self._ws.numel(), B, T,

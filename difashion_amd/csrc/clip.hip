@@ -14,6 +14,7 @@
 // not to bf16 noise.  No atomics: reruns are bit-identical.
 #include "../../include/difashion_hip.h"
 #include "clip_tower.h"
+#include "f32_tile.h"
 
 namespace {
 
@@ -34,37 +35,16 @@ __global__ __launch_bounds__(256) void clip_embed_kernel(const int64_t* __restri
 }
 
 // ------------------------------------------------------------------ LayerNorm over the last dim, fp32 in / out, one wave per row
-// (two-pass mean / biased variance like torch.nn.functional.layer_norm); input rows ldx floats apart, output rows dense
+// (f32_tile.h layernorm_row); input rows ldx floats apart, output rows dense
 __global__ __launch_bounds__(256) void clip_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                              const float* __restrict__ b, float* __restrict__ y, int M, int D, float eps, long ldx) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= M) return;
-  const float4* r = (const float4*)(x + (long)row * ldx);
-  float s = 0.f;
-  for (int c = lane; c < D / 4; c += 64) { const float4 v = r[c]; s += (v.x + v.y) + (v.z + v.w); }
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-  for (int c = lane; c < D / 4; c += 64) {
-    const float4 v = r[c];
-    const float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
-    q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
-  float4* o = (float4*)(y + (long)row * D);
-  for (int c = lane; c < D / 4; c += 64) {
-    const float4 v = r[c], gg = ((const float4*)g)[c], bb = ((const float4*)b)[c];
-    o[c] = make_float4((v.x - mean) * rstd * gg.x + bb.x, (v.y - mean) * rstd * gg.y + bb.y, (v.z - mean) * rstd * gg.z + bb.z,
-                       (v.w - mean) * rstd * gg.w + bb.w);
-  }
+  dfh::layernorm_row<false>(x, ldx, g, b, y, M, D, eps);
 }
 
 // ------------------------------------------------------------------ fp32 linear on the fp32 matrix pipe
 //   out[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]) (+ resid[m][n])
-// 64 x 64 output tile per workgroup (four waves, 32 x 32 each = 2 x 2 v_mfma_f32_16x16x4_f32 blocks), K in steps of 32.
-// Operand tiles sit k-major in LDS ([k][row], row stride 80 floats): a fragment read (lane -> row l % 16, k l / 16) touches 64 distinct
-// banks, and the transposing store of a float4 along k writes consecutive rows of one k.  The next k-tile's global loads are issued
-// before the current tile's MFMAs (register prefetch).
-constexpr int CBM = 64, CBN = 64, CBK = 32, CLD = 80;
+// The 64 x 64 tile of f32_tile.h (gemm_tile) with one accumulator down all of K (ChainSum).
+using dfh::GT_M; using dfh::GT_N;
 using dfh::CLIP_ACT_NONE; using dfh::CLIP_ACT_QUICK_GELU; using dfh::CLIP_ACT_GELU;
 
 DFH_DEVICE float clip_act(float v, int act) {
@@ -76,77 +56,11 @@ DFH_DEVICE float clip_act(float v, int act) {
 __global__ __launch_bounds__(256) void clip_gemm_f32_kernel(const float* __restrict__ A, int lda, const float* __restrict__ W, int ldw,
                                                             const float* __restrict__ bias, const float* resid, int ld_res,
                                                             float* out, int ld_out, int M, int N, int K, int act) {
-  __shared__ float As[CBK * CLD];
-  __shared__ float Ws[CBK * CLD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m0 = blockIdx.y * CBM, n0 = blockIdx.x * CBN;
-  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
-  // staging: thread -> (row = tid % 64, k-quads tid / 64 and tid / 64 + 4)
-  const int srow = tid & 63, sq = tid >> 6;
-  const int am = min(m0 + srow, M - 1), wr = min(n0 + srow, N - 1);
-  const float* ap = A + (long)am * lda;
-  const float* wp = W + (long)wr * ldw;
-  float4 ra[2], rw[2];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int k = k0 + (sq + 4 * j) * 4;
-      ra[j] = k < K ? *(const float4*)(ap + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-      rw[j] = k < K ? *(const float4*)(wp + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  auto stash = [&]() {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int kk = (sq + 4 * j) * 4;
-      As[(kk + 0) * CLD + srow] = ra[j].x; As[(kk + 1) * CLD + srow] = ra[j].y;
-      As[(kk + 2) * CLD + srow] = ra[j].z; As[(kk + 3) * CLD + srow] = ra[j].w;
-      Ws[(kk + 0) * CLD + srow] = rw[j].x; Ws[(kk + 1) * CLD + srow] = rw[j].y;
-      Ws[(kk + 2) * CLD + srow] = rw[j].z; Ws[(kk + 3) * CLD + srow] = rw[j].w;
-    }
-  };
-  f32x4_t acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  const int fr = lane & 15, fk = lane >> 4;
-  fetch(0);
-  for (int k0 = 0; k0 < K; k0 += CBK) {
-    __syncthreads();                       // the previous tile's fragment reads are done
-    stash();
-    __syncthreads();
-    if (k0 + CBK < K) fetch(k0 + CBK);
-#pragma unroll
-    for (int kk = 0; kk < CBK; kk += 4) {
-      float a[2], b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = As[(kk + fk) * CLD + wm + 16 * i + fr];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) b[j] = Ws[(kk + fk) * CLD + wn + 16 * j + fr];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    }
-  }
-  // C layout of 16x16x4: acc[r] = C[4 * (lane / 16) + r][lane % 16]
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn + 16 * j + fr;
-      if (n >= N) continue;
-      const float bv = bias ? bias[n] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm + 16 * i + 4 * fk + r;
-        if (m >= M) continue;
-        float v = clip_act(acc[i][j][r] + bv, act);
-        if (resid) v += resid[(long)m * ld_res + n];
-        out[(long)m * ld_out + n] = v;
-      }
-    }
+  dfh::gemm_tile<dfh::ChainSum>(A, lda, W, ldw, bias, M, N, K, [=](int m, int n, float acc) {
+    float v = clip_act(acc, act);
+    if (resid) v += resid[(long)m * ld_res + n];
+    out[(long)m * ld_out + n] = v;
+  });
 }
 
 // ------------------------------------------------------------------ causal self-attention over one (sequence, head): T <= 128 tokens
@@ -272,7 +186,7 @@ namespace dfh {
 int clip_linear(const float* A, int lda, const float* W, int K, const float* bias, const float* resid, int ld_res, float* out,
                 int ld_out, int M, int N, int act, int prof_class, hipStream_t s) {
   ProfScope ps(prof_class, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N), s);
-  const dim3 grid((N + CBN - 1) / CBN, (M + CBM - 1) / CBM);
+  const dim3 grid((N + GT_N - 1) / GT_N, (M + GT_M - 1) / GT_M);
   hipLaunchKernelGGL(clip_gemm_f32_kernel, grid, dim3(256), 0, s, A, lda, W, K, bias, resid, ld_res, out, ld_out, M, N, K, act);
   return check_launch("clip_gemm_f32_kernel");
 }

@@ -9,13 +9,11 @@ namespace dfh {
 
 // what an encode entry point requires of master_params; the kernels read every parameter as float4.  family: "dfh_clip" / "dfh_clipv"
 inline int require_params(const ParamList& t, const float* const* master_params, int count, const std::string& family) {
-  auto refuse = [&](const std::string& msg) { set_error(family + "_encode: " + msg); return -1; };
-  if (count != t.num_params()) return refuse("master_params count does not match " + family + "_num_params");
-  for (int i = 0; i < count; ++i) {
-    if (master_params[i] == nullptr) return refuse("null parameter pointer: " + t.params[i].name);
-    if (((uintptr_t)master_params[i] & 15) != 0) return refuse("parameter pointer not 16-byte aligned: " + t.params[i].name);
+  if (count != t.num_params()) {
+    set_error(family + "_encode: master_params count does not match " + family + "_num_params");
+    return -1;
   }
-  return 0;
+  return check_param_pointers(master_params, count, family + "_encode", [&](int i) { return ": " + t.params[i].name; });
 }
 
 // table indices of one CLIPEncoderLayer
@@ -40,16 +38,12 @@ inline std::vector<ClipLayer> add_encoder_layers(ParamList& t, const std::string
 }
 
 // Workspace of an encode over M rows: x | ln | q k v (qkv_width floats a row) | attention | MLP hidden | tail, + 64 floats of slack.
-// The same layout serves the live walk and the size query (base = null: only `floats` is read).
-struct ClipWorkspace {
-  float *x, *ln, *qkv, *att, *hid, *tail; size_t floats;
-  ClipWorkspace(void* base, size_t M, size_t D, size_t I, size_t qkv_width, size_t tail_floats) {
-    size_t off = 0;
-    auto take = [&](size_t n) { float* p = base ? (float*)base + off : nullptr; off += n; return p; };
+struct ClipWorkspace : WorkspaceCarve {
+  float *x, *ln, *qkv, *att, *hid, *tail;
+  ClipWorkspace(void* base, size_t M, size_t D, size_t I, size_t qkv_width, size_t tail_floats) : WorkspaceCarve(base, 1) {
     x = take(M * D); ln = take(M * D); qkv = take(M * qkv_width); att = take(M * D); hid = take(M * I); tail = take(tail_floats);
-    floats = off + 64;
+    take(64);                                                    // the slack
   }
-  size_t bytes() const { return floats * sizeof(float) + 256; }
 };
 
 // How a tower's launches are accounted: the ProfClass of its linears / LayerNorms (< 0: not timed), the census counters they bump (< 0: none)

@@ -260,6 +260,24 @@ struct ParamList {
 void set_error(const std::string& msg);  // api.cpp
 const char* last_error();                // the message of the last refusal on this thread (dfh_last_error)
 int check_launch(const char* what);     // returns 0 or negative and records the message
+// The carve of one fp32 workspace block into regions, each rounded up to `round` floats.  The same walk serves the live call and the
+// size query (base = null: every region is null, only `floats` is read); bytes() leaves 256 for the caller's alignment.
+struct WorkspaceCarve {
+  float* base; size_t round, floats = 0;
+  WorkspaceCarve(void* b, size_t round_floats) : base((float*)b), round(round_floats) {}
+  float* take(size_t n) { float* p = base ? base + floats : nullptr; floats += (n + round - 1) / round * round; return p; }
+  size_t bytes() const { return floats * sizeof(float) + 256; }
+};
+// What an entry point requires of a table of fp32 parameter pointers (the kernels read every parameter as float4), on the host, before
+// any HIP call.  who: the entry point, for the message; name_of(i): how parameter i is called there (": <name>", " at index <i>")
+template <class NameOf>
+int check_param_pointers(const float* const* params, int count, const std::string& who, NameOf name_of) {
+  for (int i = 0; i < count; ++i) {
+    const char* fault = params[i] == nullptr ? "null parameter pointer" : ((uintptr_t)params[i] & 15) != 0 ? "parameter pointer not 16-byte aligned" : nullptr;
+    if (fault) { set_error(who + ": " + fault + name_of(i)); return -1; }
+  }
+  return 0;
+}
 // Optional per-launch timing with HIP events recorded on the launch stream (bench.py roofline).
 enum ProfClass { PC_CONV3 = 0, PC_LINEAR = 1, PC_ATTN = 2, PC_GNORM = 3, PC_LNORM = 4, PC_SPLITK = 5, PC_OTHER = 6,
                  PC_WGRAD = 7, PC_ATTN_BWD = 8, PC_NORM_BWD = 9, PC_OPTIM = 10, PC_LINEAR_FP8 = 11, PC_COUNT = 12 };

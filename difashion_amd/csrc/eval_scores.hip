@@ -17,6 +17,7 @@
 
 #include "../../include/difashion_hip.h"
 #include "clip_kernels.h"
+#include "f32_tile.h"
 
 namespace {
 
@@ -118,28 +119,10 @@ __global__ __launch_bounds__(256) void compat_pairs_kernel(const float* __restri
   for (int c = threadIdx.x; c < F / 4; c += 256) { out[c] = fi[c]; out[F / 4 + c] = fj[c]; }
 }
 
-// y = relu(LayerNorm(x) * g + b), one wave per row, two-pass mean / biased variance (the text tower's LayerNorm with the ReLU folded in)
+// y = relu(LayerNorm(x) * g + b): the towers' one-wave-a-row LayerNorm (f32_tile.h layernorm_row) with the ReLU folded in
 __global__ __launch_bounds__(256) void compat_ln_relu_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                              const float* __restrict__ b, float* __restrict__ y, int M, int D, float eps) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= M) return;
-  const float4* r = (const float4*)(x + (long)row * D);
-  float s = 0.f;
-  for (int c = lane; c < D / 4; c += 64) { const float4 v = r[c]; s += (v.x + v.y) + (v.z + v.w); }
-  const float mean = wave_sum(s) / (float)D;
-  float q = 0.f;
-  for (int c = lane; c < D / 4; c += 64) {
-    const float4 v = r[c];
-    const float d0 = v.x - mean, d1 = v.y - mean, d2 = v.z - mean, d3 = v.w - mean;
-    q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
-  float4* o = (float4*)(y + (long)row * D);
-  for (int c = lane; c < D / 4; c += 64) {
-    const float4 v = r[c], gg = ((const float4*)g)[c], bb = ((const float4*)b)[c];
-    o[c] = make_float4(fmaxf((v.x - mean) * rstd * gg.x + bb.x, 0.f), fmaxf((v.y - mean) * rstd * gg.y + bb.y, 0.f),
-                       fmaxf((v.z - mean) * rstd * gg.z + bb.z, 0.f), fmaxf((v.w - mean) * rstd * gg.w + bb.w, 0.f));
-  }
+  dfh::layernorm_row<true>(x, D, g, b, y, M, D, eps);
 }
 
 // outfit_emb[o][c] = mean over the outfit's pairs of e[o * npairs + p][c]  (torch.mean(relation_embs, dim=0))
@@ -166,106 +149,23 @@ __global__ __launch_bounds__(256) void compat_tail_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------ the scorer's Linear: out[m][n] = sum_k A[m][k] W[n][k] + bias[n]
-// The tile, the k-major LDS image and the register prefetch of the CLIP towers' clip_gemm_f32_kernel (clip.hip) on
-// v_mfma_f32_16x16x4_f32, with another accumulation: the towers' kernel runs ONE accumulator down all of K, a chain whose rounding error
-// grows like sqrt(K); measured on an MI355X that put outfit_emb 3.9 x and the single-outfit logit 9 x beyond the real class's own fp32
-// distance from fp64 (K = 2048 in emb_layer.0; torch's CPU sgemm sums in blocks).  Here every 32-wide k-tile is summed on its own into
-// two fresh accumulators (even / odd k-quads: chains of four instructions), and the tile sums are added to the running result with a
-// compensated (Kahan) add, so the error no longer grows with K.  Same operands, same products, another summation order.
-constexpr int GBM = 64, GBN = 64, GBK = 32, GLD = 80;
+// The 64 x 64 tile of f32_tile.h (gemm_tile), the one the CLIP towers run, under the other summation policy: the towers' ChainSum runs
+// ONE accumulator down all of K, a chain whose rounding error grows like sqrt(K); measured on an MI355X that put outfit_emb 3.9 x and
+// the single-outfit logit 9 x beyond the real class's own fp32 distance from fp64 (K = 2048 in emb_layer.0; torch's CPU sgemm sums in
+// blocks).  TileKahanSum sums every 32-wide k-tile on its own and adds the tile sums with a compensated (Kahan) add, so the error no
+// longer grows with K.  Same operands, same products, another summation order.
+using dfh::GT_M; using dfh::GT_N;
 
 __global__ __launch_bounds__(256) void compat_gemm_f32_kernel(const float* __restrict__ A, int lda, const float* __restrict__ W, int ldw,
                                                               const float* __restrict__ bias, float* __restrict__ out, int ld_out, int M,
                                                               int N, int K) {
-  __shared__ float As[GBK * GLD];
-  __shared__ float Ws[GBK * GLD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m0 = blockIdx.y * GBM, n0 = blockIdx.x * GBN;
-  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
-  // staging: thread -> (row = tid % 64, k-quads tid / 64 and tid / 64 + 4); rows beyond M / N read the last row and are never stored
-  const int srow = tid & 63, sq = tid >> 6;
-  const float* ap = A + (long)min(m0 + srow, M - 1) * lda;
-  const float* wp = W + (long)min(n0 + srow, N - 1) * ldw;
-  float4 ra[2], rw[2];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int k = k0 + (sq + 4 * j) * 4;
-      ra[j] = k < K ? *(const float4*)(ap + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-      rw[j] = k < K ? *(const float4*)(wp + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  auto stash = [&]() {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int kk = (sq + 4 * j) * 4;
-      As[(kk + 0) * GLD + srow] = ra[j].x; As[(kk + 1) * GLD + srow] = ra[j].y;
-      As[(kk + 2) * GLD + srow] = ra[j].z; As[(kk + 3) * GLD + srow] = ra[j].w;
-      Ws[(kk + 0) * GLD + srow] = rw[j].x; Ws[(kk + 1) * GLD + srow] = rw[j].y;
-      Ws[(kk + 2) * GLD + srow] = rw[j].z; Ws[(kk + 3) * GLD + srow] = rw[j].w;
-    }
-  };
-  const f32x4_t zero = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  f32x4_t sum[2][2], comp[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { sum[i][j] = zero; comp[i][j] = zero; }
-  const int fr = lane & 15, fk = lane >> 4;
-  fetch(0);
-  for (int k0 = 0; k0 < K; k0 += GBK) {
-    __syncthreads();                       // the previous tile's fragment reads are done
-    stash();
-    __syncthreads();
-    if (k0 + GBK < K) fetch(k0 + GBK);
-    f32x4_t t[2][2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) { t[0][i][j] = zero; t[1][i][j] = zero; }
-#pragma unroll
-    for (int kk = 0; kk < GBK; kk += 4) {
-      float a[2], b[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = As[(kk + fk) * GLD + wm + 16 * i + fr];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) b[j] = Ws[(kk + fk) * GLD + wn + 16 * j + fr];
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          t[(kk >> 2) & 1][i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], t[(kk >> 2) & 1][i][j], 0, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const f32x4_t y = (t[0][i][j] + t[1][i][j]) - comp[i][j];
-        const f32x4_t s = sum[i][j] + y;
-        comp[i][j] = (s - sum[i][j]) - y;
-        sum[i][j] = s;
-      }
-  }
-  // C layout of 16x16x4: acc[r] = C[4 * (lane / 16) + r][lane % 16]
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn + 16 * j + fr;
-      if (n >= N) continue;
-      const float bv = bias[n];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + wm + 16 * i + 4 * fk + r;
-        if (m < M) out[(long)m * ld_out + n] = sum[i][j][r] + bv;
-      }
-    }
+  dfh::gemm_tile<dfh::TileKahanSum>(A, lda, W, ldw, bias, M, N, K, [=](int m, int n, float acc) { out[(long)m * ld_out + n] = acc; });
 }
 
 // A [M][K] dense, W [N][K] (nn.Linear layout, read in place), K a multiple of 4, rows 16-byte aligned
 int compat_linear(const float* A, const float* W, int K, const float* bias, float* out, int M, int N, hipStream_t s) {
   dfh::ProfScope ps(dfh::PC_OTHER, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N), s);
-  hipLaunchKernelGGL(compat_gemm_f32_kernel, dim3((N + GBN - 1) / GBN, (M + GBM - 1) / GBM), dim3(256), 0, s, A, K, W, K, bias, out, N, M, N, K);
+  hipLaunchKernelGGL(compat_gemm_f32_kernel, dim3((N + GT_N - 1) / GT_N, (M + GT_M - 1) / GT_M), dim3(256), 0, s, A, K, W, K, bias, out, N, M, N, K);
   return dfh::check_launch("compat_gemm_f32_kernel");
 }
 
@@ -277,27 +177,19 @@ constexpr int EVAL_DIMS[4] = {EMB, 128, 128, TAIL_IN};
 constexpr float LN_EPS = 1e-5f;                   // nn.LayerNorm's default
 
 // x | f | pairs | ping | pong | emb, every region a multiple of 64 floats
-struct CompatWorkspace {
-  float *x, *f, *pairs, *ping, *pong, *emb; size_t floats;
-  CompatWorkspace(void* base, size_t outfits, size_t items, size_t dim) {
+struct CompatWorkspace : dfh::WorkspaceCarve {
+  float *x, *f, *pairs, *ping, *pong, *emb;
+  CompatWorkspace(void* base, size_t outfits, size_t items, size_t dim) : dfh::WorkspaceCarve(base, 64) {
     const size_t R = outfits * items, P = outfits * (items * (items - 1) / 2);
-    size_t off = 0;
-    auto take = [&](size_t n) { float* p = base ? (float*)base + off : nullptr; off += (n + 63) / 64 * 64; return p; };
     x = take(R * dim); f = take(R * FEAT); pairs = take(P * 2 * FEAT); ping = take(P * 512); pong = take(P * 512); emb = take(outfits * EMB);
-    floats = off;
   }
-  size_t bytes() const { return floats * sizeof(float) + 256; }
 };
 
 int check_params(const float* const* params, int count, const char* who) {
   auto refuse = [&](const std::string& msg) { dfh::set_error(std::string(who) + ": " + msg); return -1; };
   if (!params) return refuse("null argument");
   if (count != DFH_COMPAT_NUM_PARAMS) return refuse("params count must be DFH_COMPAT_NUM_PARAMS (32)");
-  for (int i = 0; i < count; ++i) {
-    if (params[i] == nullptr) return refuse("null parameter pointer at index " + std::to_string(i));
-    if (((uintptr_t)params[i] & 15) != 0) return refuse("parameter pointer not 16-byte aligned at index " + std::to_string(i));
-  }
-  return 0;
+  return dfh::check_param_pointers(params, count, who, [](int i) { return " at index " + std::to_string(i); });
 }
 
 // n x (Linear, LayerNorm, ReLU) over M rows: dims[l] -> dims[l + 1], parameters from index p0 (weight, bias, ln weight, ln bias a layer).

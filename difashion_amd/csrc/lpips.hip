@@ -26,6 +26,7 @@
 
 #include "../../include/difashion_hip.h"
 #include "dfh_common.h"
+#include "f32_tile.h"
 
 namespace {
 
@@ -136,11 +137,11 @@ __global__ __launch_bounds__(THREADS) void lpips_conv3x3_relu_kernel(const float
   const int nchunks = C_in / CC;
   fetch_w(0, 0);
   for (int chunk = 0; chunk < nchunks; ++chunk) {
-    f32x4_t t[MF][4];                                  // FRESH accumulators: this chunk's nine taps
+    f32x4_t t[1][MF][4];                               // FRESH accumulators: this chunk's nine taps
 #pragma unroll
     for (int i = 0; i < MF; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) t[i][j] = zero;
+      for (int j = 0; j < 4; ++j) t[0][i][j] = zero;
 #pragma unroll 1
     for (int tap = 0; tap < 9; ++tap) {
       __syncthreads();                                 // the previous step's fragment reads are done
@@ -150,24 +151,13 @@ __global__ __launch_bounds__(THREADS) void lpips_conv3x3_relu_kernel(const float
       if (tap < 8) fetch_w(chunk, tap + 1);
       else if (chunk + 1 < nchunks) fetch_w(chunk + 1, 0);
       const int ky = tap / 3, kx = tap - ky * 3;
-      const float* arow = &In[(MF * wave + ky) * HALO_W + kx + fr];
-#pragma unroll
-      for (int kk = 0; kk < CC; kk += 4) {
-        float a[MF], b[4];
-#pragma unroll
-        for (int i = 0; i < MF; ++i) a[i] = arow[(kk + fk) * IN_LD + i * HALO_W];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = Ws[(kk + fk) * W_LD + 16 * j + fr];
-#pragma unroll
-        for (int i = 0; i < MF; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], t[i][j], 0, 0, 0);
-      }
+      // A fragment i: patch row MF wave + i shifted by the tap, one halo row (HALO_W) below fragment i - 1
+      dfh::mma_ktile<1, MF, 4, CC>(&In[(MF * wave + ky) * HALO_W + kx + fr], IN_LD, HALO_W, Ws + fr, W_LD, fk, t);
     }
 #pragma unroll
     for (int i = 0; i < MF; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) sum[i][j] = sum[i][j] + t[i][j];      // the plain fp32 add of the contract
+      for (int j = 0; j < 4; ++j) sum[i][j] = sum[i][j] + t[0][i][j];      // the plain fp32 add of the contract
   }
   // C layout of 16x16x4: acc[r] = C[4 * (lane / 16) + r][lane % 16] = (pixel 4 fk + r of the patch row, channel fr of the fragment)
 #pragma unroll
@@ -275,12 +265,7 @@ __global__ __launch_bounds__(THREADS) void lpips_finish_kernel(const float* __re
   if ((int)threadIdx.x < a.layers) {
     const int l = threadIdx.x;
     float s = 0.0f, comp = 0.0f;
-    for (int g = 0; g < a.G[l]; ++g) {
-      const float y = part[l * PART + g] - comp;
-      const float t = s + y;
-      comp = (t - s) - y;
-      s = t;
-    }
+    for (int g = 0; g < a.G[l]; ++g) dfh::kahan_add(s, comp, part[l * PART + g]);
     layer[l] = s / a.hw[l];
   }
   __syncthreads();
@@ -320,16 +305,12 @@ constexpr int MAX_SIDE = 8192, MAX_IMAGES = 65535;
 int score_groups(long HW) { return (int)std::min<long>(PART, (HW + 3) / 4); }
 
 // ping | pong (2 pairs images x H x W x 64 floats each: the widest activation is the first level's) | partial sums
-struct LpipsWorkspace {
-  float *ping, *pong, *partial; size_t floats;
-  LpipsWorkspace(void* base, size_t pairs, size_t H, size_t W) {
-    size_t off = 0;
-    auto take = [&](size_t n) { float* p = base ? (float*)base + off : nullptr; off += n; return p; };
+struct LpipsWorkspace : dfh::WorkspaceCarve {
+  float *ping, *pong, *partial;
+  LpipsWorkspace(void* base, size_t pairs, size_t H, size_t W) : dfh::WorkspaceCarve(base, 1) {
     const size_t act = 2 * pairs * H * W * 64;
     ping = take(act); pong = take(act); partial = take(pairs * NTAP * PART);
-    floats = off;
   }
-  size_t bytes() const { return floats * sizeof(float) + 256; }
 };
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -411,11 +392,7 @@ struct dfh_lpips {
     auto refuse = [&](const std::string& msg) { dfh::set_error(std::string(who) + ": " + msg); return -1; };
     if (!params) return refuse("null argument: params");
     if (count != t.num_params()) return refuse("params count does not match dfh_lpips_num_params (" + std::to_string(DFH_LPIPS_NUM_PARAMS) + ")");
-    for (int i = 0; i < count; ++i) {
-      if (params[i] == nullptr) return refuse("null parameter pointer: " + t.params[i].name);
-      if (!aligned16(params[i])) return refuse("parameter pointer not 16-byte aligned: " + t.params[i].name);
-    }
-    return 0;
+    return dfh::check_param_pointers(params, count, who, [&](int i) { return ": " + t.params[i].name; });
   }
 };
 

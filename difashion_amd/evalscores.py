@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._native import grow_buffer, require_hip_fp32, require_params_on
 
 NUM_PARAMS = 32          # DFH_COMPAT_NUM_PARAMS
 EMB_DIM = 256
@@ -175,13 +176,8 @@ class FashionEvaluator(nn.Module):
     # ------------------------------------------------------------------ plumbing
     def _require_hip_fp32(self, what: str, *tensors) -> torch.device:
         plist = list(self.parameters())
-        dev = plist[0].device
-        if dev.type != "cuda":
-            raise _lib.DfhError(f"{what} runs only on the MI355X HIP path: move it to 'cuda' (no CPU fallback)")
-        if any(p.dtype != torch.float32 for p in plist):
-            raise _lib.DfhError("parameters must stay fp32 (the kernels read them in place)")
-        if any(p.device != dev or not p.is_contiguous() for p in plist):
-            raise _lib.DfhError("all parameters must be contiguous and on one device")
+        dev = require_hip_fp32(what, plist, "parameters must stay fp32 (the kernels read them in place)")
+        require_params_on(dev, plist)
         if torch.is_grad_enabled() and any(p.requires_grad for p in plist):
             raise _lib.DfhError(f"{what} is inference only: call it under torch.no_grad() or .requires_grad_(False)")
         for t in tensors:
@@ -199,11 +195,7 @@ class FashionEvaluator(nn.Module):
         return (C.c_void_p * NUM_PARAMS)(*[p.data_ptr() for p in plist]), plist
 
     def _workspace(self, dev, outfits: int, items: int, dim: int) -> torch.Tensor:
-        need = _lib.raw().dfh_compat_workspace_bytes(outfits, items, dim)
-        if self._ws is None or self._ws.device != dev or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._ws
+        return grow_buffer(self, "_ws", _lib.raw().dfh_compat_workspace_bytes(outfits, items, dim), dev)
 
     def _score(self, what, feats_real, feats_gen, olists, outfits, items, want_scores=True):
         """-> (outfit_emb [O, 256], logits [O], scores [O])"""

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._native import FrozenDict, NativeModule, read_checkpoint_config, save_checkpoint
+from ._native import FrozenDict, NativeModule, grow_buffer, read_checkpoint_config, require_params_on, save_checkpoint
 
 SRC_U8_HWC, SRC_F32_CHW = 0, 1
 SHIFT = (-.030, -.088, -.188)
@@ -123,13 +123,10 @@ class LPIPS(NativeModule):
         return model
 
     def _buffer(self, name: str, nbytes: int, dev: torch.device) -> torch.Tensor:
-        buf = getattr(self, name)
-        if buf is None or buf.device != dev or buf.numel() < nbytes:
-            setattr(self, name, None)                    # release the old block before asking for the larger one
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            setattr(self, name, buf)
-            if name == "_packed":
-                self._packed_sig = None
+        packed = self._packed                            # 59 MB whatever the call: held across it, unlike the workspace
+        buf = grow_buffer(self, name, nbytes, dev)
+        if self._packed is not packed:
+            self._packed_sig = None                      # a new block holds no packed copy yet
         return buf
 
     def _prepare(self, dev: torch.device):
@@ -137,8 +134,7 @@ class LPIPS(NativeModule):
         if self._ctx is None:
             self._ctx = self._make_ctx()
         plist = self._plist()
-        if any(p.device != dev or not p.is_contiguous() for p in plist):
-            raise _lib.DfhError("all parameters must be contiguous and on one device")
+        require_params_on(dev, plist)
         packed = self._buffer("_packed", self._entry("packed_bytes")(self._ctx), dev)
         arr = self._pointers(plist)
         sig = self._signature(plist)

@@ -8,14 +8,10 @@ linears / attention / LayerNorm / embedding.
     python scripts/bench_clip_vision.py [--images 200] [--batch 50] [--model vit_h_14|vit_l_14] [--out profiles/clip_vision_bench.json]
 """
 import argparse
-import json
 import os
-import sys
 
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _rowbench import ROOT, emit, header, randomise
 
 import difashion_amd as da  # noqa: E402
 from difashion_amd import _lib  # noqa: E402
@@ -50,9 +46,7 @@ def main():
     # weights: small random values drawn on the device (the speed does not depend on them; parity is tests/test_gpu_clip_vision.py)
     m = da.CLIPVisionModelWithProjection(**cfg, init_seed=None).to("cuda").eval().requires_grad_(False)
     g = torch.Generator(device="cuda").manual_seed(0)
-    for name, p in m.named_parameters():
-        if p.dim() >= 2:
-            p.copy_(torch.randn(p.shape, generator=g, device="cuda") * (0.7 / p[0].numel() ** 0.5))
+    randomise(m, g)
     n_batches = max(1, a.images // a.batch)
     px = torch.randn(n_batches, a.batch, 3, cfg["image_size"], cfg["image_size"], generator=g, device="cuda")
     m.encode_image(px[0])                                   # warm-up: workspace allocation, code-object load
@@ -83,12 +77,8 @@ def main():
                peak_tflops=PEAK_FP32_MFMA_TFLOPS, flops_share=dict(linears=round(lin / (lin + att + emb_f), 4),
                                                                   attention=round(att / (lin + att + emb_f), 4),
                                                                   embedding=round(emb_f / (lin + att + emb_f), 4)),
-               profiled_batch=split, device=torch.cuda.get_device_name(0), build_info=_lib.raw().dfh_build_info().decode())
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+               profiled_batch=split, **header())
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -12,47 +12,16 @@ spread (min .. max) is kept.  Weights are small random values drawn on the devic
     python scripts/bench_eval_scores.py [--out profiles/eval_scores_bench.json]
 """
 import argparse
-import json
 import os
-import statistics
-import sys
 
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _rowbench import ROOT, emit, header, randomise, timed
 
 import difashion_amd as da  # noqa: E402
-from difashion_amd import _lib  # noqa: E402
 
 PEAK_HBM_GBPS = 8000.0
 TEXT_H = dict(vocab_size=49408, hidden_size=1024, intermediate_size=4096, num_hidden_layers=24, num_attention_heads=16,
               max_position_embeddings=77, hidden_act="gelu", eos_token_id=2, projection_dim=1024)
-
-
-def timed(fn, windows=5, min_window_ms=200.0):
-    """ms per call: median, min, max over `windows` event-timed windows, each long enough to swamp the launch overhead."""
-    fn(); fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(); fn(); b.record()
-    torch.cuda.synchronize()
-    reps = max(1, int(min_window_ms / max(a.elapsed_time(b), 1e-3)) + 1)
-    per = []
-    for _ in range(windows):
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        per.append(a.elapsed_time(b) / reps)
-    return dict(ms=round(statistics.median(per), 4), ms_min=round(min(per), 4), ms_max=round(max(per), 4), calls_per_window=reps)
-
-
-def randomise(module, g):
-    for p in module.parameters():
-        if p.dim() >= 2:
-            p.copy_(torch.randn(p.shape, generator=g, device="cuda") * (0.7 / p[0].numel() ** 0.5))
 
 
 def main():
@@ -62,7 +31,7 @@ def main():
     torch.cuda.set_device(0)
     torch.set_grad_enabled(False)
     g = torch.Generator(device="cuda").manual_seed(0)
-    res = dict(device=torch.cuda.get_device_name(0), build_info=_lib.raw().dfh_build_info().decode())
+    res = header()
 
     O, items, dim = 4096, 4, 1024
     ev = da.FashionEvaluator(dim).to("cuda")
@@ -98,11 +67,7 @@ def main():
     t_encode = timed(lambda: base(ids))
     res["encode_text"] = dict(prompts=51, seq_len=77, shape="OpenCLIP ViT-H/14 text tower, 24 x 1024, projection 1024", **t_embeds)
     res["clip_encode_same_tower"] = dict(prompts=51, seq_len=77, **t_encode)
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

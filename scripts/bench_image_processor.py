@@ -13,43 +13,18 @@ spread (min .. max) is kept.  The kernel's time does not depend on the pixel val
     python scripts/bench_image_processor.py [--out profiles/image_processor_bench.json] [--no-tower]
 """
 import argparse
-import json
 import os
-import statistics
-import sys
 import time
 
 import numpy as np
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _rowbench import ROOT, emit, header, randomise, timed
 
 import difashion_amd as da  # noqa: E402
-from difashion_amd import _lib  # noqa: E402
 
 PEAK_HBM_GBPS = 8000.0
 VIT_H_14 = dict(hidden_size=1280, intermediate_size=5120, projection_dim=1024, num_hidden_layers=32, num_attention_heads=16,
                 image_size=224, patch_size=14, hidden_act="gelu")
-
-
-def timed(fn, windows=5, min_window_ms=200.0):
-    """ms per call: median, min, max over `windows` event-timed windows, each long enough to swamp the launch overhead."""
-    fn(); fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record(); fn(); b.record()
-    torch.cuda.synchronize()
-    reps = max(1, int(min_window_ms / max(a.elapsed_time(b), 1e-3)) + 1)
-    per = []
-    for _ in range(windows):
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        per.append(a.elapsed_time(b) / reps)
-    return dict(ms=round(statistics.median(per), 4), ms_min=round(min(per), 4), ms_max=round(max(per), 4), calls_per_window=reps)
 
 
 def case(p, src, images, grid=None):
@@ -69,9 +44,7 @@ def main():
     torch.cuda.set_device(0)
     torch.set_grad_enabled(False)
     g = torch.Generator(device="cuda").manual_seed(0)
-    prop = torch.cuda.get_device_properties(0)                    # the marketing name alone does not identify the card
-    res = dict(device=torch.cuda.get_device_name(0), gcn_arch=getattr(prop, "gcnArchName", ""), compute_units=prop.multi_processor_count,
-               hbm_gib=round(prop.total_memory / 2 ** 30, 1), build_info=_lib.raw().dfh_build_info().decode())
+    res = header(card=True)
     p = da.CLIPImageProcessor()
 
     u8 = torch.randint(0, 256, (200, 512, 512, 3), generator=g, device="cuda", dtype=torch.uint8)
@@ -83,9 +56,7 @@ def main():
 
     if not a.no_tower:
         m = da.CLIPVisionModelWithProjection(**VIT_H_14, init_seed=None).to("cuda").eval().requires_grad_(False)
-        for q in m.parameters():
-            if q.dim() >= 2:
-                q.copy_(torch.randn(q.shape, generator=g, device="cuda") * (0.7 / q[0].numel() ** 0.5))
+        randomise(m, g)
         px = p(images=u8).pixel_values
         t = timed(lambda: m.encode_image(px), windows=3, min_window_ms=1.0)
         res["encode_image_vit_h_14"] = dict(images=200, ms_per_image=round(t["ms"] / 200, 4), **t)
@@ -104,11 +75,7 @@ def main():
         res["pil_on_this_host"] = dict(version=PIL.__version__, **out)
     except ImportError:
         res["pil_on_this_host"] = None
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -13,15 +13,10 @@ not depend on the values.
     python scripts/bench_lpips.py [--out profiles/lpips_bench.json] [--sizes 512 1024]
 """
 import argparse
-import json
 import os
-import statistics
-import sys
 
 import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from _rowbench import ROOT, emit, header, spread
 
 import difashion_amd as da  # noqa: E402
 from difashion_amd import _lib  # noqa: E402
@@ -32,10 +27,6 @@ MAC_PER_PIXEL = 305_856
 CONVS = [(4, 64, 0), (64, 64, 0), (64, 128, 1), (128, 128, 1), (128, 256, 2), (256, 256, 2), (256, 256, 2), (256, 512, 3), (512, 512, 3),
          (512, 512, 3), (512, 512, 4), (512, 512, 4), (512, 512, 4)]
 NAMES = ["conv1_1", "conv1_2", "conv2_1", "conv2_2", "conv3_1", "conv3_2", "conv3_3", "conv4_1", "conv4_2", "conv4_3", "conv5_1", "conv5_2", "conv5_3"]
-
-
-def spread(per):
-    return dict(ms=round(statistics.median(per), 4), ms_min=round(min(per), 4), ms_max=round(max(per), 4))
 
 
 def conv_case(cin, cout, h, w, g, windows=5, min_window_ms=50.0):
@@ -91,9 +82,7 @@ def main():
     torch.cuda.set_device(0)
     torch.set_grad_enabled(False)
     g = torch.Generator(device="cuda").manual_seed(0)
-    prop = torch.cuda.get_device_properties(0)
-    res = dict(device=torch.cuda.get_device_name(0), gcn_arch=getattr(prop, "gcnArchName", ""), compute_units=prop.multi_processor_count,
-               hbm_gib=round(prop.total_memory / 2 ** 30, 1), build_info=_lib.raw().dfh_build_info().decode(), peak_fp32_matrix_tflops=PEAK_TFLOPS)
+    res = dict(**header(card=True), peak_fp32_matrix_tflops=PEAK_TFLOPS)
     model = da.LPIPS().to("cuda")
     for size in a.sizes:
         convs = {}
@@ -104,11 +93,7 @@ def main():
         many = model.pairs_per_call(size, size)
         res[f"pair_{size}"] = [pair_case(model, 1, size, g), pair_case(model, many, size, g)]
         torch.cuda.empty_cache()
-    line = json.dumps(res)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(line + "\n")
-    print(line)
+    emit(res, a.out)
 
 
 if __name__ == "__main__":

@@ -99,6 +99,7 @@ COMPAT_CASES = {
     "three_items": (7, 3, 1024, 43),
     "five_items": (6, 5, 1024, 44),
     "two_items_narrow": (9, 2, 64, 45),
+    "ragged_k": (5, 3, 44, 46),          # feat_dim 44: one full and one ragged 32-wide k-tile in feat_layer's GEMM
 }
 COMPAT_REAL_ROWS, COMPAT_GEN_ROWS = 300, 40
 

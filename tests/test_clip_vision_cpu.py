@@ -229,9 +229,10 @@ def test_fixtures_belong_to_the_regenerated_inputs(name):
 def test_product_file_is_in_both_builds_and_fp32():
     """The row is compiled into both storage builds from one source, and that source names neither 16-bit type."""
     mk = open(os.path.join(_lib.CSRC, "Makefile")).read()
-    assert "clip_vision.hip" in mk and "clip_kernels.h" in mk
-    src = open(os.path.join(_lib.CSRC, "clip_vision.hip")).read()
-    assert not re.search(r"\b(bf16_t|h16x8_t|DFH_F16|pack2bf|f2bf)\b", src)
+    assert "clip_vision.hip" in mk and "clip_kernels.h" in mk and "f32_tile.h" in mk
+    for name in ("clip_vision.hip", "f32_tile.h"):
+        src = open(os.path.join(_lib.CSRC, name)).read()
+        assert not re.search(r"\b(bf16_t|h16x8_t|DFH_F16|pack2bf|f2bf)\b", src), name
     r = subprocess.run(["nm", "-D", "--defined-only", os.path.join(_lib.CSRC, _lib._LIB_NAMES["fp16"])], capture_output=True, text=True)
     if r.returncode == 0:
         assert "dfh_clipv_encode" in r.stdout
