@@ -40,9 +40,7 @@ struct AttnBwdArgs {
 // four consecutive channels d0 .. d0 + 3 of output row `row` (elements from the start of O), already normalised (and, for O8, scaled)
 DFH_DEVICE void attn_store4(const AttnArgs& a, long row, int d0, float v0, float v1, float v2, float v3) {
   if (a.O8) {
-    const int lo = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v0, -448.f, 448.f), __builtin_amdgcn_fmed3f(v1, -448.f, 448.f), 0, false);
-    *(unsigned*)(a.O8 + row + d0) =
-        (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(v2, -448.f, 448.f), __builtin_amdgcn_fmed3f(v3, -448.f, 448.f), lo, true);
+    *(unsigned*)(a.O8 + row + d0) = pack4_e4m3_sat(v0, v1, v2, v3);
   } else {
     uint2 w;
     w.x = pack2bf(v0, v1); w.y = pack2bf(v2, v3);
@@ -53,7 +51,7 @@ DFH_DEVICE void attn_store4(const AttnArgs& a, long row, int d0, float v0, float
 DFH_DEVICE float attn_qmul(const AttnArgs& a, int b) {
   if (!a.O8) return 1.0f;
   const float am = a.o_amax[b];
-  return am > 0.f ? 448.0f / am : 0.f;
+  return am > 0.f ? E4M3_MAX / am : 0.f;
 }
 #endif
 

@@ -48,20 +48,15 @@ template <int D> struct F8Geom {
 
 DFH_DEVICE int k_sw(int krow_bytes, int key) { return krow_bytes == 64 ? ((key >> 2) & 3) : (krow_bytes == 128 ? ((key >> 1) & 7) : (key & 15)); }
 
-DFH_DEVICE float sat8(float x) { return __builtin_amdgcn_fmed3f(x, -448.0f, 448.0f); }   // the static bounds make this a no-op; it keeps a NaN byte out
-DFH_DEVICE unsigned cvt4(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-}
-// 16 bf16 values (two uint4) times 16 per-channel factors -> 16 e4m3 bytes
+// 16 bf16 values (two uint4) times 16 per-channel factors -> 16 e4m3 bytes (the static bounds make the clamp a no-op; it keeps a NaN byte out)
 DFH_DEVICE uint4 quant16(const uint4& lo, const uint4& hi, const float* r) {
   float f[16];
   unpack8(lo, f); unpack8(hi, f + 8);
   uint4 o;
 #pragma unroll
-  for (int e = 0; e < 16; ++e) f[e] = sat8(f[e] * r[e]);
-  o.x = cvt4(f[0], f[1], f[2], f[3]); o.y = cvt4(f[4], f[5], f[6], f[7]);
-  o.z = cvt4(f[8], f[9], f[10], f[11]); o.w = cvt4(f[12], f[13], f[14], f[15]);
+  for (int e = 0; e < 16; ++e) f[e] = sat_e4m3(f[e] * r[e]);
+  o.x = pack4_e4m3(f[0], f[1], f[2], f[3]); o.y = pack4_e4m3(f[4], f[5], f[6], f[7]);
+  o.z = pack4_e4m3(f[8], f[9], f[10], f[11]); o.w = pack4_e4m3(f[12], f[13], f[14], f[15]);
   return o;
 }
 DFH_DEVICE uint4 quant16s(const uint4& lo, const uint4& hi, float r) {
@@ -69,9 +64,9 @@ DFH_DEVICE uint4 quant16s(const uint4& lo, const uint4& hi, float r) {
   unpack8(lo, f); unpack8(hi, f + 8);
   uint4 o;
 #pragma unroll
-  for (int e = 0; e < 16; ++e) f[e] = sat8(f[e] * r);
-  o.x = cvt4(f[0], f[1], f[2], f[3]); o.y = cvt4(f[4], f[5], f[6], f[7]);
-  o.z = cvt4(f[8], f[9], f[10], f[11]); o.w = cvt4(f[12], f[13], f[14], f[15]);
+  for (int e = 0; e < 16; ++e) f[e] = sat_e4m3(f[e] * r);
+  o.x = pack4_e4m3(f[0], f[1], f[2], f[3]); o.y = pack4_e4m3(f[4], f[5], f[6], f[7]);
+  o.z = pack4_e4m3(f[8], f[9], f[10], f[11]); o.w = pack4_e4m3(f[12], f[13], f[14], f[15]);
   return o;
 }
 
@@ -263,7 +258,7 @@ __global__ __launch_bounds__(256, 2) void attention_fp8_kernel(const AttnArgs a)
         for (int g = 0; g < 4; ++g) {
           const float p0 = __builtin_amdgcn_exp2f(fmaf(s[qb][kb][4 * g], cs, -m_run[qb])), p1 = __builtin_amdgcn_exp2f(fmaf(s[qb][kb][4 * g + 1], cs, -m_run[qb]));
           const float p2 = __builtin_amdgcn_exp2f(fmaf(s[qb][kb][4 * g + 2], cs, -m_run[qb])), p3 = __builtin_amdgcn_exp2f(fmaf(s[qb][kb][4 * g + 3], cs, -m_run[qb]));
-          w[kb * 4 + g] = cvt4(p0, p1, p2, p3);
+          w[kb * 4 + g] = pack4_e4m3(p0, p1, p2, p3);
         }
       pf[qb] = i32x8_t{(int)w[0], (int)w[1], (int)w[2], (int)w[3], (int)w[4], (int)w[5], (int)w[6], (int)w[7]};
     }
@@ -337,13 +332,13 @@ __global__ __launch_bounds__(256) void attn_scales_kernel(const bf16_t* __restri
   __shared__ float red[4];
   if (lane == 0) red[wave] = g;
   __syncthreads();
-  const float sigma = fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) / 448.0f, 1e-30f);
+  const float sigma = fmaxf(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) / E4M3_MAX, 1e-30f);
   for (int c = threadIdx.x; c < D; c += 256) {
     const float bq = fmaxf(bnd[0][c], 1e-30f), bk = fmaxf(bnd[1][c], 1e-30f), bv = fmaxf(bnd[2][c], 1e-30f);
     const float sc = sqrtf(bq / bk);
     rq[h * D + c] = 1.0f / (sc * sigma);
     rk[h * D + c] = sc / sigma;
-    rv[h * D + c] = 448.0f / bv;
+    rv[h * D + c] = E4M3_MAX / bv;
   }
   if (threadIdx.x == 0) hs[h] = sigma * sigma;
 }

@@ -96,6 +96,19 @@ DFH_DEVICE uint4 pack8(const float* f) {
   return v;
 }
 
+// four floats -> four e4m3 bytes (a in the lowest), round-to-nearest-even: v_cvt_pk_fp8_f32 twice.  _sat clamps to the largest finite
+// e4m3 first (one v_med3_f32 each), which also keeps a NaN byte out.
+constexpr float E4M3_MAX = 448.0f;
+DFH_DEVICE unsigned pack4_e4m3(float a, float b, float c, float d) {
+  const int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
+  return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+}
+DFH_DEVICE float sat_e4m3(float x) { return __builtin_amdgcn_fmed3f(x, -E4M3_MAX, E4M3_MAX); }
+DFH_DEVICE unsigned pack4_e4m3_sat(float a, float b, float c, float d) {
+  const int w = __builtin_amdgcn_cvt_pk_fp8_f32(sat_e4m3(a), sat_e4m3(b), 0, false);
+  return (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(sat_e4m3(c), sat_e4m3(d), w, true);
+}
+
 // x * sigmoid(x) with the hardware reciprocal (1 ulp) instead of an IEEE division: the division expands to ~10 VALU
 // instructions (v_div_scale / v_rcp / 4 x v_fma / v_div_fmas / v_div_fixup), which made GroupNorm+SiLU VALU-bound -- 42 M
 // elements per 64x64-level launch at ~70 wave-cycles per 64 of them is 19 us of a 27 us kernel.  The result is rounded to bf16

@@ -17,6 +17,7 @@
 // registers (scales, bias, GEGLU on the (value, gate) rows a lane holds of one 32-row block, residual), bf16 tile staged per wave
 // through LDS for full-row 16-byte stores.
 #include "gemm.h"
+#include "norm_steps.h"
 
 #include <algorithm>
 
@@ -30,17 +31,10 @@ constexpr int NST8 = 3;
 
 template <int N> DFH_DEVICE void f8_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-DFH_DEVICE unsigned pack4_fp8(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (unsigned)w;
-}
-constexpr float FP8_MAX = 448.0f;
-
 // E8M0 block scale of a group whose largest magnitude is am: the smallest power of two 2^e with am / 2^e <= 448.  Returns the biased
 // exponent byte (e + 127, kept inside [1, 253] so that its reciprocal is a normal float) and, through inv, 2^-e.
 DFH_DEVICE unsigned e8m0_of(float am, float* inv) {
-  const unsigned bits = __float_as_uint(am * (1.0f / FP8_MAX));
+  const unsigned bits = __float_as_uint(am * (1.0f / E4M3_MAX));
   unsigned e = (bits >> 23) + ((bits & 0x7fffffu) ? 1u : 0u);       // ceil(log2(am / 448)) + 127
   e = am > 0.f ? min(max(e, 1u), 253u) : 127u;
   *inv = __uint_as_float((254u - e) << 23);
@@ -311,7 +305,7 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8GemmArgs a) {
 #pragma unroll
             for (int g = 0; g < 2; ++g)
               *(unsigned*)(stage + ql * RS + c * 32 + h * 16 + 8 * g + 4 * kh) =
-                  pack4_fp8(hv[2 * c + h][4 * g] * inv, hv[2 * c + h][4 * g + 1] * inv, hv[2 * c + h][4 * g + 2] * inv, hv[2 * c + h][4 * g + 3] * inv);
+                  pack4_e4m3(hv[2 * c + h][4 * g] * inv, hv[2 * c + h][4 * g + 1] * inv, hv[2 * c + h][4 * g + 2] * inv, hv[2 * c + h][4 * g + 3] * inv);
           const int kb = (n0_ >> 6) + c;                      // 32-unit block index along the hidden axis
           if (kh == 0 && m_ok && (kb << 6) < a.N) a.out_sx[(size_t)kb * a.M + m] = (uint8_t)e;
         }
@@ -347,7 +341,7 @@ __global__ __launch_bounds__(256, 2) void gemm_fp8_kernel(const Fp8GemmArgs a) {
           const unsigned e = e8m0_of(am, &inv);
 #pragma unroll
           for (int g = 0; g < 4; ++g)
-            *(unsigned*)(stage + ql * RS + ci * 32 + 8 * g + 4 * kh) = pack4_fp8(v[4 * g] * inv, v[4 * g + 1] * inv, v[4 * g + 2] * inv, v[4 * g + 3] * inv);
+            *(unsigned*)(stage + ql * RS + ci * 32 + 8 * g + 4 * kh) = pack4_e4m3(v[4 * g] * inv, v[4 * g + 1] * inv, v[4 * g + 2] * inv, v[4 * g + 3] * inv);
           const int kb = (n0_ >> 5) + ci;
           if (kh == 0 && m_ok && (kb << 5) < a.N) a.out_sx[(size_t)kb * a.M + m] = (uint8_t)e;
         }
@@ -396,15 +390,15 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const bf16_t* __res
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-  const float sc = amax > 0.f ? amax / FP8_MAX : 1.0f;
+  const float sc = amax > 0.f ? amax / E4M3_MAX : 1.0f;
   const float inv = 1.0f / sc;
   if (lane == 0) scale[row] = sc;
   for (int o = lane * 8; o < K; o += 512) {
     float f[8];
     unpack8(*(const uint4*)(xr + o), f);
     uint2 w;
-    w.x = pack4_fp8(f[0] * inv, f[1] * inv, f[2] * inv, f[3] * inv);
-    w.y = pack4_fp8(f[4] * inv, f[5] * inv, f[6] * inv, f[7] * inv);
+    w.x = pack4_e4m3(f[0] * inv, f[1] * inv, f[2] * inv, f[3] * inv);
+    w.y = pack4_e4m3(f[4] * inv, f[5] * inv, f[6] * inv, f[7] * inv);
     *(uint2*)(q + (long)row * K + o) = w;
   }
 }
@@ -421,24 +415,12 @@ __global__ __launch_bounds__(256) void layernorm_fp8_kernel(const bf16_t* __rest
   if (row0 >= M) return;
   const int C8 = C >> 3;
   uint4 raw[R][MAXO];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int i = 0; i < MAXO; ++i) {
-      const int o = lane + i * 64;
-      raw[r][i] = make_uint4(0u, 0u, 0u, 0u);
-      if (o < C8 && row0 + r < M) raw[r][i] = *(const uint4*)(x + (long)(row0 + r) * C + o * 8);
-    }
+  ln_load_rows<MAXO, R>(x, row0, M, C, lane, raw);
   float gg[MAXO][8], bb[MAXO][8];
 #pragma unroll
   for (int i = 0; i < MAXO; ++i) {
     const int o = lane + i * 64;
-    if (o < C8) {
-      const float4 g0 = *(const float4*)(gamma + o * 8), g1 = *(const float4*)(gamma + o * 8 + 4);
-      const float4 b0 = *(const float4*)(beta + o * 8), b1 = *(const float4*)(beta + o * 8 + 4);
-      gg[i][0] = g0.x; gg[i][1] = g0.y; gg[i][2] = g0.z; gg[i][3] = g0.w; gg[i][4] = g1.x; gg[i][5] = g1.y; gg[i][6] = g1.z; gg[i][7] = g1.w;
-      bb[i][0] = b0.x; bb[i][1] = b0.y; bb[i][2] = b0.z; bb[i][3] = b0.w; bb[i][4] = b1.x; bb[i][5] = b1.y; bb[i][6] = b1.z; bb[i][7] = b1.w;
-    }
+    if (o < C8) { load8f(gamma + o * 8, gg[i]); load8f(beta + o * 8, bb[i]); }
   }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
@@ -447,22 +429,15 @@ __global__ __launch_bounds__(256) void layernorm_fp8_kernel(const bf16_t* __rest
     // the kernel is VALU-issue bound (40 of 64 lanes hold data at C = 320): the centred values of the variance pass are kept and
     // normalised with one multiply + one fma per element; the fp32 value is quantised directly (no bf16 round trip)
     float v[MAXO][8];
-    float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < MAXO; ++i) {
-      unpack8(raw[r][i], v[i]);
-      if (lane + i * 64 < C8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += v[i][k];
-      }
-    }
-    const float mean = wave_sum(s) / (float)C;
-    float qq = 0.f;
+    for (int i = 0; i < MAXO; ++i) unpack8(raw[r][i], v[i]);
+    ln_centre<MAXO>(v, lane, C);
+    float qq = 0.f;                                  // fused squares: this kernel's own rounding (norm_steps.h ln_rstd)
 #pragma unroll
     for (int i = 0; i < MAXO; ++i) {
       if (lane + i * 64 < C8) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) { v[i][k] -= mean; qq = fmaf(v[i][k], v[i][k], qq); }
+        for (int k = 0; k < 8; ++k) qq = fmaf(v[i][k], v[i][k], qq);
       }
     }
     const float rstd = rsqrtf(wave_sum(qq) / (float)C + eps);
@@ -479,7 +454,7 @@ __global__ __launch_bounds__(256) void layernorm_fp8_kernel(const bf16_t* __rest
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    const float sc = amax > 0.f ? amax / FP8_MAX : 1.0f;
+    const float sc = amax > 0.f ? amax / E4M3_MAX : 1.0f;
     const float inv = 1.0f / sc;
     if (lane == 0) scale[row] = sc;
 #pragma unroll
@@ -487,8 +462,8 @@ __global__ __launch_bounds__(256) void layernorm_fp8_kernel(const bf16_t* __rest
       const int o = lane + i * 64;
       if (o < C8) {
         uint2 w;
-        w.x = pack4_fp8(v[i][0] * inv, v[i][1] * inv, v[i][2] * inv, v[i][3] * inv);
-        w.y = pack4_fp8(v[i][4] * inv, v[i][5] * inv, v[i][6] * inv, v[i][7] * inv);
+        w.x = pack4_e4m3(v[i][0] * inv, v[i][1] * inv, v[i][2] * inv, v[i][3] * inv);
+        w.y = pack4_e4m3(v[i][4] * inv, v[i][5] * inv, v[i][6] * inv, v[i][7] * inv);
         *(uint2*)(q + (long)row * C + o * 8) = w;
       }
     }

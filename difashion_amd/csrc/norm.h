@@ -53,6 +53,28 @@ struct GnFoldArgs {
 };
 
 namespace dfh {
+// Launch geometry of a statistics kernel + apply kernel pair over a = GnArgs or GnBwdArgs (a.C, B, HW set): a thread owns a channel
+// octet and one of PL pixel lanes; the statistics pass runs as a.chunks pixel chunks an image (its partial buffer holds GN_MAX_CHUNKS),
+// the apply pass as achunks.  The targets are the chunk counts to aim for over the whole batch: enough blocks to fill the chip.
+struct GnTwoKernel { int block, achunks; size_t lds; };     // threads of both kernels, apply grid, dynamic LDS of the statistics kernel
+template <class Args>
+int gn_two_kernel_geometry(Args& a, int stats_target, int apply_target, GnTwoKernel* g) {
+  const int C8 = a.C / 8;
+  a.PL = std::max(1, std::min(256 / C8, a.HW));
+  g->block = ((C8 * a.PL + 63) / 64) * 64;
+  DFH_REQUIRE(g->block <= 512, "block too large (more than 4096 channels)");
+  const int max_by_pix = (a.HW + a.PL - 1) / a.PL;
+  const int chunks = std::max(1, std::min({(stats_target + a.B - 1) / a.B, max_by_pix, (int)GN_MAX_CHUNKS}));
+  a.pix_per_chunk = (a.HW + chunks - 1) / chunks;
+  a.chunks = (a.HW + a.pix_per_chunk - 1) / a.pix_per_chunk;
+  const int ac = std::max(1, std::min((apply_target + a.B - 1) / a.B, max_by_pix));
+  a.apix_per_chunk = (a.HW + ac - 1) / ac;
+  g->achunks = (a.HW + a.apix_per_chunk - 1) / a.apix_per_chunk;
+  g->lds = (size_t)a.PL * a.C * 2 * sizeof(float);          // [PL][C][2]
+  DFH_REQUIRE(g->lds <= 64 * 1024, "GroupNorm LDS reduction too large");
+  return 0;
+}
+
 int groupnorm_fold_launch(GnFoldArgs a, hipStream_t stream);
 int groupnorm_bwd_launch(GnBwdArgs a, hipStream_t stream);
 // LayerNorm backward over rows [M][C]; dx (=|+=); dgamma/dbeta fp32 atomics

@@ -11,20 +11,20 @@
 // octet below C0/8 comes from src0, the rest from src1.
 #include "dfh_common.h"
 #include "norm.h"
+#include "norm_steps.h"
 #include "walk_knobs.h"
 #include <cstring>
 #include <cstdlib>
 
 namespace {
 
-struct GnGeom {
-  int C, C0, C1, HW, cpg, C8, PL, chunks, pix_per_chunk;
-};
-
-DFH_DEVICE const uint4* gn_src(const GnArgs& a, int b, int p, int o) {
-  const int o0 = a.C0 >> 3;
-  if (o < o0) return (const uint4*)(a.src0 + ((long)(b * a.HW + p) * a.C0 + o * 8));
-  return (const uint4*)(a.src1 + ((long)(b * a.HW + p) * a.C1 + (o - o0) * 8));
+// the accumulation body of gn_stats_kernel (a function, not a lambda as in gn_bwd_stats_kernel: with a lambda the compiler schedules
+// the load batches into 154 VGPRs instead of 94, three waves a SIMD instead of five)
+DFH_DEVICE void gn_sum_sq(const uint4& raw, float* s, float* q) {
+  float f[8];
+  unpack8(raw, f);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { s[k] += f[k]; q[k] += f[k] * f[k]; }
 }
 
 // grid (chunks, B); block = roundup64(C8 * PL) threads; thread -> (pixel lane pl, octet o)
@@ -41,39 +41,24 @@ __global__ __launch_bounds__(512) void gn_stats_kernel(const GnArgs a) {
 #pragma unroll
   for (int k = 0; k < 8; ++k) { s[k] = 0.f; q[k] = 0.f; }
   if (pl < a.PL) {
-    // 4 independent 16-byte loads in flight per thread (a single dependent load per iteration is
+    // batches of 8, then 4 independent 16-byte loads in flight per thread (a single dependent load per iteration is
     // latency-bound at ~1 TB/s); accumulation order stays p-ascending, so results are unchanged.
     int p = p_begin + pl;
-    for (; p + 7 * a.PL < p_end; p += 8 * a.PL) {    // eight loads in flight
+    for (; p + 7 * a.PL < p_end; p += 8 * a.PL) {
       uint4 v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[u] = *gn_src(a, b, p + u * a.PL, o);
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        float f[8];
-        unpack8(v[u], f);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { s[k] += f[k]; q[k] += f[k] * f[k]; }
-      }
+      for (int u = 0; u < 8; ++u) gn_sum_sq(v[u], s, q);
     }
     for (; p + 3 * a.PL < p_end; p += 4 * a.PL) {
       uint4 v[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) v[u] = *gn_src(a, b, p + u * a.PL, o);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        float f[8];
-        unpack8(v[u], f);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { s[k] += f[k]; q[k] += f[k] * f[k]; }
-      }
+      for (int u = 0; u < 4; ++u) gn_sum_sq(v[u], s, q);
     }
-    for (; p < p_end; p += a.PL) {
-      float f[8];
-      unpack8(*gn_src(a, b, p, o), f);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { s[k] += f[k]; q[k] += f[k] * f[k]; }
-    }
+    for (; p < p_end; p += a.PL) gn_sum_sq(*gn_src(a, b, p, o), s, q);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       red[((pl * a.C) + o * 8 + k) * 2 + 0] = s[k];
@@ -117,45 +102,17 @@ __global__ void gn_apply_kernel(const GnArgs a) {
     if (live && p < p_end) pre[u] = *gn_src(a, b, p, o);
   }
   float gmr[8], btr[8];
-  if (live && !a.out8) {
-    const float4 g0 = *(const float4*)(a.gamma + o * 8), g1 = *(const float4*)(a.gamma + o * 8 + 4);
-    const float4 b0 = *(const float4*)(a.beta + o * 8), b1 = *(const float4*)(a.beta + o * 8 + 4);
-    gmr[0] = g0.x; gmr[1] = g0.y; gmr[2] = g0.z; gmr[3] = g0.w; gmr[4] = g1.x; gmr[5] = g1.y; gmr[6] = g1.z; gmr[7] = g1.w;
-    btr[0] = b0.x; btr[1] = b0.y; btr[2] = b0.z; btr[3] = b0.w; btr[4] = b1.x; btr[5] = b1.y; btr[6] = b1.z; btr[7] = b1.w;
-  }
-  // statistics: the image's `chunks` partials per group, summed by eight threads per group (each a contiguous run of chunks in
-  // ascending order, then the eight runs in ascending order: a fixed order).  Summed by one thread per group this prologue was a
-  // chain of 8-16 dependent load batches per block and paced the whole kernel (37 -> 28 us on 64x64 x 320 with it gone).
+  if (live && !a.out8) { load8f(a.gamma + o * 8, gmr); load8f(a.beta + o * 8, btr); }
+  // statistics: the eight-runs order whenever the block has eight threads per group
   __shared__ float2 run_s[64][8];
-  const bool wide_red = blockDim.x >= (unsigned)a.G * 8u;
-  if (wide_red) {
-    if (tid < a.G * 8) {
-      const int g = tid >> 3, sub = tid & 7;
-      const int per = (a.chunks + 7) >> 3, c0 = sub * per, c1 = min(a.chunks, c0 + per);
-      const float2* src = (const float2*)(a.partial + ((long)b * a.G + g) * a.chunks * 2);
-      float ss = 0.f, qq = 0.f;
-      for (int c = c0; c < c1; ++c) { const float2 v = src[c]; ss += v.x; qq += v.y; }
-      run_s[g][sub] = float2{ss, qq};
-    }
-    __syncthreads();
-  }
+  const float2 sums = gn_chunk_sums(a.partial, a.chunks, a.G, b, blockDim.x >= (unsigned)a.G * 8u, run_s);
   if (tid < a.G) {
-    float ss = 0.f, qq = 0.f;
-    if (wide_red) {
-#pragma unroll
-      for (int sub = 0; sub < 8; ++sub) { ss += run_s[tid][sub].x; qq += run_s[tid][sub].y; }
-    } else {
-      const float2* src = (const float2*)(a.partial + ((long)b * a.G + tid) * a.chunks * 2);      // contiguous (gn_stats_kernel)
-      for (int c = 0; c < a.chunks; ++c) { ss += src[c].x; qq += src[c].y; }
-    }
-    const float n = (float)a.HW * (float)cpg;
-    const float mean = ss / n;
-    const float var = fmaxf(qq / n - mean * mean, 0.f);
-    mean_s[tid] = mean;
-    rstd_s[tid] = rsqrtf(var + a.eps);
+    const float2 mr = gn_mean_rstd(sums, (float)a.HW * (float)cpg, a.eps);
+    mean_s[tid] = mr.x;
+    rstd_s[tid] = mr.y;
     if (a.stats_out && blockIdx.x == 0) {
-      a.stats_out[((long)b * a.G + tid) * 2 + 0] = mean;
-      a.stats_out[((long)b * a.G + tid) * 2 + 1] = rstd_s[tid];
+      a.stats_out[((long)b * a.G + tid) * 2 + 0] = mr.x;
+      a.stats_out[((long)b * a.G + tid) * 2 + 1] = mr.y;
     }
   }
   __syncthreads();
@@ -174,10 +131,10 @@ __global__ void gn_apply_kernel(const GnArgs a) {
     unpack8(raw, f);
     if (a.out8) {                                    // e4m3 of the normalised value under the static scale (GnArgs::out8)
 #pragma unroll
-      for (int k = 0; k < 8; ++k) f[k] = __builtin_amdgcn_fmed3f(f[k] * sc[k] + sh[k], -448.f, 448.f);
+      for (int k = 0; k < 8; ++k) f[k] = sat_e4m3(f[k] * sc[k] + sh[k]);
       uint2 w;
-      w.x = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false), true);
-      w.y = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], 0, false), true);
+      w.x = pack4_e4m3(f[0], f[1], f[2], f[3]);
+      w.y = pack4_e4m3(f[4], f[5], f[6], f[7]);
       *(uint2*)(a.out8 + ((long)(b * a.HW + p) * a.C + o * 8)) = w;
       return;
     }
@@ -205,8 +162,7 @@ __global__ void gn_apply_kernel(const GnArgs a) {
 }
 
 // one wave per R token rows; exact two-pass variance in registers (C <= 8*64*MAXO).  The loads of all R rows (and gamma / beta)
-// are issued before anything is reduced: with one 640-byte row per wave the chip had ~5 MB in flight, half of what 5 TB/s
-// needs at ~2 us of loaded latency.
+// are issued before anything is reduced (norm_steps.h).
 template <int MAXO, int R>
 __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, bf16_t* __restrict__ y,
@@ -216,45 +172,31 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
   if (row0 >= M) return;
   const int C8 = C >> 3;
   uint4 raw[R][MAXO];
-#pragma unroll
-  for (int r = 0; r < R; ++r)
-#pragma unroll
-    for (int i = 0; i < MAXO; ++i) {
-      const int o = lane + i * 64;
-      raw[r][i] = make_uint4(0u, 0u, 0u, 0u);
-      if (o < C8 && row0 + r < M) raw[r][i] = *(const uint4*)(x + (long)(row0 + r) * C + o * 8);
-    }
+  ln_load_rows<MAXO, R>(x, row0, M, C, lane, raw);
   float gg[MAXO][8], bb[MAXO][8];
 #pragma unroll
   for (int i = 0; i < MAXO; ++i) {
     const int o = lane + i * 64;
-    if (o < C8) {
-      const float4 g0 = *(const float4*)(gamma + o * 8), g1 = *(const float4*)(gamma + o * 8 + 4);
-      const float4 b0 = *(const float4*)(beta + o * 8), b1 = *(const float4*)(beta + o * 8 + 4);
-      gg[i][0] = g0.x; gg[i][1] = g0.y; gg[i][2] = g0.z; gg[i][3] = g0.w; gg[i][4] = g1.x; gg[i][5] = g1.y; gg[i][6] = g1.z; gg[i][7] = g1.w;
-      bb[i][0] = b0.x; bb[i][1] = b0.y; bb[i][2] = b0.z; bb[i][3] = b0.w; bb[i][4] = b1.x; bb[i][5] = b1.y; bb[i][6] = b1.z; bb[i][7] = b1.w;
-    }
+    if (o < C8) { load8f(gamma + o * 8, gg[i]); load8f(beta + o * 8, bb[i]); }
   }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     if (row0 + r >= M) break;
     float v[MAXO][8];
-    float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < MAXO; ++i) {
-      unpack8(raw[r][i], v[i]);                    // lanes past C8 hold zeros
-      if (lane + i * 64 < C8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += v[i][k];
-      }
-    }
-    const float mean = wave_sum(s) / (float)C;
+    for (int i = 0; i < MAXO; ++i) unpack8(raw[r][i], v[i]);
+    ln_centre<MAXO>(v, lane, C);
     float q = 0.f;
+    {
+      // every square is ROUNDED before it is added: what this kernel has always computed (the compiler multiplied in pairs,
+      // v_pk_mul_f32, and added the products one by one), but only by its own choice; stated here
+#pragma clang fp contract(off)
 #pragma unroll
-    for (int i = 0; i < MAXO; ++i) {
-      if (lane + i * 64 < C8) {
+      for (int i = 0; i < MAXO; ++i) {
+        if (lane + i * 64 < C8) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) { const float d = v[i][k] - mean; q += d * d; }
+          for (int k = 0; k < 8; ++k) q += v[i][k] * v[i][k];
+        }
       }
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
@@ -264,7 +206,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
       if (o < C8) {
         float f[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) f[k] = (v[i][k] - mean) * rstd * gg[i][k] + bb[i][k];
+        for (int k = 0; k < 8; ++k) f[k] = v[i][k] * rstd * gg[i][k] + bb[i][k];
         *(uint4*)(y + (long)(row0 + r) * C + o * 8) = pack8(f);
       }
     }
@@ -307,11 +249,8 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const GnArgs a) {
       s += (v[u][0] + v[u][1]) + (v[u][2] + v[u][3]);
     }
   }
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
   const float n = (float)a.HW * (float)cpg;
-  const float mean = ((red[0] + red[1]) + (red[2] + red[3])) / n;
+  const float mean = block_sum4(s, red) / n;
   float q = 0.f;
 #pragma unroll
   for (int u = 0; u < UNITS; ++u)
@@ -319,10 +258,7 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const GnArgs a) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) { const float d = v[u][k] - mean; q += d * d; }
     }
-  q = wave_sum(q);
-  if ((tid & 63) == 0) red[4 + (tid >> 6)] = q;
-  __syncthreads();
-  const float rstd = rsqrtf(((red[4] + red[5]) + (red[6] + red[7])) / n + a.eps);
+  const float rstd = rsqrtf(block_sum4(q, red + 4) / n + a.eps);
   if (a.stats_out && tid == 0) { a.stats_out[((long)b * a.G + g) * 2] = mean; a.stats_out[((long)b * a.G + g) * 2 + 1] = rstd; }
   if (a.out8) {                                      // e4m3 of the normalised value under the static scale (GnArgs::out8)
     uint8_t* dst8 = a.out8 + (long)b * a.HW * a.C + cg;
@@ -332,9 +268,8 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const GnArgs a) {
       if (pix[u] >= 0) {
         float y[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) y[k] = __builtin_amdgcn_fmed3f((v[u][k] - mean) * w, -448.f, 448.f);
-        *(unsigned*)(dst8 + (long)pix[u] * a.C + ch[u]) =
-            (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false), true);
+        for (int k = 0; k < 4; ++k) y[k] = sat_e4m3((v[u][k] - mean) * w);
+        *(unsigned*)(dst8 + (long)pix[u] * a.C + ch[u]) = pack4_e4m3(y[0], y[1], y[2], y[3]);
       }
     return;
   }
@@ -363,8 +298,8 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const GnArgs a) {
 // (2 VGPRs per unit), the statistics are reduced in a fixed order through LDS (two-pass variance), one read, one write.
 //   threads = PPB pixel lanes x UPPB units per pixel (UPPB = GQ * cpg / 4), thread -> (pp = tid / UPPB, j = tid % UPPB)
 //   MAXT: largest block the instantiation is launched with.  More than 16 units per thread (64+ VGPRs of slab plus as many load addresses
-//   in flight) do not fit the 128 VGPRs of a 1024-thread block (the 24- / 32-unit variants spilled 22 / 72 registers): those run with at
-//   most 512 threads (256 VGPRs), the launcher picks the geometry accordingly.
+//   in flight) do not fit the 128 VGPRs of a 1024-thread block (the 24-unit variant spilled 22 registers): it runs with at
+//   most 512 threads (256 VGPRs), gn_select picks the geometry accordingly.
 template <int UNITS, int MAXT = 1024>
 __global__ __launch_bounds__(MAXT) void gn_mid_kernel(const GnArgs a, const int gq, const int ppb) {
   __shared__ float red[MAXT];
@@ -446,15 +381,12 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const GnFoldArgs a, const 
   __shared__ float mean_s[64], rstd_s[64];
   const int tid = threadIdx.x, b = blockIdx.y;
   const int cpg = a.C / a.G;
+  // the one-thread order, always: a 256-thread block has eight threads per group, but this kernel never summed in eight runs
+  const float2 sums = gn_chunk_sums(partial, chunks, a.G, b, false, nullptr);
   if (tid < a.G) {
-    const float2* src = (const float2*)(partial + ((long)b * a.G + tid) * chunks * 2);
-    float ss = 0.f, qq = 0.f;
-    for (int c = 0; c < chunks; ++c) { ss += src[c].x; qq += src[c].y; }
-    const float n = (float)a.HW * (float)cpg;
-    const float mean = ss / n;
-    const float var = fmaxf(qq / n - mean * mean, 0.f);
-    mean_s[tid] = mean;
-    rstd_s[tid] = rsqrtf(var + a.eps);
+    const float2 mr = gn_mean_rstd(sums, (float)a.HW * (float)cpg, a.eps);
+    mean_s[tid] = mr.x;
+    rstd_s[tid] = mr.y;
   }
   __syncthreads();
   const int wave = tid >> 6, lane = tid & 63;
@@ -489,25 +421,50 @@ __global__ __launch_bounds__(256) void gn_fold_kernel(const GnFoldArgs a, const 
 
 namespace dfh {
 
-static void gn_geometry(GnArgs& a, int* block, int* achunks) {
-  const int C8 = a.C / 8;
-  int PL = 256 / C8;
-  if (PL < 1) PL = 1;
-  if (PL > a.HW) PL = a.HW;
-  a.PL = PL;
-  *block = ((C8 * PL + 63) / 64) * 64;
-  // statistics: enough chunks to fill the chip, at most GN_MAX_CHUNKS (partial buffer size)
-  const int env_sc = WalkKnobs::get().gn_sc, env_ac = WalkKnobs::get().gn_ac;    // DFH_GN_SC / DFH_GN_AC: probe knobs
-  int chunks = (env_sc + a.B - 1) / a.B;
-  const int max_by_pix = (a.HW + PL - 1) / PL;
-  chunks = std::max(1, std::min({chunks, max_by_pix, (int)GN_MAX_CHUNKS}));
-  a.pix_per_chunk = (a.HW + chunks - 1) / chunks;
-  a.chunks = (a.HW + a.pix_per_chunk - 1) / a.pix_per_chunk;
-  int ac = (env_ac + a.B - 1) / a.B;
-  ac = std::max(1, std::min(ac, max_by_pix));
-  a.apix_per_chunk = (a.HW + ac - 1) / ac;
-  *achunks = (a.HW + a.apix_per_chunk - 1) / a.apix_per_chunk;
+namespace {
+// Which kernels a GroupNorm runs as: a pure function of the shape and the probe switches.
+enum GnPath { GN_PRODUCER_STATS, GN_ONE_SLAB, GN_GROUP_QUAD, GN_TWO_KERNEL };
+struct GnPlan {
+  GnPath path;
+  int units;                 // the UNITS instantiation of gn_small_kernel / gn_mid_kernel
+  int gq, ppb, threads;      // gn_mid_kernel: groups per block, pixel lanes per block, block size
+};
+
+GnPlan gn_select(const GnArgs& a, const WalkKnobs& knobs) {
+  // the producer's epilogue already summed the tensor (one source, its own group structure): normalise only
+  if (a.pre) return {GN_PRODUCER_STATS, 0, 0, 0, 0};
+  const int cpg = a.C / a.G, upp = cpg >> 2;
+  // small tensors (16x16 / 8x8 levels), one (image, group) slab per block.  DFH_GN_SMALL_MAX, probe knob; > 16 units per thread
+  // (32x32 x 640) the two-kernel path is faster since its prologue fix: 25.6 -> 21.3 us
+  const long slab = (long)a.HW * upp;
+  const bool one_source_per_group = a.C1 == 0 || a.C0 % cpg == 0;
+  if ((cpg & 3) == 0 && slab <= 256 * knobs.gn_small_max && one_source_per_group && (long)a.B * a.G >= 64)
+    return {GN_ONE_SLAB, slab <= 256 * 8 ? 8 : slab <= 256 * 16 ? 16 : 32, 0, 0, 256};
+  // mid path (16x16 / 8x8 tensors the one-slab kernel cannot take: groups that straddle the two concat sources, e.g. 1280 + 640
+  // channels): GQ adjacent groups per block.  Measured against the alternatives (scripts/norm_microbench.py): 24.4 -> 13.4 us
+  // on 16x16 x (1280 + 640); where gn_small_kernel is eligible it is faster (its blocks are four waves, the reductions here
+  // run across up to sixteen), and at 32x32 the two-kernel path is, so this is the fallback between them.  DFH_GN_MID=0: off.
+  if (knobs.gn_mid && !a.out8 && (cpg & 3) == 0 && a.HW <= 256 && a.G % 2 == 0) {
+    for (int gq = 4; gq >= 2; gq >>= 1) {
+      if (a.G % gq || (long)a.B * (a.G / gq) < 128 || gq * upp > 256) continue;
+      const int uppb = gq * upp;
+      int threads = 256;
+      auto units_at = [&](int t) { return t / uppb < 1 ? 1 << 30 : (a.HW + t / uppb - 1) / (t / uppb); };
+      while (threads < 1024 && units_at(threads) > 24) threads *= 2;
+      // 1024-thread blocks hold at most 16 units per thread in registers (128 VGPRs); 17..24 units run as 512-thread blocks
+      if (threads == 1024 && units_at(1024) > 16) threads = 512;
+      const int ppb = threads / uppb;
+      if (ppb < 1) continue;
+      const int units = (a.HW + ppb - 1) / ppb;
+      // more than the widest instantiation holds: refused.  (25..32 never comes out of the rule above -- only the 1024 -> 512 step
+      // could give it, and that takes units_at(1024) > 16 with units_at(512) <= 32 -- so this refuses what `units > 32` did.)
+      if (units > 24) continue;
+      return {GN_GROUP_QUAD, units <= 4 ? 4 : units <= 8 ? 8 : units <= 16 ? 16 : 24, gq, ppb, threads};
+    }
+  }
+  return {GN_TWO_KERNEL, 0, 0, 0, 0};
 }
+}  // namespace
 
 int groupnorm_launch(GnArgs a, hipStream_t stream) {
   a.C = a.C0 + a.C1;
@@ -519,75 +476,38 @@ int groupnorm_launch(GnArgs a, hipStream_t stream) {
   DFH_REQUIRE((a.partial != nullptr || a.pre != nullptr) && (a.out != nullptr || a.out8 != nullptr) && a.src0 != nullptr, "null pointer");
   if (a.out8) DFH_REQUIRE(a.C1 == 0 && !a.silu && a.q_mul > 0.f && !a.stats_out, "e4m3 GroupNorm output: one source, no SiLU, a positive scale");
   DFH_REQUIRE(a.C1 == 0 || a.src1 != nullptr, "second source missing");
-  if (a.pre) {
-    // the producer's epilogue already summed the tensor (one source, its own group structure): normalise only
-    DFH_REQUIRE(a.C1 == 0 && a.pre_chunks > 0 && a.pre_chunks <= (int)GN_MAX_CHUNKS, "producer statistics: one source, 1..64 chunks");
-    int block, achunks;
-    gn_geometry(a, &block, &achunks);
-    DFH_REQUIRE(block <= 512, "block too large (more than 4096 channels)");
-    a.partial = const_cast<float*>(a.pre); a.chunks = a.pre_chunks;
-    ProfScope ps(PC_GNORM, 0.0, (a.out8 ? 3.0 : 4.0) * a.B * (double)a.HW * a.C, stream);
-    census(CK_GN_PRE);
-    hipLaunchKernelGGL(gn_apply_kernel, dim3(achunks, a.B), dim3(block), 0, stream, a);
-    return check_launch("gn_apply_kernel");
-  }
-  {
-    const int cpg = a.C / a.G;
-    const long units = (long)a.HW * (cpg >> 2);
-    const bool one_source_per_group = a.C1 == 0 || a.C0 % cpg == 0;
-    const int small_max = WalkKnobs::get().gn_small_max;   // DFH_GN_SMALL_MAX, probe knob; > 16 units per thread (32x32 x 640) the two-kernel path is faster since its prologue fix: 25.6 -> 21.3 us
-    if ((cpg & 3) == 0 && units <= 256 * small_max && one_source_per_group && (long)a.B * a.G >= 64) {
-      ProfScope ps(PC_GNORM, 0.0, (a.out8 ? 3.0 : 4.0) * a.B * (double)a.HW * a.C, stream);
-      const dim3 grid(a.G, a.B);
+  if (a.pre) DFH_REQUIRE(a.C1 == 0 && a.pre_chunks > 0 && a.pre_chunks <= (int)GN_MAX_CHUNKS, "producer statistics: one source, 1..64 chunks");
+  const WalkKnobs& knobs = WalkKnobs::get();
+  const GnPlan plan = gn_select(a, knobs);
+  GnTwoKernel tk{};
+  if (plan.path == GN_PRODUCER_STATS || plan.path == GN_TWO_KERNEL)
+    if (int rc = gn_two_kernel_geometry(a, knobs.gn_sc, knobs.gn_ac, &tk)) return rc;    // DFH_GN_SC / DFH_GN_AC: probe knobs
+  ProfScope ps(PC_GNORM, 0.0, (a.out8 ? 3.0 : 4.0) * a.B * (double)a.HW * a.C, stream);   // algorithmic: one read + one write (bf16)
+  switch (plan.path) {
+    case GN_PRODUCER_STATS:
+      a.partial = const_cast<float*>(a.pre); a.chunks = a.pre_chunks;
+      census(CK_GN_PRE);
+      break;
+    case GN_ONE_SLAB: {
+      const auto kernel = plan.units == 8 ? gn_small_kernel<8> : plan.units == 16 ? gn_small_kernel<16> : gn_small_kernel<32>;
       census(CK_GN_SMALL);
-      if (units <= 256 * 8) hipLaunchKernelGGL(gn_small_kernel<8>, grid, dim3(256), 0, stream, a);
-      else if (units <= 256 * 16) hipLaunchKernelGGL(gn_small_kernel<16>, grid, dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL(gn_small_kernel<32>, grid, dim3(256), 0, stream, a);
+      hipLaunchKernelGGL(kernel, dim3(a.G, a.B), dim3(plan.threads), 0, stream, a);
       return check_launch("gn_small_kernel");
     }
-  }
-  {
-    // mid path (16x16 / 8x8 tensors the one-slab kernel cannot take: groups that straddle the two concat sources, e.g. 1280 + 640
-    // channels): GQ adjacent groups per block.  Measured against the alternatives (scripts/norm_microbench.py): 24.4 -> 13.4 us
-    // on 16x16 x (1280 + 640); where gn_small_kernel is eligible it is faster (its blocks are four waves, the reductions here
-    // run across up to sixteen), and at 32x32 the two-kernel path is, so this is the fallback between them.
-    const bool mid_off = !WalkKnobs::get().gn_mid;     // DFH_GN_MID=0
-    const int cpg = a.C / a.G, upp = cpg >> 2;
-    if (!mid_off && !a.out8 && (cpg & 3) == 0 && a.HW <= 256 && a.G % 2 == 0) {
-      for (int gq = 4; gq >= 2; gq >>= 1) {
-        if (a.G % gq || (long)a.B * (a.G / gq) < 128 || gq * upp > 256) continue;
-        const int uppb = gq * upp;
-        int threads = 256;
-        auto units_at = [&](int t) { return t / uppb < 1 ? 1 << 30 : (a.HW + t / uppb - 1) / (t / uppb); };
-        while (threads < 1024 && units_at(threads) > 24) threads *= 2;
-        // 1024-thread blocks hold at most 16 units per thread in registers (128 VGPRs); 17..32 units run as 512-thread blocks
-        if (threads == 1024 && units_at(1024) > 16) threads = 512;
-        const int ppb = threads / uppb;
-        if (ppb < 1) continue;
-        const int units = (a.HW + ppb - 1) / ppb;
-        if (units > 32) continue;
-        ProfScope ps(PC_GNORM, 0.0, 4.0 * a.B * (double)a.HW * a.C, stream);
-        const dim3 grid(a.G / gq, a.B), block(threads);
-        census(CK_GN_MID);
-        if (units <= 4) hipLaunchKernelGGL(gn_mid_kernel<4>, grid, block, 0, stream, a, gq, ppb);
-        else if (units <= 8) hipLaunchKernelGGL(gn_mid_kernel<8>, grid, block, 0, stream, a, gq, ppb);
-        else if (units <= 16) hipLaunchKernelGGL(gn_mid_kernel<16>, grid, block, 0, stream, a, gq, ppb);
-        else if (units <= 24) hipLaunchKernelGGL((gn_mid_kernel<24, 512>), grid, block, 0, stream, a, gq, ppb);      // threads <= 512 here
-        else hipLaunchKernelGGL((gn_mid_kernel<32, 512>), grid, block, 0, stream, a, gq, ppb);
-        return check_launch("gn_mid_kernel");
-      }
+    case GN_GROUP_QUAD: {
+      const auto kernel = plan.units == 4 ? gn_mid_kernel<4> : plan.units == 8 ? gn_mid_kernel<8> : plan.units == 16 ? gn_mid_kernel<16>
+                                                                                                  : gn_mid_kernel<24, 512>;   // threads <= 512 there
+      census(CK_GN_MID);
+      hipLaunchKernelGGL(kernel, dim3(a.G / plan.gq, a.B), dim3(plan.threads), 0, stream, a, plan.gq, plan.ppb);
+      return check_launch("gn_mid_kernel");
     }
+    case GN_TWO_KERNEL:
+      census(CK_GN_STATS);
+      hipLaunchKernelGGL(gn_stats_kernel, dim3(a.chunks, a.B), dim3(tk.block), tk.lds, stream, a);
+      if (int rc = check_launch("gn_stats_kernel")) return rc;
+      break;
   }
-  int block, achunks;
-  gn_geometry(a, &block, &achunks);
-  DFH_REQUIRE(block <= 512, "block too large (more than 4096 channels)");
-  const size_t lds = (size_t)a.PL * a.C * 2 * sizeof(float);
-  DFH_REQUIRE(lds <= 64 * 1024, "GroupNorm LDS reduction too large");
-  ProfScope ps(PC_GNORM, 0.0, (a.out8 ? 3.0 : 4.0) * a.B * (double)a.HW * a.C, stream);   // algorithmic: one read + one write (bf16)
-  census(CK_GN_STATS);
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(a.chunks, a.B), dim3(block), lds, stream, a);
-  if (int rc = check_launch("gn_stats_kernel")) return rc;
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(achunks, a.B), dim3(block), 0, stream, a);
+  hipLaunchKernelGGL(gn_apply_kernel, dim3(tk.achunks, a.B), dim3(tk.block), 0, stream, a);
   return check_launch("gn_apply_kernel");
 }
 
@@ -599,14 +519,11 @@ int groupnorm_fold_launch(GnFoldArgs f, hipStream_t stream) {
   if (!partial) {
     GnArgs a; std::memset(&a, 0, sizeof(a));
     a.src0 = f.x; a.C0 = a.C = f.C; a.B = f.B; a.HW = f.HW; a.G = f.G; a.partial = f.partial;
-    int block, achunks;
-    gn_geometry(a, &block, &achunks);
-    DFH_REQUIRE(block <= 512, "block too large (more than 4096 channels)");
-    const size_t lds = (size_t)a.PL * a.C * 2 * sizeof(float);
-    DFH_REQUIRE(lds <= 64 * 1024, "GroupNorm LDS reduction too large");
+    GnTwoKernel tk;
+    if (int rc = gn_two_kernel_geometry(a, WalkKnobs::get().gn_sc, WalkKnobs::get().gn_ac, &tk)) return rc;
     ProfScope ps(PC_GNORM, 0.0, 2.0 * a.B * (double)a.HW * a.C, stream);        // one read of the tensor
     census(CK_GN_STATS);
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(a.chunks, a.B), dim3(block), lds, stream, a);
+    hipLaunchKernelGGL(gn_stats_kernel, dim3(a.chunks, a.B), dim3(tk.block), tk.lds, stream, a);
     if (int rc = check_launch("gn_stats_kernel")) return rc;
     partial = f.partial; chunks = a.chunks;
   } else {

@@ -9,14 +9,9 @@
 //   dx = rstd * (gamma*dz - s1/n - x^ * s2/n)
 #include "dfh_common.h"
 #include "norm.h"
+#include "norm_steps.h"
 
 namespace {
-
-DFH_DEVICE const uint4* gnb_src(const GnBwdArgs& a, int b, int p, int o) {
-  const int o0 = a.C0 >> 3;
-  if (o < o0) return (const uint4*)(a.src0 + ((long)(b * a.HW + p) * a.C0 + o * 8));
-  return (const uint4*)(a.src1 + ((long)(b * a.HW + p) * a.C1 + (o - o0) * 8));
-}
 
 // d/dz silu(z) = s (1 + z (1 - s)), s = sigmoid(z): hardware reciprocal instead of an IEEE division (~10 VALU instructions; these
 // kernels run two passes over 2.9 G elements per training step and are VALU-heavy), as silu_f in dfh_common.h
@@ -58,13 +53,13 @@ __global__ __launch_bounds__(512) void gn_bwd_stats_kernel(const GnBwdArgs a) {
       uint4 xr[4], dr[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        xr[u] = *gnb_src(a, b, p + u * a.PL, o);
+        xr[u] = *gn_src(a, b, p + u * a.PL, o);
         dr[u] = *(const uint4*)(a.dy + ((long)(b * a.HW + p + u * a.PL) * a.C + o * 8));
       }
 #pragma unroll
       for (int u = 0; u < 4; ++u) accum(xr[u], dr[u]);
     }
-    for (; p < p_end; p += a.PL) accum(*gnb_src(a, b, p, o), *(const uint4*)(a.dy + ((long)(b * a.HW + p) * a.C + o * 8)));
+    for (; p < p_end; p += a.PL) accum(*gn_src(a, b, p, o), *(const uint4*)(a.dy + ((long)(b * a.HW + p) * a.C + o * 8)));
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       red[((pl * a.C) + o * 8 + k) * 2 + 0] = A[k];
@@ -95,31 +90,12 @@ __global__ __launch_bounds__(512) void gn_bwd_apply_kernel(const GnBwdArgs a) {
   const int tid = threadIdx.x;
   const int o = tid % C8, pl = tid / C8;
   const int b = blockIdx.y;
-  // the image's partials per group, summed by eight threads per group in a fixed order (see gn_apply_kernel in norm.hip)
+  // the image's partials per group: the eight-runs order whenever the block has eight threads per group, as gn_apply_kernel
   __shared__ float2 run_s[64][8];
-  const bool wide_red = blockDim.x >= (unsigned)a.G * 8u;
-  if (wide_red) {
-    if (tid < a.G * 8) {
-      const int g = tid >> 3, sub = tid & 7;
-      const int per = (a.chunks + 7) >> 3, c0 = sub * per, c1 = min(a.chunks, c0 + per);
-      const float2* src = (const float2*)(a.partial + ((long)b * a.G + g) * a.chunks * 2);
-      float s1 = 0.f, s2 = 0.f;
-      for (int c = c0; c < c1; ++c) { const float2 v = src[c]; s1 += v.x; s2 += v.y; }
-      run_s[g][sub] = float2{s1, s2};
-    }
-    __syncthreads();
-  }
+  const float2 sums = gn_chunk_sums(a.partial, a.chunks, a.G, b, blockDim.x >= (unsigned)a.G * 8u, run_s);
   if (tid < a.G) {
-    float s1 = 0.f, s2 = 0.f;
-    if (wide_red) {
-#pragma unroll
-      for (int sub = 0; sub < 8; ++sub) { s1 += run_s[tid][sub].x; s2 += run_s[tid][sub].y; }
-    } else {
-      const float2* src = (const float2*)(a.partial + ((long)b * a.G + tid) * a.chunks * 2);
-      for (int c = 0; c < a.chunks; ++c) { s1 += src[c].x; s2 += src[c].y; }
-    }
     const float n = (float)a.HW * (float)cpg;
-    s1_s[tid] = s1 / n; s2_s[tid] = s2 / n;
+    s1_s[tid] = sums.x / n; s2_s[tid] = sums.y / n;
   }
   __syncthreads();
   if (pl >= a.PL) return;
@@ -156,7 +132,7 @@ __global__ __launch_bounds__(512) void gn_bwd_apply_kernel(const GnBwdArgs a) {
     uint4 xr[4], dr[4], rr[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-      xr[u] = *gnb_src(a, b, p + u * a.PL, o);
+      xr[u] = *gn_src(a, b, p + u * a.PL, o);
       dr[u] = *(const uint4*)(a.dy + ((long)(b * a.HW + p + u * a.PL) * a.C + o * 8));
       rr[u] = make_uint4(0u, 0u, 0u, 0u);
       if (acc) rr[u] = *dst_of(p + u * a.PL);
@@ -167,7 +143,7 @@ __global__ __launch_bounds__(512) void gn_bwd_apply_kernel(const GnBwdArgs a) {
   for (; p < p_end; p += a.PL) {
     uint4 rr = make_uint4(0u, 0u, 0u, 0u);
     if (acc) rr = *dst_of(p);
-    emit(*gnb_src(a, b, p, o), *(const uint4*)(a.dy + ((long)(b * a.HW + p) * a.C + o * 8)), rr, dst_of(p));
+    emit(*gn_src(a, b, p, o), *(const uint4*)(a.dy + ((long)(b * a.HW + p) * a.C + o * 8)), rr, dst_of(p));
   }
 }
 
@@ -208,6 +184,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
   for (int row = blockIdx.x * 64 + wave; row < r_end; row += 4) {
     float v[MAXO][8], d[MAXO][8];
     uint4 rcur[MAXO];
+    // (the row statistics are this kernel's own, not the steps of norm_steps.h: written over them its dx changed in the last bit for
+    // C > 512 and the C <= 1024 instantiations ran 3-4 % slower)
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXO; ++i) {
@@ -287,26 +265,12 @@ int groupnorm_bwd_launch(GnBwdArgs a, hipStream_t stream) {
   DFH_REQUIRE(a.G > 0 && a.G <= 64 && a.C % a.G == 0, "bad group count");
   DFH_REQUIRE(a.src0 && a.dy && a.stats && a.gamma && a.beta && a.dx0 && a.dgamma && a.dbeta && a.partial, "null pointer");
   DFH_REQUIRE(a.C1 == 0 || (a.src1 && a.dx1), "second source / gradient missing");
-  const int C8 = a.C / 8;
-  int PL = 256 / C8;
-  if (PL < 1) PL = 1;
-  if (PL > a.HW) PL = a.HW;
-  a.PL = PL;
-  const int block = ((C8 * PL + 63) / 64) * 64;
-  DFH_REQUIRE(block <= 512, "block too large (more than 4096 channels)");
-  const int max_by_pix = (a.HW + PL - 1) / PL;
-  int chunks = std::max(1, std::min({(512 + a.B - 1) / a.B, max_by_pix, (int)GN_MAX_CHUNKS}));
-  a.pix_per_chunk = (a.HW + chunks - 1) / chunks;
-  a.chunks = (a.HW + a.pix_per_chunk - 1) / a.pix_per_chunk;
-  int ac = std::max(1, std::min((2048 + a.B - 1) / a.B, max_by_pix));
-  a.apix_per_chunk = (a.HW + ac - 1) / ac;
-  const int achunks = (a.HW + a.apix_per_chunk - 1) / a.apix_per_chunk;
-  const size_t lds = (size_t)a.PL * a.C * 2 * sizeof(float);
-  DFH_REQUIRE(lds <= 64 * 1024, "GroupNorm LDS reduction too large");
+  GnTwoKernel tk;
+  if (int rc = gn_two_kernel_geometry(a, 512, 2048, &tk)) return rc;
   ProfScope ps(PC_NORM_BWD, 0.0, 10.0 * a.B * (double)a.HW * a.C, stream);   // x, dy read twice, dx written
-  hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(a.chunks, a.B), dim3(block), lds, stream, a);
+  hipLaunchKernelGGL(gn_bwd_stats_kernel, dim3(a.chunks, a.B), dim3(tk.block), tk.lds, stream, a);
   if (int rc = check_launch("gn_bwd_stats_kernel")) return rc;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(achunks, a.B), dim3(block), 0, stream, a);
+  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(tk.achunks, a.B), dim3(tk.block), 0, stream, a);
   return check_launch("gn_bwd_apply_kernel");
 }
 

@@ -20,6 +20,7 @@
 // the fp64 conv of the same bf16 operands the relative L2 error of one conv is 4.9e-3, against 1.7e-3 for the direct kernel (whose
 // only error is the bf16 rounding of its output) -- tests/test_gpu_ops.py states the bound.
 #include "gemm.h"
+#include "norm_steps.h"
 
 namespace {
 
@@ -178,11 +179,8 @@ __global__ __launch_bounds__(256) void gn_wino_input_kernel(const GnWinoArgs a) 
     *(uint2*)(smem + p * RS + j * 8) = r;
     s += (h16lo(r.x) + h16hi(r.x)) + (h16lo(r.y) + h16hi(r.y));
   }
-  s = wave_sum(s);
-  if ((tid & 63) == 0) red[tid >> 6] = s;
-  __syncthreads();
   const float n = (float)HW * (float)cpg;
-  const float mean = ((red[0] + red[1]) + (red[2] + red[3])) / n;
+  const float mean = block_sum4(s, red) / n;                  // the barrier inside also publishes the slab
   // ---- pass 2: centred squares (each thread re-reads the units it wrote)
   float q = 0.f;
   for (int idx = tid; idx < total; idx += 256) {
@@ -192,10 +190,7 @@ __global__ __launch_bounds__(256) void gn_wino_input_kernel(const GnWinoArgs a) 
 #pragma unroll
     for (int k = 0; k < 4; ++k) { const float d = v[k] - mean; q += d * d; }
   }
-  q = wave_sum(q);
-  if ((tid & 63) == 0) red[4 + (tid >> 6)] = q;
-  __syncthreads();
-  const float rstd = rsqrtf(((red[4] + red[5]) + (red[6] + red[7])) / n + a.eps);
+  const float rstd = rsqrtf(block_sum4(q, red + 4) / n + a.eps);
   // ---- pass 3: normalise + SiLU in place, rounded to bf16
   for (int idx = tid; idx < total; idx += 256) {
     const int p = idx / upp, j = idx - p * upp;

@@ -158,7 +158,11 @@ def test_dgrad_conv3x3(cin, cout, H, stride, ups):
 
 
 # ----------------------------------------------------------------------------- normalisation backward
-@pytest.mark.parametrize("C0,C1,HW,silu,eps", [(320, 0, 256, 1, 1e-5), (640, 320, 64, 1, 1e-5), (64, 0, 4, 0, 1e-6), (32, 32, 256, 1, 1e-5)])
+@pytest.mark.parametrize("C0,C1,HW,silu,eps", [(320, 0, 256, 1, 1e-5), (640, 320, 64, 1, 1e-5), (64, 0, 4, 0, 1e-6), (32, 32, 256, 1, 1e-5),
+                                               # the widest concatenated tensor: C8 * PL rounds up to a block of 8 * G threads (the eight-runs order), 64 chunks
+                                               (1280, 640, 64, 0, 1e-6),
+                                               # one pixel: chunks == 1 under the eight-runs order (a 256-thread block)
+                                               (1280, 768, 1, 1, 1e-5)])
 def test_groupnorm_backward(C0, C1, HW, silu, eps):
     import math
     B, G = 3, 32

@@ -496,10 +496,17 @@ def test_conv3x3_with_fused_shortcut_and_temb(tile):
 
 
 # ----------------------------------------------------------------------------- normalisation
-@pytest.mark.parametrize("C0,C1,HW,silu,eps", [(320, 0, 256, 1, 1e-5), (640, 320, 64, 1, 1e-5), (1280, 1280, 16, 1, 1e-5),
-                                               (64, 0, 4, 0, 1e-6), (32, 32, 256, 1, 1e-5), (1280, 640, 64, 0, 1e-6)])
-def test_groupnorm_silu(C0, C1, HW, silu, eps):
-    B, G = 3, 32
+# B = 8 / 16 cases: the smallest shapes that reach each gn_mid_kernel instantiation (groups of 16+ channels that straddle the two sources
+# keep the one-slab kernel out; B * (G / gq) >= 128 picks gq = 2 at B = 8 and gq = 4 at B = 16): <4>, <8>, <16> at 512 threads,
+# <24, 512>, and <16> with gq = 4
+_GN_MID_CASES = [(8, 264, 248, 16, 1, 1e-5), (8, 264, 248, 256, 1, 1e-5), (8, 1280, 640, 256, 1, 1e-5), (8, 1280, 1280, 256, 1, 1e-5),
+                 (16, 1280, 640, 64, 1, 1e-5)]
+
+
+@pytest.mark.parametrize("B,C0,C1,HW,silu,eps", [(3, 320, 0, 256, 1, 1e-5), (3, 640, 320, 64, 1, 1e-5), (3, 1280, 1280, 16, 1, 1e-5),
+                                                 (3, 64, 0, 4, 0, 1e-6), (3, 32, 32, 256, 1, 1e-5), (3, 1280, 640, 64, 0, 1e-6)] + _GN_MID_CASES)
+def test_groupnorm_silu(B, C0, C1, HW, silu, eps):
+    G = 32
     C = C0 + C1
     H = int(math.isqrt(HW))
     x0 = bf(rnd(B, C0, H, H, seed=31) * 2 + 0.7)
@@ -508,9 +515,12 @@ def test_groupnorm_silu(C0, C1, HW, silu, eps):
     out = torch.empty((B, HW, C), dtype=torch.bfloat16, device=DEV)
     part = torch.empty(B * 64 * G * 2, device=DEV)
     s0, s1 = gu.nhwc(x0), (gu.nhwc(x1) if C1 else None)      # keep the NHWC copies alive across the launch
+    _lib.census_reset()
     _lib.call("dfh_groupnorm", _lib.ptr(s0), C0, _lib.ptr(s1), C1, B, HW, G,
               _lib.ptr(gamma), _lib.ptr(beta), eps, silu, _lib.ptr(out), _lib.ptr(part), gu.stream())
     torch.cuda.synchronize()
+    if (B, C0, C1, HW, silu, eps) in _GN_MID_CASES:
+        assert _lib.census()["gn_mid"] == 1, _lib.census()
     xin = torch.cat([x0, x1], 1).float() if C1 else x0.float()
     ref = F.group_norm(xin, G, gamma, beta, eps)
     ref = F.silu(ref) if silu else ref
