@@ -20,6 +20,9 @@ from .image_processor import CLIPImageProcessor
 from .evalscores import (CLIPScore, CompatibilityEvaluator, FashionEvaluator, candidate_cosine, extract_image_features, lpips_given_data,
                          lpips_retrieval, pair_cosine)
 from .lpips import LPIPS
+from .evalscores import (activation_statistics, fid_given_data, frechet_distance, inception_rows, inception_score_from_probs,
+                         inception_score_given_data)
+from .inception import FIDInceptionV3, InceptionV3
 from .difashion import DiFashion
 
 __all__ = [
@@ -29,4 +32,6 @@ __all__ = [
     "CLIPVisionModelWithProjection", "CLIPVisionModelOutput", "CLIPTextModelWithProjection", "CLIPTextModelOutput", "CLIPScore",
     "CompatibilityEvaluator", "FashionEvaluator", "pair_cosine", "candidate_cosine", "CLIPImageProcessor", "extract_image_features",
     "LPIPS", "lpips_given_data", "lpips_retrieval",
+    "FIDInceptionV3", "InceptionV3", "activation_statistics", "frechet_distance", "fid_given_data", "inception_rows",
+    "inception_score_from_probs", "inception_score_given_data",
 ]

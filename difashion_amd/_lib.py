@@ -71,6 +71,16 @@ class LpipsConfigC(C.Structure):
     _fields_ = [("net", C.c_int)]
 
 
+class IncepConfigC(C.Structure):
+    _fields_ = [("variant", C.c_int), ("num_classes", C.c_int), ("resize_input", C.c_int), ("normalize_input", C.c_int), ("block_mask", C.c_int)]
+
+
+class IncepLaunchC(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kind", "conv", "pool_mode", "block", "KH", "KW", "stride", "padH", "padW", "Hin", "Win", "Cin", "Hout", "Wout",
+                                       "Cout", "ldc", "offset", "src_region", "dst_region")] + \
+               [(n, C.c_size_t) for n in ("src_off", "src_floats", "dst_off", "dst_floats")] + [("name", C.c_char * 48)]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [
         ("conv_src", C.c_void_p), ("conv_c", C.c_int), ("conv", C.c_int),
@@ -205,6 +215,26 @@ SIGNATURES = {
     "dfh_lpips_conv3x3_relu": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "dfh_lpips_maxpool2x2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "dfh_lpips_layer_score": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "dfh_incep_create": (_i, [C.POINTER(IncepConfigC), C.POINTER(_vp)]),
+    "dfh_incep_destroy": (None, [_vp]),
+    "dfh_incep_num_params": (_i, [_vp]),
+    "dfh_incep_param_name": (C.c_char_p, [_vp, _i]),
+    "dfh_incep_param_ndim": (_i, [_vp, _i]),
+    "dfh_incep_param_dim": (_i, [_vp, _i, _i]),
+    "dfh_incep_packed_bytes": (_sz, [_vp]),
+    "dfh_incep_pack": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp]),
+    "dfh_incep_plan_count": (_i, [_vp, _i, _i, _i]),
+    "dfh_incep_plan_entry": (_i, [_vp, _i, _i, _i, _i, C.POINTER(IncepLaunchC)]),
+    "dfh_incep_workspace_bytes": (_sz, [_vp, _i, _i, _i]),
+    "dfh_incep_forward": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _i, C.POINTER(_vp), _vp, _vp, _sz, _vp]),
+    "dfh_incep_prep": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "dfh_incep_conv_bn_relu": (_i, [_vp, _vp, _i, C.POINTER(_vp), _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "dfh_incep_pool": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "dfh_incep_global_mean": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "dfh_incep_fc_softmax": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "dfh_incep_is_rows": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "dfh_incep_is_splits": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "dfh_incep_stats": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "dfh_vae_create": (_i, [C.POINTER(VAEConfigC), C.POINTER(_vp)]),
     "dfh_vae_destroy": (None, [_vp]),
     "dfh_vae_num_params": (_i, [_vp]),
@@ -318,7 +348,8 @@ _NO_STATUS = {"dfh_abi_version", "dfh_census_count", "dfh_unet_num_params", "dfh
               "dfh_vae_param_ndim", "dfh_vae_param_dim", "dfh_clip_num_params", "dfh_clip_param_ndim", "dfh_clip_param_dim",
               "dfh_clipv_num_params", "dfh_clipv_param_ndim", "dfh_clipv_param_dim", "dfh_lpips_num_params", "dfh_lpips_param_ndim", "dfh_lpips_param_dim",
               "dfh_imgproc_resized_height", "dfh_imgproc_resized_width", "dfh_imgproc_out_height", "dfh_imgproc_out_width", "dfh_imgproc_crop_top",
-              "dfh_imgproc_crop_left", "dfh_imgproc_ksize_x", "dfh_imgproc_ksize_y"}
+              "dfh_imgproc_crop_left", "dfh_imgproc_ksize_x", "dfh_imgproc_ksize_y",
+              "dfh_incep_num_params", "dfh_incep_param_ndim", "dfh_incep_param_dim"}
 
 _lib = None
 _UNBOUND = set()

@@ -9,7 +9,10 @@ What the reference computes from the CLIP embeddings once ``encode_image`` / ``e
     (Evaluation/compatibility_evaluator/compatibility_net.py:14-81), which the reference runs one outfit at a time.
 And, over images and not embeddings:
   * ``calculate_lpips_given_data`` (:473-501) and the two ``calculate_lpips_retrieval_acc_given_data*`` (:769-821) over an ``LPIPS`` model
-    (lpips.py): ``lpips_given_data`` and ``lpips_retrieval`` below, batch by batch without the DataLoader.
+    (lpips.py, DESIGN.md row f8): ``lpips_given_data`` and ``lpips_retrieval`` below, batch by batch without the DataLoader;
+  * ``calculate_fid_given_data`` (:282-337) and ``calculate_inception_score_given_data`` (:339-406) over the two Inception v3 models
+    (inception.py): ``activation_statistics``, ``frechet_distance`` (the one host step, as in the reference),
+    ``fid_given_data``, ``inception_rows``, ``inception_score_from_probs`` and ``inception_score_given_data`` at the end of the file.
 
 All arithmetic runs in the kernel library (csrc/eval_scores.hip: ``dfh_embed_pair_cosine``, ``dfh_embed_candidates``,
 ``dfh_compat_score``) in fp32, in both storage builds.  The ``nn.Linear`` / ``nn.LayerNorm`` modules of ``FashionEvaluator`` only HOLD
@@ -321,3 +324,133 @@ class CLIPScore:
         ``clip_og_retrieval_given_data`` (:733-745) is a ``topk`` over the same sims."""
         _require_cosine(similarity_func)
         return candidate_cosine(self.image_model.encode_image(images), cnn_features, candidates)
+
+
+# ------------------------------------------------------------------ FID and the Inception Score (DESIGN.md row f9; csrc/inception.hip)
+@torch.no_grad()
+def activation_statistics(model, data, batch_size: int = 50, dims: int = 2048):
+    """``calculate_activation_statistics`` (eval_utils.py:282-320): ``(mu [dims], sigma [dims, dims])`` as fp64 DEVICE tensors --
+    ``np.mean(act, axis=0)`` and ``np.cov(act, rowvar=False)`` of the float64 copy of the pooled activations, on the fp64 matrix
+    instruction.  ``model``: a ``FIDInceptionV3`` whose first output block is ``dims`` wide; ``data``: fp32 ``[N, 3, H, W]`` in [0, 1]
+    on the device, or a list of per-image device tensors."""
+    acts = []
+    for batch in _image_batches(data, batch_size, "data"):
+        pred = model(batch)[0]
+        if pred.shape[1] != dims:
+            raise ValueError(f"the model's first output block is {pred.shape[1]} wide, dims={dims}")
+        acts.append(pred.reshape(pred.shape[0], dims))
+    act = torch.cat(acts).contiguous()
+    N = act.shape[0]
+    if N < 2:
+        raise ValueError(f"the covariance needs at least two images (N - 1 divides), got {N}")
+    mu = torch.empty((dims,), dtype=torch.float64, device=act.device)
+    sigma = torch.empty((dims, dims), dtype=torch.float64, device=act.device)
+    with torch.cuda.device(act.device):
+        _lib.call("dfh_incep_stats", _lib.ptr(act), N, dims, _lib.ptr(mu), _lib.ptr(sigma), _lib.stream_ptr())
+    return mu, sigma
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2, eps: float = 1e-6) -> float:
+    """pytorch_fid's ``calculate_frechet_distance`` restated in fp64 on the HOST -- the one host step of the row, where the reference
+    has it: ``|mu1 - mu2|^2 + tr s1 + tr s2 - 2 tr sqrtm(s1 s2)``, with the ``eps`` offset on both covariances when the root is not
+    finite and the imaginary-diagonal check at 1e-3.  Takes numpy arrays or tensors (device tensors are copied to the host)."""
+    import numpy as np
+    try:
+        from scipy import linalg
+    except ImportError as e:
+        raise ImportError("frechet_distance needs scipy (scipy.linalg.sqrtm, as pytorch_fid does): install scipy; the statistics "
+                          "themselves (activation_statistics) do not need it") from e
+
+    def host(a):
+        return np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64)
+
+    def root(a):
+        r = linalg.sqrtm(a)
+        return r[0] if isinstance(r, tuple) else r
+
+    mu1, mu2 = np.atleast_1d(host(mu1)), np.atleast_1d(host(mu2))
+    sigma1, sigma2 = np.atleast_2d(host(sigma1)), np.atleast_2d(host(sigma2))
+    if mu1.shape != mu2.shape:
+        raise ValueError("Training and test mean vectors have different lengths")
+    if sigma1.shape != sigma2.shape:
+        raise ValueError("Training and test covariances have different dimensions")
+    diff = mu1 - mu2
+    covmean = root(sigma1.dot(sigma2))
+    if not np.isfinite(covmean).all():
+        offset = np.eye(sigma1.shape[0]) * eps
+        covmean = root((sigma1 + offset).dot(sigma2 + offset))
+    if np.iscomplexobj(covmean):
+        if not np.allclose(np.diagonal(covmean).imag, 0, atol=1e-3):
+            raise ValueError(f"Imaginary component {np.max(np.abs(covmean.imag))}")
+        covmean = covmean.real
+    return float(diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean))
+
+
+@torch.no_grad()
+def fid_given_data(gen, grd, batch_size: int = 50, dims: int = 2048, model=None) -> float:
+    """``calculate_fid_given_data`` (eval_utils.py:322-337).  ``model``: a ``FIDInceptionV3`` on the device holding the FID weights
+    (built for block ``BLOCK_INDEX_BY_DIM[dims]``); None makes one with seeded stand-in weights on the images' device."""
+    from .inception import FIDInceptionV3
+    if dims not in FIDInceptionV3.BLOCK_INDEX_BY_DIM:
+        raise ValueError(f"dims must be one of {sorted(FIDInceptionV3.BLOCK_INDEX_BY_DIM)}, got {dims}")
+    if model is None:
+        first = gen if isinstance(gen, torch.Tensor) else gen[0]
+        model = FIDInceptionV3([FIDInceptionV3.BLOCK_INDEX_BY_DIM[dims]]).to(first.device)
+    m1, s1 = activation_statistics(model, gen, batch_size, dims)
+    m2, s2 = activation_statistics(model, grd, batch_size, dims)
+    return frechet_distance(m1, s1, m2, s2)
+
+
+@torch.no_grad()
+def inception_rows(probs: torch.Tensor, cate: Optional[torch.Tensor] = None, eps: float = 1e-16):
+    """Per image of ``probs [N, classes]``: ``(label int64, entropy, kl, correct)`` -- ``argmax``, ``-sum p log(p + eps)``,
+    ``sum p (log(p + eps) - log(1 / classes))`` and ``label == cate`` (zeros without ``cate``), on the HIP path."""
+    probs = _device_rows(probs, "inception_rows: probs")
+    if probs.dim() != 2 or probs.shape[0] < 1 or probs.shape[1] < 1:
+        raise ValueError(f"probs must be [N >= 1, classes >= 1], got {tuple(probs.shape)}")
+    N, dev = probs.shape[0], probs.device
+    if cate is not None:
+        if not isinstance(cate, torch.Tensor) or cate.device != dev or cate.numel() != N:
+            raise ValueError(f"cate must hold one label per image on {dev}")
+        cate = cate.reshape(N).to(torch.int64).contiguous()
+    label = torch.empty((N,), dtype=torch.int64, device=dev)
+    ent, kl, correct = (torch.empty((N,), dtype=torch.float32, device=dev) for _ in range(3))
+    with torch.cuda.device(dev):
+        _lib.call("dfh_incep_is_rows", _lib.ptr(probs), _lib.ptr(cate), N, probs.shape[1], float(eps), _lib.ptr(label), _lib.ptr(ent), _lib.ptr(kl),
+                  _lib.ptr(correct), _lib.stream_ptr())
+    return label, ent, kl, correct
+
+
+@torch.no_grad()
+def inception_score_from_probs(probs: torch.Tensor, cate: torch.Tensor, num_splits: int = 1, eps: float = 1e-16):
+    """The arithmetic of ``calculate_inception_score_given_data`` after the network (eval_utils.py:371-406) on ``probs [N, classes]``:
+    ``(acc, mean entropy, std entropy, mean score, std score)``; split ``i`` holds images ``[i N // num_splits, (i + 1) N // num_splits)``,
+    the standard deviations are unbiased (``nan`` for one split, as the reference's are)."""
+    _, ent, kl, correct = inception_rows(probs, cate, eps)
+    N = probs.shape[0]
+    if not 1 <= num_splits <= N:
+        raise ValueError(f"num_splits must be in 1 .. {N}, got {num_splits}")
+    out = torch.empty((num_splits, 3), dtype=torch.float32, device=probs.device)
+    with torch.cuda.device(probs.device):
+        _lib.call("dfh_incep_is_splits", _lib.ptr(ent), _lib.ptr(kl), _lib.ptr(correct), N, num_splits, _lib.ptr(out), _lib.stream_ptr())
+    rows = out.cpu().double()                            # num_splits x 3 numbers: the last step is host arithmetic on them
+
+    def mean_std(v):
+        m = float(v.mean())
+        return m, (float(((v - m) ** 2).sum() / (len(v) - 1)) ** 0.5 if len(v) > 1 else float("nan"))
+
+    acc = float(rows[:, 2].sum()) / N
+    return (acc,) + mean_std(rows[:, 0]) + mean_std(rows[:, 1])
+
+
+@torch.no_grad()
+def inception_score_given_data(model, data, cate, batch_size: int = 50, num_splits: int = 1, eps: float = 1e-16, resize_input: bool = True,
+                               normalize_input: bool = True):
+    """``calculate_inception_score_given_data`` (eval_utils.py:339-406) over an ``InceptionV3`` on the device: ``data`` fp32
+    ``[N, 3, H, W]`` (or a list of per-image tensors) in [0, 1], ``cate [N]`` the categories.  The resize to 299 x 299 and ``2 x - 1``
+    run in the network's first kernel."""
+    model.set_input_flags(resize_input, normalize_input)
+    probs = torch.cat([model(batch) for batch in _image_batches(data, batch_size, "data")])
+    if not isinstance(cate, torch.Tensor):
+        cate = torch.as_tensor(list(cate))
+    return inception_score_from_probs(probs, cate.to(probs.device), num_splits, eps)

@@ -458,6 +458,100 @@ int dfh_lpips_conv3x3_relu(const float* x, const float* weight, int w_cin, const
 int dfh_lpips_maxpool2x2(const float* x, float* out, int n, int H, int W, int C, void* stream);
 int dfh_lpips_layer_score(const float* feat, const float* lin_weight, int pairs, int H, int W, int C, float* partial, float* out, void* stream);
 
+/* ------------------------------------------------------------------ Inception v3: FID and the Inception Score
+ * Replaces (arithmetic) the two networks of Evaluation/eval_utils.py: pytorch_fid's FIDInceptionV3 (:137-280, variant FID) and
+ * torchvision's inception_v3 under the fine-tuned classifier (:17-89, variant TV), the per-image entropy / KL terms of the customised
+ * Inception Score (:382-398) and np.mean / np.cov of the activations (:318-319).  csrc/inception.hip: fp32 NHWC in both storage builds,
+ * every convolution ONE implicit-GEMM kernel on v_mfma_f32_16x16x4_f32 with BatchNorm folded to a per-channel scale / shift and ReLU in
+ * the epilogue, written into a channel slice of the concatenated output; the statistics on v_mfma_f64_16x16x4_f64.  No atomics, nothing
+ * allocated; every per-image value is a function of its image alone.
+ * The convolution sums K = KH * KW * C_in in k-tiles of 32: each tile in fresh accumulators, added to the running sum with a compensated
+ * (Kahan) add (f32_tile.h TileKahanSum), so the rounding error does not grow with K (up to 4032 here).
+ * Parameters under torchvision's state-dict names, per BasicConv2d <layer>.conv.weight [C_out][C_in][KH][KW], <layer>.bn.weight, .bn.bias,
+ * .bn.running_mean, .bn.running_var [C_out], in torchvision's module order (AuxLogits left out), then for TV fc.weight [classes][2048],
+ * fc.bias: 94 convolutions -> 470 entries (FID), 472 (TV). */
+#define DFH_INCEP_VARIANT_TV 0       /* torchvision: transform_input, avg pools count the padding, fc + softmax */
+#define DFH_INCEP_VARIANT_FID 1      /* pytorch_fid: avg pools leave the padding out, Mixed_7c pools with max, no fc */
+#define DFH_INCEP_NUM_CONVS 94
+#define DFH_INCEP_NUM_BLOCKS 4       /* taps: 64 after maxpool1, 192 after maxpool2, 768 after Mixed_6e, 2048 after the global average */
+#define DFH_INCEP_SIDE 299
+/* launch kinds of the plan */
+#define DFH_INCEP_K_PREP 0
+#define DFH_INCEP_K_CONV 1
+#define DFH_INCEP_K_POOL 2
+#define DFH_INCEP_K_GMEAN 3
+#define DFH_INCEP_K_FC 4
+#define DFH_INCEP_K_SOFTMAX 5
+/* pool modes */
+#define DFH_INCEP_POOL_MAX_S2 0      /* max_pool2d(3, 2) */
+#define DFH_INCEP_POOL_MAX_S1 1      /* max_pool2d(3, 1, 1) */
+#define DFH_INCEP_POOL_AVG_INCL 2    /* avg_pool2d(3, 1, 1), count_include_pad=True: always / 9 */
+#define DFH_INCEP_POOL_AVG_EXCL 3    /* avg_pool2d(3, 1, 1, count_include_pad=False): / the pixels inside the image */
+/* regions of a launch's source / destination */
+#define DFH_INCEP_REGION_INPUT (-1)  /* the caller's images */
+#define DFH_INCEP_REGION_TAP (-2)    /* the caller's taps[block] */
+#define DFH_INCEP_REGION_PROBS (-3)  /* the caller's probs */
+typedef struct dfh_incep_config {
+  int variant;                       /* DFH_INCEP_VARIANT_* */
+  int num_classes;                   /* TV: width of fc (1 .. 4096); FID: ignored */
+  int resize_input, normalize_input; /* bilinear to 299 x 299; 2 x - 1 */
+  int block_mask;                    /* bit b: tap b is written; the walk stops after the highest bit.  TV: bit 3 is required (the classifier) */
+} dfh_incep_config;
+typedef struct dfh_incep_launch {
+  int kind, conv, pool_mode, block;  /* conv: index into the layer list or -1; block: the tap of a GMEAN or -1 */
+  int KH, KW, stride, padH, padW;
+  int Hin, Win, Cin, Hout, Wout, Cout, ldc, offset;      /* the output is channels [offset, offset + Cout) of a tensor with ldc channels */
+  int src_region, dst_region;        /* workspace region 0 .. 3 (4: the logits) or DFH_INCEP_REGION_* */
+  size_t src_off, src_floats, dst_off, dst_floats;       /* in floats from the workspace base: the launch reads / writes inside [off, off + floats) */
+  char name[48];                     /* the layer (state-dict prefix) or the pool / head step */
+} dfh_incep_launch;
+typedef struct dfh_incep dfh_incep;
+int dfh_incep_create(const dfh_incep_config* cfg, dfh_incep** out);   /* host-only work */
+void dfh_incep_destroy(dfh_incep* c);
+int dfh_incep_num_params(const dfh_incep* c);
+const char* dfh_incep_param_name(const dfh_incep* c, int i);
+int dfh_incep_param_ndim(const dfh_incep* c, int i);
+int dfh_incep_param_dim(const dfh_incep* c, int i, int d);
+/* Per convolution [C_out][KH * KW * C_in_padded] weights (k = tap * C_in_padded + channel; the first layer's three channels padded to
+ * four), then scale [C_out] = bn.weight / sqrt(running_var + 1e-3) and shift [C_out] = bn.bias - running_mean * scale. */
+size_t dfh_incep_packed_bytes(const dfh_incep* c);
+int dfh_incep_pack(dfh_incep* c, const float* const* params, int count, void* packed, void* stream);
+/* The launch plan of n images of H x W: pure host arithmetic.  count: the number of launches, negative on a refusal. */
+int dfh_incep_plan_count(const dfh_incep* c, int n, int H, int W);
+int dfh_incep_plan_entry(const dfh_incep* c, int n, int H, int W, int i, dfh_incep_launch* out);
+/* Four activation regions, each the largest tensor the plan puts there, + n * num_classes logits (TV), + 256 bytes; 0 on a refusal. */
+size_t dfh_incep_workspace_bytes(const dfh_incep* c, int n, int H, int W);
+/* in: fp32 [n][3][H][W]; taps: HOST array of DFH_INCEP_NUM_BLOCKS device pointers, taps[b] = [n][64 | 192 | 768 | 2048] for every bit
+ * of block_mask (the spatial mean of the block's output; others ignored); probs: TV [n][num_classes] softmax, FID NULL.
+ * Refused on the host before any HIP call: a wrong count, a null / misaligned pointer by name, a missing tap, a small workspace,
+ * without resize_input a side below 75 (Mixed_7a would be empty). */
+int dfh_incep_forward(dfh_incep* c, const float* const* params, int count, const void* packed, const float* in, int n, int H, int W,
+                      float* const* taps, float* probs, void* workspace, size_t workspace_bytes, void* stream);
+/* The kernels on their own (tests, microbenchmarks).  Activations are NHWC fp32.
+ * prep: out [n][OH][OW][4], (OH, OW) = resize ? (299, 299) : (H, W); affine != 0: TV's transform_input after 2 x - 1.
+ * conv_bn_relu: out[.., offset : offset + C_out] of [n][OH][OW][ldc] = relu(batch_norm(conv2d(x [n][H][W][C_in], weight
+ *   [C_out][w_cin][KH][KW], stride, (padH, padW)), eps 1e-3)); bn: weight, bias, running_mean, running_var; C_in a multiple of 4, input
+ *   channels from w_cin up carry zero weights; packed: C_out * (KH * KW * C_in + 2) floats.
+ * pool: the four 3 x 3 pools into a channel slice; C, ldc, offset multiples of 4.
+ * global_mean: out [n][C] = the mean over the H * W pixels, summed in fp64 in a fixed order.
+ * fc_softmax: probs [n][classes] = softmax(feat [n][K] . weight [classes][K]^T + bias); logits: n * classes floats of scratch.
+ * is_rows: per image label = argmax (the lowest index among equals, a NaN wins), ent = -sum p log(p + eps),
+ *   kl = sum p (log(p + eps) - log(1 / classes)), correct = (label == cate) (cate NULL: 0).
+ * is_splits: out [splits][3] = (mean ent, exp(mean kl), sum correct) over images [s N / splits, (s + 1) N / splits), in index order.
+ * stats: mu [D] = np.mean(act, 0), sigma [D][D] = np.cov(act, rowvar=False) of the float64 copy of act [N][D] (two-pass, / (N - 1));
+ *   N >= 2; sigma is written symmetric. */
+int dfh_incep_prep(const float* src, int n, int H, int W, int resize, int normalize, int affine, float* out, void* stream);
+int dfh_incep_conv_bn_relu(const float* x, const float* weight, int w_cin, const float* const* bn, float* packed, float* out, int n, int H, int W,
+                           int C_in, int C_out, int KH, int KW, int stride, int padH, int padW, int ldc, int offset, void* stream);
+int dfh_incep_pool(const float* x, float* out, int mode, int n, int H, int W, int C, int ldc, int offset, void* stream);
+int dfh_incep_global_mean(const float* x, float* out, int n, int HW, int C, void* stream);
+int dfh_incep_fc_softmax(const float* feat, const float* weight, const float* bias, float* logits, float* probs, int n, int K, int classes,
+                         void* stream);
+int dfh_incep_is_rows(const float* probs, const int64_t* cate, int n, int classes, float eps, int64_t* label, float* ent, float* kl,
+                      float* correct, void* stream);
+int dfh_incep_is_splits(const float* ent, const float* kl, const float* correct, int n, int splits, float* out, void* stream);
+int dfh_incep_stats(const float* act, int N, int D, double* mu, double* sigma, void* stream);
+
 /* ------------------------------------------------------------------ op-level entry points (tests, profiling)
  * ResnetBlock2D conv3x3 / Downsample2D / Upsample2D / 1x1 conv / Linear, as one implicit GEMM:
  *   out[M][N] = act( conv3x3(x) (+ a0 . W[:, k0:] + a1 . W[:, k1:]) + bias + rowvec[b] ) + resid */
