@@ -56,6 +56,8 @@ namespace dfh {
 // Launch geometry of a statistics kernel + apply kernel pair over a = GnArgs or GnBwdArgs (a.C, B, HW set): a thread owns a channel
 // octet and one of PL pixel lanes; the statistics pass runs as a.chunks pixel chunks an image (its partial buffer holds GN_MAX_CHUNKS),
 // the apply pass as achunks.  The targets are the chunk counts to aim for over the whole batch: enough blocks to fill the chip.
+// tests/helpers_norm.py two_kernel_geometry restates PL / chunks / pix_per_chunk (at the default DFH_GN_SC) to choose shapes with ragged
+// chunks and to bound the summation depth: change the two together (tests/test_norm_inputs_cpu.py pins the figures).
 struct GnTwoKernel { int block, achunks; size_t lds; };     // threads of both kernels, apply grid, dynamic LDS of the statistics kernel
 template <class Args>
 int gn_two_kernel_geometry(Args& a, int stats_target, int apply_target, GnTwoKernel* g) {

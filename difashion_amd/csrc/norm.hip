@@ -440,6 +440,7 @@ GnPlan gn_select(const GnArgs& a, const WalkKnobs& knobs) {
   const bool one_source_per_group = a.C1 == 0 || a.C0 % cpg == 0;
   if ((cpg & 3) == 0 && slab <= 256 * knobs.gn_small_max && one_source_per_group && (long)a.B * a.G >= 64)
     return {GN_ONE_SLAB, slab <= 256 * 8 ? 8 : slab <= 256 * 16 ? 16 : 32, 0, 0, 256};
+  // (tests/helpers_norm.py group_quad_geometry restates the rule below for the summation depth of its bounds: change the two together)
   // mid path (16x16 / 8x8 tensors the one-slab kernel cannot take: groups that straddle the two concat sources, e.g. 1280 + 640
   // channels): GQ adjacent groups per block.  Measured against the alternatives (scripts/norm_microbench.py): 24.4 -> 13.4 us
   // on 16x16 x (1280 + 640); where gn_small_kernel is eligible it is faster (its blocks are four waves, the reductions here

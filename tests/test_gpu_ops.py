@@ -12,6 +12,7 @@ import torch.nn.functional as F
 from difashion_amd import _lib
 from oracle import glue_ref, sched_ref, unet_ref
 from tests import gpu_util as gu
+from tests import helpers_norm as hn
 from tests.gpu_util import DEV, bf, rnd
 
 pytestmark = pytest.mark.gpu
@@ -459,6 +460,12 @@ def test_gemm_writes_groupnorm_statistics_for_its_consumer(kind, cin, cout, H, B
     gu.assert_close_bf16(gu.nchw(o_pre.view(B, H, H, cout)), gref, "groupnorm from producer statistics")
     mean = xr.view(B, G, -1).mean(-1)
     assert torch.allclose(stats.view(B, G, 2)[..., 0], mean, atol=1e-3)
+    # rstd, which the backward pass trusts: the one-pass variance against fp64 of the GEMM's own output, within Higham's bound for the
+    # epilogue's summation depth times kappa_g = 1 + mean^2 / var (tests/helpers_norm.py; tests/test_gpu_norm_stats.py leg B)
+    rb = hn.conditioning_leg(stats.cpu(), out.cpu().view(B, HW, cout), 1e-5, True, hn.producer_depth(cout, HW, rows))
+    print(f"groupnorm parity B gn_pre {kind} {cin}->{cout}@{HW} tile{tile} R_g {rb['R'][0]:.2f}..{rb['R'][1]:.2f} rstd_err {rb['rstd_err']:.2e} "
+          f"var_err/bound {rb['var']:.3f} mean_err/bound {rb['mean']:.3f} K {rb['K']:.2f}")
+    assert rb["var"] <= 1 and rb["mean"] <= 1, rb
     # bit-identical reruns (fixed summation orders), and a launch that runs on a kernel without the statistics epilogue must say so
     g1 = gst.clone()
     gu.gemm(force_tile=tile, gstat=gst, gstat_cpg=cpg, gstat_hw=HW, **kw)
