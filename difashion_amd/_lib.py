@@ -63,6 +63,26 @@ class CLIPVisionConfigC(C.Structure):
                 ("hidden_act", C.c_int), ("layer_norm_eps", C.c_float)]
 
 
+CLIPVH_MAX_LAUNCHES, CLIPVH_MAX_REGIONS = 8, 16
+
+
+class CLIPVHalfLaunchC(C.Structure):
+    _fields_ = [("name", C.c_char * 16)] + \
+               [(n, C.c_int) for n in ("M", "N", "K", "lda", "ldw", "ld_out", "n_split", "ld_out2", "rows_per_b", "act", "resid", "per_layer",
+                                       "a_region", "out_region", "out2_region")]
+
+
+class CLIPVHalfRegionC(C.Structure):
+    _fields_ = [("name", C.c_char * 16), ("offset", C.c_size_t), ("bytes", C.c_size_t)]
+
+
+class CLIPVHalfPlanC(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("batch", "tokens", "hidden", "intermediate", "heads", "head_dim", "layers", "projection_dim",
+                                       "patch_k", "patch_k_padded", "rows", "patch_rows", "ldvt", "attention_x32", "num_launches", "num_regions")] + \
+               [("workspace_bytes", C.c_size_t), ("packed_bytes", C.c_size_t), ("launches", CLIPVHalfLaunchC * CLIPVH_MAX_LAUNCHES),
+                ("regions", CLIPVHalfRegionC * CLIPVH_MAX_REGIONS)]
+
+
 class ImgProcConfigC(C.Structure):
     _fields_ = [("shortest_edge", C.c_int), ("crop_height", C.c_int), ("crop_width", C.c_int), ("resample", C.c_int)]
 
@@ -187,6 +207,11 @@ SIGNATURES = {
     "dfh_clipv_workspace_bytes": (_sz, [_vp, _i]),
     "dfh_clipv_encode": (_i, [_vp, C.POINTER(_vp), _i, _vp, _i, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
     "dfh_clipv_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "dfh_clipvh_plan": (_i, [_vp, _i, C.POINTER(CLIPVHalfPlanC)]),
+    "dfh_clipvh_packed_bytes": (_sz, [_vp]),
+    "dfh_clipvh_pack": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp]),
+    "dfh_clipvh_workspace_bytes": (_sz, [_vp, _i]),
+    "dfh_clipvh_encode": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
     "dfh_imgproc_create": (_i, [C.POINTER(ImgProcConfigC), _i, _i, _i, C.POINTER(_vp)]),
     "dfh_imgproc_destroy": (None, [_vp]),
     "dfh_imgproc_resized_height": (_i, [_vp]),

@@ -11,7 +11,13 @@
 #include <stdint.h>
 #include "dfh_common.h"
 
-enum GemmAct { ACT_NONE = 0, ACT_SILU = 1, ACT_LEAKY = 2, ACT_TANH = 3, ACT_GEGLU = 4 };
+enum GemmAct { ACT_NONE = 0, ACT_SILU = 1, ACT_LEAKY = 2, ACT_TANH = 3, ACT_GEGLU = 4,
+               // the MLP activations of the CLIP vision towers (clip_vision_half.hip), evaluated in fp32 before the 16-bit store: exact-erf GELU
+               // (OpenCLIP ViT-H/14) and x * sigmoid(1.702 x) (OpenAI ViT-L/14).  Only the two XACT instantiations of gemm_bf16_kernel (the
+               // eight-wave 128 x 160 tile, LEAN or not) carry them, so that no other instantiation's code changes: the plan sends every
+               // launch with one of them there, single pass, bf16 row-major output
+               ACT_GELU = 5, ACT_QUICK_GELU = 6 };
+inline bool gemm_act_is_xact(int act) { return act == ACT_GELU || act == ACT_QUICK_GELU; }
 enum GemmOut {
   OUT_BF16 = 0,    // bf16 [M][ld_out]
   OUT_BF16_T = 1,  // bf16 transposed per batch: out[b][n][ld_out], m = b*rows_per_b + mm (attention V^T)

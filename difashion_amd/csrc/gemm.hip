@@ -36,6 +36,11 @@ namespace {
 // counted wait on this wave's outstanding vector-memory operations (LDS-DMA pieces)
 template <int N> DFH_DEVICE void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
+// x * sigmoid(1.702 x) (transformers' QuickGELUActivation) with the hardware reciprocal, as silu_f
+DFH_DEVICE float quick_gelu_f(float x) {
+  return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * (-1.702f * 1.44269504088896340736f)));
+}
+
 // ---------------------------------------------------------------------------------------------
 // LEAN: the launch has ONE plain K segment whose length is a multiple of 64 (every linear / 1x1 of the U-Net): a k-step's
 // sources are the previous k-step's plus 128 bytes, so the k-loop keeps one 64-bit pointer per staging piece and adds a
@@ -46,7 +51,8 @@ template <int N> DFH_DEVICE void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0
 // k-steps of 128-byte rows (LDS-DMA gathers 128-byte rows at twice the rate of the 64-byte rows of gemm_wide.hip), 128 x 80 per wave
 // (13 fragment reads per 40 MFMAs), 72 staging pieces per 640 MFMAs of a k-step (0.11 per MFMA against 0.16 for 256 x 160 x 32), two
 // stages = 144 KB, one workgroup per CU.
-template <int BM, int BN, int WM, int WN, int NSTAGE, bool LEAN = false, bool WEPI = false>
+// XACT: the epilogue also knows ACT_GELU / ACT_QUICK_GELU (gemm.h); every other instantiation is compiled without them.
+template <int BM, int BN, int WM, int WN, int NSTAGE, bool LEAN = false, bool WEPI = false, bool XACT = false>
 // second launch-bound = waves per SIMD the register allocation must leave room for: the eight-wave 128-row tiles run TWO workgroups
 // per CU (4 waves per SIMD, <= 128 VGPRs); without the bound the allocator settles at 130 and silently halves the occupancy
 // (+35 % on every 32x32 / 16x16-level conv, measured)
@@ -498,6 +504,14 @@ void gemm_bf16_kernel(const GemmArgs a) {
         } else if (a.act == ACT_TANH) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) v[r] = tanhf(v[r]);
+        } else if constexpr (XACT) {
+          if (a.act == ACT_GELU) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = gelu_erf_f(v[r]);
+          } else if (a.act == ACT_QUICK_GELU) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = quick_gelu_f(v[r]);
+          }
         }
         if (a.resid) {
           const uint2 rr = rpre[i][j];
@@ -708,6 +722,14 @@ void gemm_bf16_kernel(const GemmArgs a) {
       } else if (a.act == ACT_TANH) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = tanhf(v[r]);
+      } else if constexpr (XACT) {
+        if (a.act == ACT_GELU) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = gelu_erf_f(v[r]);
+        } else if (a.act == ACT_QUICK_GELU) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = quick_gelu_f(v[r]);
+        }
       }
       if (a.resid) {
         const uint2 rr = *(const uint2*)(a.resid + (long)m * a.ld_res + n);
@@ -780,24 +802,26 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce(const GemmArgs a) {
   }
 }
 
-template <int BM, int BN, int WM, int WN, int NSTAGE, bool LEAN = false, bool WEPI = false>
+template <int BM, int BN, int WM, int WN, int NSTAGE, bool LEAN = false, bool WEPI = false, bool XACT = false>
 int launch_tile(const GemmArgs& a, hipStream_t stream) {
   constexpr int lds = NSTAGE * (BM + BN) * BK * 2;
   static_assert(lds <= 160 * 1024, "LDS ring exceeds the CU's 160 KiB");
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<BM, BN, WM, WN, NSTAGE, LEAN, WEPI>,
+    (void)hipFuncSetAttribute((const void*)gemm_bf16_kernel<BM, BN, WM, WN, NSTAGE, LEAN, WEPI, XACT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_set = true;
   }
   const int ntm = (a.M + BM - 1) / BM, ntn = (a.N + BN - 1) / BN;
   dim3 grid(ntm * ntn, a.nbatch > 1 ? a.nbatch : 1, a.ksplit);
-  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, NSTAGE, LEAN, WEPI>), grid, dim3(WM * WN * 64), lds, stream, a);
+  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, NSTAGE, LEAN, WEPI, XACT>), grid, dim3(WM * WN * 64), lds, stream, a);
   return dfh::check_launch("gemm_bf16_kernel");
 }
 
 // the gemm_bf16_kernel instantiation a GK_TILE / GK_BIG / GK_BIG_GEGLU plan names: tile, ring depth and LEAN k-loop are plan fields (gemm_plan.hip)
 int launch_planned(const dfh::GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+  // ACT_GELU / ACT_QUICK_GELU (the CLIP vision MLPs): the plan pins the eight-wave 128 x 160 tile, two stages, single pass
+  if (gemm_act_is_xact(a.act)) return p.lean ? launch_tile<128, 160, 4, 2, 2, true, false, true>(a, s) : launch_tile<128, 160, 4, 2, 2, false, false, true>(a, s);
   // the GEGLU projections on a 256 x 256 eight-wave tile (128 x 64 per wave: whole (value, gate) block pairs inside a wave)
   if (p.kernel == dfh::GK_BIG_GEGLU) return p.lean ? launch_tile<256, 256, 2, 4, 2, true, true>(a, s) : launch_tile<256, 256, 2, 4, 2, false, true>(a, s);
   // the "big" tile: 256 x 320, eight waves, 64-deep k-steps (see the kernel's WEPI note)

@@ -104,6 +104,10 @@ int gemm_pick_split(const GemmArgs& a, int* tile_out) {
   // Measured on MI355X (scripts/gemm_microbench.py): the 128-row / 4-wave / 2-stage variants at two
   // workgroups per CU beat the 256-row / 8-wave / 3-stage ring on every U-Net shape except the 8x8 level.
   const int ksteps = gemm_count_ksteps(a);
+  if (gemm_act_is_xact(a.act)) {       // only the XACT instantiations of the eight-wave 128 x 160 tile know these activations; the reduce kernel does not
+    if (tile_out) *tile_out = kEightWave;
+    return 1;
+  }
   int tile;
   if (a.N <= 64 && !geglu) tile = 2;
   else if (a.M > 128 && a.M <= 1024 && ksteps >= 64) tile = n160 ? 0 : 1;
@@ -310,6 +314,13 @@ int gemm_plan(GemmArgs& a, const GemmForce& f, const GemmKnobs& k, GemmPlan& p) 
     PLAN_REQUIRE(a.N % 32 == 0 && kGemmTiles[tile].bn != 160 && split == 1, "GEGLU needs N % 32 == 0, a 64/128-wide tile and no split-K");
     PLAN_REQUIRE(a.out_mode == OUT_BF16 && !a.resid && !a.rowvec, "GEGLU epilogue is bias-only, bf16 out");
   }
+  const bool xact = gemm_act_is_xact(a.act);
+  if (xact) {
+    PLAN_REQUIRE(a.out_mode == OUT_BF16 && a.ntaps == 0 && a.nbatch <= 1 && !a.out2 && !a.pre_out && !a.ln_stat && !a.w_img_bs && !a.w_blocked &&
+                 !a.phase2x && (a.N & 7) == 0 && (a.ld_out & 7) == 0 && (!a.resid || (a.ld_res & 7) == 0),
+                 "GELU / quick-GELU epilogue: plain linears with a row-major 16-bit output and 16-byte aligned rows only");
+    tile = kEightWave; split = 1;      // whatever the force ids say: no other instantiation carries these activations
+  }
   split = std::min(split, a.ksteps);
   {
     double kk = (double)a.ntaps * a.conv_c;
@@ -352,7 +363,7 @@ int gemm_plan(GemmArgs& a, const GemmForce& f, const GemmKnobs& k, GemmPlan& p) 
 
   // ---- kernel: 256 x 256 GEGLU tile, 256 x 320 tile, a wide variant, else `tile`.  A forced kernel the launch cannot take (fp32 / transposed
   //      outputs, GEGLU, N % 8) falls back to the heuristic tile; without force ids the *_pick rules decide.
-  const bool wide_ok0 = split == 1 && a.out2 == nullptr && a.out_mode == OUT_BF16 && (a.act != ACT_GEGLU || a.N % 160 == 0 || a.N % 128 == 0) && (a.N & 7) == 0 &&
+  const bool wide_ok0 = !xact && split == 1 && a.out2 == nullptr && a.out_mode == OUT_BF16 && (a.act != ACT_GEGLU || a.N % 160 == 0 || a.N % 128 == 0) && (a.N & 7) == 0 &&
                         (a.ld_out & 7) == 0 && (!a.resid || (a.ld_res & 7) == 0);
   const bool wide_ok = wide_ok0 && a.nbatch <= 1 && !a.w_img_bs;       // batched launches / per-image weights: gemm_bf16_kernel tiles only (the 256 x 320 one when pinned)
   const bool heur = f.none() && f.split == 0;
@@ -388,7 +399,7 @@ int gemm_plan(GemmArgs& a, const GemmForce& f, const GemmKnobs& k, GemmPlan& p) 
         // launches of at most ~one workgroup per CU (the 8x8-level Winograd GEMM: 16 planes x 256 rows = 256 workgroups; the 16x16-level token
         // linears), each a chain of k-steps that wait for lines requested one stage ahead: a 4-stage ring keeps three stages in flight.
         const long wgs = (long)((a.M + 127) / 128) * ((a.N + 159) / 160) * (a.nbatch > 1 ? a.nbatch : 1) * a.ksplit;
-        if (!k.deep4_off && (a.nbatch > 1 || k.deep4_all) && wgs <= 320) p.stages = 4;
+        if (!xact && !k.deep4_off && (a.nbatch > 1 || k.deep4_all) && wgs <= 320) p.stages = 4;
         p.lean = lean;
       }
     }

@@ -357,6 +357,62 @@ int dfh_clipv_encode(dfh_clipv* c, const float* const* master_params, int count,
  * head_dim a multiple of 4 up to 128, any T >= 1. */
 int dfh_clipv_attention(const float* qkv, float* out, int batch, int T, int heads, int head_dim, float scale, void* stream);
 
+/* ---- the same tower in the library's 16-bit storage format (bf16; fp16 in libdifashion_hip_f16.so), opt-in (csrc/clip_vision_half.hip):
+ * the `dfh_clipvh_*` family works on a dfh_clipv context (the `dfh_clipv_*` name set above is the fp32 tower's and stays as it is).
+ * What transformers' torch_dtype= / .half() and open_clip's precision="bf16" / "fp16" give: 16-bit weights and a 16-bit residual stream
+ * between launches, with every accumulation, LayerNorm statistic, softmax and activation in fp32.  The walk: im2col (16-bit rows, K
+ * zero-padded to a multiple of 8) -> patch GEMM -> class token + position embeddings + pre_layrnorm in one launch -> per block LayerNorm,
+ * ONE q | k | v launch (q | k row-major, V transposed per image with rows padded to a multiple of 8 keys), dfh_attention's kernels,
+ * out-proj + residual, LayerNorm, fc1 + GELU / quick-GELU in the GEMM epilogue, fc2 + residual -> post_layernorm of the class rows and
+ * visual_projection in fp32 arithmetic.  No atomics: a rerun is bit-identical.  Head dims: those of dfh_attention (32, 40, 64, 80, 128, 160).
+ *   packed copy  : dfh_clipvh_packed_bytes(c) bytes, 256-byte aligned, written by dfh_clipvh_pack from the fp32 masters and remade by the
+ *                  caller whenever a master changes: per matrix [N][K] 16-bit, K-contiguous -- the patch-conv weight as
+ *                  [hidden][C p p padded to a multiple of 8], q | k | v stacked as one [3 hidden][hidden] matrix with their biases
+ *                  stacked as one fp32 [3 hidden] vector.  All other biases, the LayerNorm affines, class / position embeddings and
+ *                  visual_projection are read from the fp32 masters in place.
+ *   pixel_values : fp32 (pixel_dtype 0) or the storage format (1), aligned to its element size
+ *   outputs      : as dfh_clipv_encode, all fp32, each 16-byte aligned (the non-null hidden_states entries too); last_hidden_state and
+ *                  hidden_states are exact upcasts of the 16-bit stream
+ *   workspace    : >= dfh_clipvh_workspace_bytes(c, batch) (0: refused, see dfh_last_error), 256-byte aligned
+ * A config whose 2 x hidden is no whole number of the q | k | v launch's column tiles (hidden 192: 160-column tiles) is refused by every
+ * entry point of the family, dfh_clipvh_plan included, before anything is launched.
+ * dfh_clipvh_plan is the host function both the size query and the walk are built on (no GPU needed): every GEMM launch's
+ * M / N / K / leading dims, the V^T padding and the byte range of every workspace region. */
+#define DFH_CLIPVH_MAX_LAUNCHES 8
+#define DFH_CLIPVH_MAX_REGIONS 16
+typedef struct dfh_clipvh_launch {
+  char name[16];                   /* patch, qkv, out_proj, fc1, fc2 */
+  int M, N, K;                     /* K as the kernel walks it (patch: padded) */
+  int lda, ldw, ld_out;            /* elements */
+  int n_split, ld_out2, rows_per_b;/* qkv: columns [n_split, N) leave transposed per image into [batch][N - n_split][ld_out2] */
+  int act;                         /* 0 none, 5 gelu, 6 quick_gelu (dfh_gemm_desc.act) */
+  int resid;                       /* 1: + the residual stream, in place */
+  int per_layer;                   /* 1: launched once per block */
+  int a_region, out_region, out2_region;   /* indices into regions (-1: none) */
+} dfh_clipvh_launch;
+typedef struct dfh_clipvh_region {
+  char name[16];
+  size_t offset, bytes;            /* inside the workspace; offsets are multiples of 256 */
+} dfh_clipvh_region;
+typedef struct dfh_clipvh_plan_info {
+  int batch, tokens, hidden, intermediate, heads, head_dim, layers, projection_dim;
+  int patch_k, patch_k_padded;     /* C p p and its multiple of 8 (588 -> 592 at patch 14) */
+  int rows, patch_rows;            /* batch * tokens, batch * (tokens - 1) */
+  int ldvt;                        /* V^T row pitch: tokens rounded up to a multiple of 8 (257 -> 264) */
+  int attention_x32;               /* 1: dfh_attention takes the 32x32x16 kernel at this length and head dim, 0: the 16x16x32 one */
+  int num_launches, num_regions;
+  size_t workspace_bytes, packed_bytes;
+  dfh_clipvh_launch launches[DFH_CLIPVH_MAX_LAUNCHES];
+  dfh_clipvh_region regions[DFH_CLIPVH_MAX_REGIONS];
+} dfh_clipvh_plan_info;
+int dfh_clipvh_plan(const dfh_clipv* c, int batch, dfh_clipvh_plan_info* out);   /* host-only work */
+size_t dfh_clipvh_packed_bytes(const dfh_clipv* c);
+int dfh_clipvh_pack(dfh_clipv* c, const float* const* master_params, int count, void* packed, void* stream);
+size_t dfh_clipvh_workspace_bytes(const dfh_clipv* c, int batch);
+int dfh_clipvh_encode(dfh_clipv* c, const float* const* master_params, int count, const void* packed, const void* pixel_values,
+                      int pixel_dtype, int batch, float* last_hidden_state, float* pooler_output, float* image_embeds,
+                      float* const* hidden_states, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ CLIP image preprocessing
  * Replaces (arithmetic) open_clip's / transformers' image transform in front of the tower (Evaluation/extract_hist_embs.py:83-100,
  * evaluate_gor.py:193-236): PIL's antialiased 8-bit resize (horizontal pass, then vertical pass, integer arithmetic over 22-bit
@@ -564,7 +620,9 @@ typedef struct dfh_gemm_desc {
   const float* bias;                            /* [N] or NULL */
   const float* rowvec; int rv_ld, rv_off, rows_per_b;  /* + rowvec[m / rows_per_b][rv_off + n] (time embedding) */
   const void* resid; int ld_res;                /* + resid[m][n] bf16 */
-  int act;                                      /* 0 none 1 silu 2 leaky_relu(0.01) 3 tanh 4 GEGLU (W/bias pre-interleaved) */
+  int act;                                      /* 0 none 1 silu 2 leaky_relu(0.01) 3 tanh 4 GEGLU (W/bias pre-interleaved); 5 gelu (exact erf)
+                                                 * 6 quick_gelu (x sigmoid(1.702 x)): plain linears, 16-bit row-major output, N and ld_out
+                                                 * multiples of 8, always the eight-wave 128x160 tile in a single pass (force ids ignored) */
   void* out; int ld_out; int out_mode;          /* 0 bf16 [M][ld] 1 bf16 [b][N][ld] 2 fp32 [M][ld] 3 fp32 [b][N][ld] */
   float* partial; size_t partial_floats;        /* split-K slabs (dfh_gemm_partial_floats) */
   const void* zero_page;                        /* >= 256 zero bytes */
