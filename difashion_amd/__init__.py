@@ -11,7 +11,7 @@ from ._lib import DfhError, set_storage, storage
 from .mutual import MutualEncoder
 from .pipeline import OutfitSampler, guidance_plan, sample_outfits, sampling_tables, train_forward, training_tables
 from .schedulers import DDIMScheduler, PNDMScheduler
-from .training import EMAModel, FusedAdamW, clip_grad_norm_, train_step
+from .training import AdamW8bit, EMAModel, FusedAdamW, clip_grad_norm_, train_step
 from .unet import UNet2DConditionModel, UNet2DConditionOutput
 from .vae import AutoencoderKL
 from .clip import CLIPTextModel, CLIPTextModelOutput, CLIPTextModelWithProjection
@@ -28,7 +28,7 @@ from .difashion import DiFashion
 __all__ = [
     "DfhError", "set_storage", "storage", "UNet2DConditionModel", "UNet2DConditionOutput", "DDIMScheduler", "PNDMScheduler",
     "MutualEncoder", "OutfitSampler", "sample_outfits", "train_forward", "guidance_plan", "sampling_tables", "training_tables",
-    "FusedAdamW", "EMAModel", "clip_grad_norm_", "train_step", "AutoencoderKL", "CLIPTextModel", "DiFashion",
+    "FusedAdamW", "AdamW8bit", "EMAModel", "clip_grad_norm_", "train_step", "AutoencoderKL", "CLIPTextModel", "DiFashion",
     "CLIPVisionModelWithProjection", "CLIPVisionModelOutput", "CLIPTextModelWithProjection", "CLIPTextModelOutput", "CLIPScore",
     "CompatibilityEvaluator", "FashionEvaluator", "pair_cosine", "candidate_cosine", "CLIPImageProcessor", "extract_image_features",
     "LPIPS", "lpips_given_data", "lpips_retrieval",

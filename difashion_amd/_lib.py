@@ -322,6 +322,10 @@ SIGNATURES = {
     "dfh_adamw": (_i, [_vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _f, _vp]),
     "dfh_ema": (_i, [_vp, _vp, _sz, _f, _vp]),
     "dfh_adamw_ema": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _f, _f, _vp]),
+    "dfh_q8_table": (_i, [_i, _vp]),
+    "dfh_q8_quantize": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
+    "dfh_q8_dequantize": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
+    "dfh_adamw8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _f, _i, _vp, _f, _f, _vp]),
     "dfh_wire_pack": (_i, [_vp, _vp, _sz, _sz, _vp]),
     "dfh_wire_shard_mean": (_i, [_vp, _vp, _i, _sz, _vp]),
     "dfh_wire_unpack": (_i, [_vp, _vp, _sz, _vp]),

@@ -376,6 +376,30 @@ int dfh_ema(float* shadow, const float* p, size_t n, float decay, void* stream) 
   DFH_BF16_ONLY_TRAINING;
   return dfh::ema_launch(shadow, p, (long)n, decay, (hipStream_t)stream);
 }
+// block-wise 8-bit optimizer states (adamw8.hip)
+int dfh_q8_table(int is_signed, float* out256_host) {
+  DFH_REQUIRE(out256_host != nullptr, "null output");
+  dfh::q8_table_host(is_signed, out256_host);
+  return 0;
+}
+int dfh_q8_quantize(const float* x, unsigned char* codes, float* absmax, size_t n, int is_signed, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
+  DFH_REQUIRE(x != nullptr && codes != nullptr && absmax != nullptr, "null pointer");
+  return dfh::q8_quantize_launch(x, codes, absmax, (long)n, is_signed, (hipStream_t)stream);
+}
+int dfh_q8_dequantize(const unsigned char* codes, const float* absmax, float* x, size_t n, int is_signed, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
+  DFH_REQUIRE(x != nullptr && codes != nullptr && absmax != nullptr, "null pointer");
+  return dfh::q8_dequantize_launch(codes, absmax, x, (long)n, is_signed, (hipStream_t)stream);
+}
+int dfh_adamw8(float* p, const float* g, unsigned char* m8, float* m_absmax, unsigned char* v8, float* v_absmax, float* shadow, size_t n,
+               float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* sumsq, float max_norm,
+               float ema_decay, void* stream) {
+  DFH_BF16_ONLY_TRAINING;
+  DFH_REQUIRE(p != nullptr && g != nullptr && m8 != nullptr && m_absmax != nullptr && v8 != nullptr && v_absmax != nullptr, "null pointer");
+  return dfh::adamw8_launch(p, g, m8, m_absmax, v8, v_absmax, shadow, (long)n, lr, beta1, beta2, eps, weight_decay, step, sumsq, max_norm,
+                            ema_decay, (hipStream_t)stream);
+}
 
 int dfh_wire_pack(const float* g, void* wire, size_t n, size_t n_pad, void* stream) {
   DFH_BF16_ONLY_TRAINING;

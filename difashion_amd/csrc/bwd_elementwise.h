@@ -35,4 +35,11 @@ int wire_pack_launch(const float* g, bf16_t* wire, long n, long n_pad, hipStream
 int wire_shard_mean_launch(const bf16_t* recv, bf16_t* shard, int world, long per, hipStream_t s);
 int wire_unpack_launch(const bf16_t* wire, float* g, long n, hipStream_t s);
 int ema_launch(float* shadow, const float* p, long n, float decay, hipStream_t s);
+// block-wise 8-bit optimizer states (adamw8.hip): 64-element blocks, one uint8 code per element and one fp32 absmax per block and moment
+void q8_table_host(int is_signed, float* out256);
+int q8_quantize_launch(const float* x, unsigned char* codes, float* absmax, long n, int is_signed, hipStream_t s);
+int q8_dequantize_launch(const unsigned char* codes, const float* absmax, float* x, long n, int is_signed, hipStream_t s);
+int adamw8_launch(float* p, const float* g, unsigned char* m8, float* m_absmax, unsigned char* v8, float* v_absmax, float* shadow, long n,
+                  float lr, float beta1, float beta2, float eps, float wd, int step, const float* sumsq, float max_norm, float ema_decay,
+                  hipStream_t s);
 }  // namespace dfh

@@ -43,15 +43,14 @@ class FusedAdamW(torch.optim.Optimizer):
             raise ValueError("no parameters")
         dev = plist[0].device
         if dev.type != "cuda":
-            raise _lib.DfhError("FusedAdamW runs on the HIP path only: move the modules to 'cuda' first")
+            raise _lib.DfhError(f"{type(self).__name__} runs on the HIP path only: move the modules to 'cuda' first")
         for p in plist:
             if p.dtype != torch.float32 or p.device != dev:
-                raise _lib.DfhError("FusedAdamW needs fp32 parameters on one device")
+                raise _lib.DfhError(f"{type(self).__name__} needs fp32 parameters on one device")
         total = sum(_align(p.numel()) for p in plist)
         self.flat_param = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_grad = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._alloc_state(total, dev)
         self._sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self._slices = {}
         self._group_ranges = []
@@ -76,6 +75,21 @@ class FusedAdamW(torch.optim.Optimizer):
         self._zero_epoch = _lib.grad_epoch()      # gradients stamped at or after this epoch are fresh
         self._pstep = {}                          # id(param) -> number of updates it has received (torch: state[p]["step"])
         self._all_fresh = False                   # zero_grad(set_to_none=False): torch's "zeros, not None" -> everything updates
+
+    # the two places a subclass with another state format differs (AdamW8bit): what the moments are stored in, and the update launch
+    def _alloc_state(self, total: int, dev) -> None:
+        self.exp_avg = torch.zeros(total, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(total, dtype=torch.float32, device=dev)
+
+    def _launch_update(self, lo: int, fe: int, hi: int, hyper: tuple, ema, ema_decay: float, s) -> None:
+        """Update the flat range [lo, hi): [lo, fe) with the EMA of ``ema`` folded in, [fe, hi) without."""
+        if fe > lo:
+            _lib.call("dfh_adamw_ema", self.flat_param.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + 4 * lo,
+                      self.exp_avg.data_ptr() + 4 * lo, self.exp_avg_sq.data_ptr() + 4 * lo, ema.flat.data_ptr() + 4 * lo,
+                      fe - lo, *hyper, float(ema_decay), s)
+        if hi > fe:
+            _lib.call("dfh_adamw", self.flat_param.data_ptr() + 4 * fe, self.flat_grad.data_ptr() + 4 * fe,
+                      self.exp_avg.data_ptr() + 4 * fe, self.exp_avg_sq.data_ptr() + 4 * fe, hi - fe, *hyper, s)
 
     def _fresh(self, p) -> bool:
         """torch.optim.AdamW skips parameters whose ``.grad`` is None.  The gradient views here are never None, so freshness
@@ -248,13 +262,7 @@ class FusedAdamW(torch.optim.Optimizer):
                               float(ema_decay), s)
                 cursor = hi
                 fe = min(hi, max(lo, ema_end))         # [lo, fe): fused with the EMA update, [fe, hi): plain
-                if fe > lo:
-                    _lib.call("dfh_adamw_ema", self.flat_param.data_ptr() + 4 * lo, self.flat_grad.data_ptr() + 4 * lo,
-                              self.exp_avg.data_ptr() + 4 * lo, self.exp_avg_sq.data_ptr() + 4 * lo, ema.flat.data_ptr() + 4 * lo,
-                              fe - lo, *hyper, float(ema_decay), s)
-                if hi > fe:
-                    _lib.call("dfh_adamw", self.flat_param.data_ptr() + 4 * fe, self.flat_grad.data_ptr() + 4 * fe,
-                              self.exp_avg.data_ptr() + 4 * fe, self.exp_avg_sq.data_ptr() + 4 * fe, hi - fe, *hyper, s)
+                self._launch_update(lo, fe, hi, hyper, ema, ema_decay, s)
         self._collective_fresh = None
         _lib.bump_weight_epoch()          # packed bf16 copies of these weights are stale now
         return loss
@@ -288,6 +296,126 @@ class FusedAdamW(torch.optim.Optimizer):
                     self._pstep[id(p)] = int(float(st["step"]))
                     self._step = max(self._step, self._pstep[id(p)])
                 idx += 1
+
+
+Q8_BLOCK = 64      # elements per quantisation block == _align's granule: no block straddles two parameters
+
+
+def q8_table(signed: bool):
+    """The 256 ascending fp32 entries of the library's 8-bit state type (``dfh_q8_table``; host only, no GPU needed): the dynamic
+    (tree) type of Dettmers et al., signed for ``exp_avg`` (no -1; the code of 0 is 127), unsigned for ``exp_avg_sq`` (the code of 0
+    is 0)."""
+    import ctypes
+    import numpy as np
+    buf = (ctypes.c_float * 256)()
+    _lib.call("dfh_q8_table", 1 if signed else 0, buf)
+    return np.frombuffer(buf, dtype=np.float32).copy()
+
+
+class AdamW8bit(FusedAdamW):
+    """``FusedAdamW`` with block-wise 8-bit optimizer states: the reference's ``bnb.optim.AdamW8bit`` under ``--use_8bit_adam``
+    (train.py:573-593), called the same way.  Everything but the state format and the update launch is the parent's.
+
+    Each block of 64 consecutive elements of the flat buffers keeps one fp32 ``absmax`` per moment and each element one ``uint8``
+    code per moment into the dynamic (tree) 8-bit tables of Dettmers et al. (``q8_table``); ``x = table[code] * absmax``.  The
+    update runs in fp32 on the dequantised moments and moves the parameter by the unquantised new ones: 2.125 B of state per
+    parameter instead of 8.
+
+    Deviations from bitsandbytes, on purpose:
+      * a second moment ``v > 0`` never takes code 0 (it takes code 1, ``3.25e-7 * absmax``): gradient scales inside a block span
+        more decades than the table, and a ``v`` rounded to 0 lets ``m / (sqrt(v) + eps)`` explode on the next small gradient;
+      * ``min_8bit_size`` is not built: every parameter is 8-bit (64-element blocks already give a small tensor a scale of its own,
+        and a per-tensor fp32 exemption would break the few-launches-over-one-flat-buffer design);
+      * no percentile clipping, paged state, stochastic rounding or ``amsgrad``; the stored state is not bit-compatible.
+    A block that holds a NaN / Inf moment stores a non-finite ``absmax``: the whole block reads back non-finite on the next step."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, *,
+                 max_grad_norm: Optional[float] = None, ddp_group="default", min_8bit_size: int = 0):
+        if min_8bit_size != 0:
+            raise _lib.DfhError(f"AdamW8bit(min_8bit_size={min_8bit_size}): not built -- every parameter keeps 8-bit states here (a "
+                                "deliberate deviation from bitsandbytes: 64-element blocks give small tensors a private scale); pass 0")
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, ddp_group=ddp_group)
+
+    def _alloc_state(self, total: int, dev) -> None:
+        _lib.require_bf16("AdamW8bit")
+        self.state1 = torch.full((total,), 127, dtype=torch.uint8, device=dev)         # exp_avg codes: 127 is the code of 0
+        self.state2 = torch.zeros(total, dtype=torch.uint8, device=dev)                 # exp_avg_sq codes
+        self.absmax1 = torch.zeros(total // Q8_BLOCK, dtype=torch.float32, device=dev)
+        self.absmax2 = torch.zeros(total // Q8_BLOCK, dtype=torch.float32, device=dev)
+
+    def state_bytes(self) -> int:
+        """Resident optimizer state: two codes per element, two fp32 absmax per 64 elements."""
+        return sum(t.numel() * t.element_size() for t in (self.state1, self.state2, self.absmax1, self.absmax2))
+
+    def _launch_update(self, lo: int, fe: int, hi: int, hyper: tuple, ema, ema_decay: float, s) -> None:
+        for a, b, e in ((lo, fe, ema), (fe, hi, None)):       # [lo, fe): with the EMA shadow, [fe, hi): without
+            if b > a:
+                _lib.call("dfh_adamw8", self.flat_param.data_ptr() + 4 * a, self.flat_grad.data_ptr() + 4 * a,
+                          self.state1.data_ptr() + a, self.absmax1.data_ptr() + 4 * (a // Q8_BLOCK),
+                          self.state2.data_ptr() + a, self.absmax2.data_ptr() + 4 * (a // Q8_BLOCK),
+                          None if e is None else e.flat.data_ptr() + 4 * a, b - a, *hyper, float(ema_decay) if e is not None else 0.0, s)
+
+    def dequantized_state(self, p):
+        """(exp_avg, exp_avg_sq) of one parameter as fp32 tensors shaped like it (``dfh_q8_dequantize``): for inspection and tests."""
+        off, n = self._slices[id(p)]
+        out = []
+        for codes, absmax, signed in ((self.state1, self.absmax1, 1), (self.state2, self.absmax2, 0)):
+            x = torch.empty(_align(n), dtype=torch.float32, device=codes.device)
+            _lib.call("dfh_q8_dequantize", codes.data_ptr() + off, absmax.data_ptr() + 4 * (off // Q8_BLOCK), _lib.ptr(x), _align(n),
+                      signed, _lib.stream_ptr())
+            out.append(x[:n].view(p.shape))
+        return tuple(out)
+
+    def state_dict(self):
+        """Per parameter: ``step``; ``state1`` / ``state2`` (uint8 codes of exp_avg / exp_avg_sq, shaped like the parameter);
+        ``absmax1`` / ``absmax2`` (fp32, ``ceil(numel / 64)`` entries)."""
+        state, idx = {}, 0
+        groups = []
+        for g in self.param_groups:
+            ids = []
+            for p in g["params"]:
+                off, n = self._slices[id(p)]
+                b0, nb = off // Q8_BLOCK, _align(n) // Q8_BLOCK
+                state[idx] = dict(step=torch.tensor(float(self._pstep.get(id(p), 0))),
+                                  state1=self.state1[off:off + n].view(p.shape).clone(), state2=self.state2[off:off + n].view(p.shape).clone(),
+                                  absmax1=self.absmax1[b0:b0 + nb].clone(), absmax2=self.absmax2[b0:b0 + nb].clone())
+                ids.append(idx)
+                idx += 1
+            groups.append({**{k: v for k, v in g.items() if k != "params"}, "params": ids})
+        return {"state": state, "param_groups": groups}
+
+    def load_state_dict(self, sd):
+        """Accepts the 8-bit form of ``state_dict()`` (restored bit for bit) and the fp32 form of ``FusedAdamW`` /
+        ``torch.optim.AdamW`` (``exp_avg`` / ``exp_avg_sq``; quantised on load), so a run can switch optimizers at a checkpoint."""
+        idx = 0
+        dev = self.state1.device
+        for g, sg in zip(self.param_groups, sd["param_groups"]):
+            for k, v in sg.items():
+                if k != "params":
+                    g[k] = v
+            for p in g["params"]:
+                st = sd["state"].get(idx, sd["state"].get(str(idx)))
+                idx += 1
+                if st is None:
+                    continue
+                off, n = self._slices[id(p)]
+                b0, nb = off // Q8_BLOCK, _align(n) // Q8_BLOCK
+                if "state1" in st:
+                    self.state1[off:off + n].copy_(st["state1"].reshape(-1))
+                    self.state2[off:off + n].copy_(st["state2"].reshape(-1))
+                    self.absmax1[b0:b0 + nb].copy_(st["absmax1"].reshape(-1))
+                    self.absmax2[b0:b0 + nb].copy_(st["absmax2"].reshape(-1))
+                elif "exp_avg" in st:
+                    for key, codes, absmax, signed in (("exp_avg", self.state1, self.absmax1, 1), ("exp_avg_sq", self.state2, self.absmax2, 0)):
+                        x = torch.zeros(_align(n), dtype=torch.float32, device=dev)      # the padding of the last block quantises to zero codes
+                        x[:n].copy_(st[key].reshape(-1))
+                        _lib.call("dfh_q8_quantize", _lib.ptr(x), codes.data_ptr() + off, absmax.data_ptr() + 4 * b0, _align(n), signed,
+                                  _lib.stream_ptr())
+                else:
+                    raise _lib.DfhError("AdamW8bit.load_state_dict: a parameter's state holds neither state1/state2/absmax1/absmax2 nor "
+                                        "exp_avg/exp_avg_sq")
+                self._pstep[id(p)] = int(float(st["step"]))
+                self._step = max(self._step, self._pstep[id(p)])
 
 
 class EMAModel:

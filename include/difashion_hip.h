@@ -872,6 +872,20 @@ int dfh_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, 
 int dfh_adamw_ema(float* p, const float* g, float* m, float* v, float* shadow, size_t n, float lr, float beta1, float beta2, float eps,
                   float weight_decay, int step, const float* sumsq, float max_norm, float ema_decay, void* stream);
 int dfh_ema(float* shadow, const float* p, size_t n, float decay, void* stream);
+/* AdamW with block-wise 8-bit optimizer states (the reference's bnb.optim.AdamW8bit under --use_8bit_adam, train.py:573-593).  A block is
+ * 64 consecutive elements; each block has one fp32 absmax per moment, each element one uint8 code per moment, x = table[code] * absmax.
+ * The tables are the dynamic (tree) 8-bit type of Dettmers et al., 256 ascending fp32 entries: signed (exp_avg; no -1, code of 0 = 127)
+ * and unsigned (exp_avg_sq; code of 0 = 0).  Quantising takes absmax = max |x| exactly and the nearest entry, with three fixed rules: an
+ * all-zero block stores absmax 0 and zero codes; a second moment v > 0 never takes code 0 (it takes code 1); a block that holds a NaN or
+ * an Inf stores a non-finite absmax.  Every device entry point needs n % 64 == 0 and 16-byte aligned fp32 buffers; the fp16-storage
+ * library refuses them like dfh_adamw.  dfh_q8_table is host only (no GPU needed) and answers in both libraries.
+ * dfh_adamw8 = dfh_adamw / dfh_adamw_ema (shadow may be NULL) on such states: the parameter moves by the unquantised new moments. */
+int dfh_q8_table(int is_signed, float* out256_host);
+int dfh_q8_quantize(const float* x, unsigned char* codes, float* absmax, size_t n, int is_signed, void* stream);
+int dfh_q8_dequantize(const unsigned char* codes, const float* absmax, float* x, size_t n, int is_signed, void* stream);
+int dfh_adamw8(float* p, const float* g, unsigned char* m8, float* m_absmax, unsigned char* v8, float* v_absmax,
+               float* shadow /* may be NULL */, size_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+               int step, const float* sumsq /* may be NULL */, float max_norm, float ema_decay, void* stream);
 /* bf16 wire format of the data-parallel gradient exchange (replaces DDP's fp32 all-reduce behind accelerator.backward, train.py:611,699;
  * difashion_amd/dist.py exchange_bf16): fp32 range -> bf16 wire of n_pad elements (zero padding, n_pad % 8 == 0) | this rank's shard =
  * the `world` received contributions ([world][per] bf16) summed in fp32 in rank order, / world, rounded once | bf16 wire -> fp32 range */
