@@ -272,6 +272,8 @@ int dfh_groupnorm_bwd(const void* src0, int c0, const void* src1, int c1, const 
   a.dx0 = (bf16_t*)dx0; a.dx1 = (bf16_t*)dx1; a.acc0 = acc0; a.acc1 = acc1; a.dgamma = dgamma; a.dbeta = dbeta; a.partial = partial;
   return dfh::groupnorm_bwd_launch(a, (hipStream_t)stream);
 }
+// dfh_attention that also reports the log2-domain LSE for the backward.  At d = 40 / 80 below the 32x32 kernel's sizes the scores come
+// from bf16(Q * scale * log2(e)), as the backward takes them, so O may differ from dfh_attention's in the last bf16 bits there.
 int dfh_attention_lse(const void* Q, int ldq, const void* K, int ldk, const void* Vt, int ldvt, void* O, int ldo, int batch,
                       int heads, int head_dim, int Nq, int Nk, float scale, float* lse, void* stream) {
   AttnArgs a; std::memset(&a, 0, sizeof(a));

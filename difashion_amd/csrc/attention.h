@@ -34,6 +34,10 @@ struct AttnBwdArgs {
   bf16_t* dV; int lddv;          // [B][Nk][lddv]
   int B, H, D, Nq, Nk;
   float scale;
+  // Written by attention_bwd_launch from attention_fwd_q_prescaled, whatever the caller left here: the forward that produced `lse`
+  // pre-scaled Q by scale * log2(e) and rounded it (d = 64 on the 32x32 kernel); both passes then take their scores from the same
+  // rounded Q, so that P belongs to that LSE
+  int q_scaled;
 };
 
 #ifdef __HIPCC__
@@ -57,6 +61,9 @@ DFH_DEVICE float attn_qmul(const AttnArgs& a, int b) {
 
 namespace dfh {
 int attention_launch(const AttnArgs& a, hipStream_t stream);
+// did the forward that reports an LSE at these sizes round Q * scale * log2(e) where the plain backward scales the fp32 score?  Answered
+// by attention_launch's own dispatch predicate (attention.hip)
+bool attention_fwd_q_prescaled(int D, int Nq, int Nk);
 // operand factors of the fp8 attention from the LayerNorm-folded projection weights wf [3C][C] (rows q | k | v) and biases bf [3C]
 int attn_scales_launch(const bf16_t* wf, const float* bf, int C, int heads, float* rq, float* rk, float* rv, float* hs, hipStream_t stream);
 // delta[b][h][q] = sum_d dO[b][q][h*D+d] * O[b][q][h*D+d]

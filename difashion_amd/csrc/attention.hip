@@ -29,6 +29,7 @@
 #include "walk_knobs.h"
 
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 namespace {
@@ -64,6 +65,13 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
   const bf16_t* Kb = a.K + (long)b * a.Nk * a.ldk + h * D;
   const bf16_t* Vb = a.Vt + (long)b * (a.vt_bstride ? a.vt_bstride : (long)a.H * D * a.ldvt) + (long)h * D * a.ldvt;
 
+  // Training (an LSE is asked for) at the head dims whose backward carries scale * log2(e) on a rounded operand (attention_bwd.hip PADS:
+  // d = 40, 80): Q is pre-scaled and rounded to the storage type here as well, exactly as the 32x32 kernel (x32_q_frags) and the dQ pass
+  // do it, so that the P the backward recomputes belongs to the LSE this kernel reports.  With the scale on the fp32 score instead, a
+  // one-hot row at |s| = 146 log2 units came back from the dK / dV pass as P = 1.20 (tests/test_gpu_attention_parity.py, leg A2, d = 40
+  // at 200 x 77).  Without an LSE pointer nothing changes.
+  const float c_raw = a.scale * 1.44269504088896340736f;   // fold log2(e): p = 2^(s*c - m)
+  const bool prescale = (D == 40 || D == 80) && a.lse != nullptr;
   // ---- Q fragments (B operand of S^T = K.Q^T): lane holds Q[q = fr][d = ks*32 + fg*8 ..+8]
   h16x8_t qf[2][KS];
 #pragma unroll
@@ -73,7 +81,16 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
     for (int ks = 0; ks < KS; ++ks) {
       const int d0 = ks * 32 + fg * 8;
       uint4 v = uint4{0, 0, 0, 0};
-      if (q < a.Nq && d0 < D) v = *(const uint4*)(Qb + (long)q * a.ldq + d0);
+      if (q < a.Nq && d0 < D) {
+        v = *(const uint4*)(Qb + (long)q * a.ldq + d0);
+        if (prescale) {
+          float f[8];
+          unpack8(v, f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) f[e] *= c_raw;
+          v = pack8(f);
+        }
+      }
       qf[qt][ks] = __builtin_bit_cast(h16x8_t, v);
     }
   }
@@ -145,7 +162,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const AttnArgs a) {
     for (int f = 0; f < DF; ++f) oacc[qt][f] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   float m_run[2] = {-INFINITY, -INFINITY};   // running max in units of s*c (log2 domain)
   float l_run[2] = {0.f, 0.f};
-  const float c = a.scale * 1.44269504088896340736f;   // fold log2(e): p = 2^(s*c - m)
+  const float c = prescale ? 1.0f : c_raw;                // the factor still owed by the fp32 score
 
   const int ntiles = (a.Nk + KV_TILE - 1) / KV_TILE;
   load_tile(0, std::false_type{});
@@ -304,14 +321,28 @@ int attention_x32_launch(const AttnArgs& a, hipStream_t stream);
 bool attention_fp8_eligible(const AttnArgs& a);
 int attention_fp8_launch(const AttnArgs& a, hipStream_t stream);
 
+// The one place that decides whether the 32x32 kernel runs.  attention_launch dispatches on it and attention_bwd_launch asks
+// attention_fwd_q_prescaled, so a change here (another field read, another knob) moves the forward and the backward together.
+static bool takes_x32(const AttnArgs& a) {
+  return WalkKnobs::get().attn_x32 && attention_x32_eligible(a);   // DFH_ATTN_X32=0: A/B switch for the microbenchmarks
+}
+
+// True when the forward that reports an LSE for these sizes took its scores from bf16(Q * scale * log2(e)) while the backward's plain
+// path would scale the fp32 score: d = 64 on the 32x32 kernel.  (d = 40 / 80 round a pre-scaled operand on every path.)  The fp8 forward
+// takes no LSE, so it never stands in front of a backward.
+bool attention_fwd_q_prescaled(int D, int Nq, int Nk) {
+  AttnArgs f; std::memset(&f, 0, sizeof(f));
+  f.D = D; f.Nq = Nq; f.Nk = Nk;
+  return D == 64 && takes_x32(f);
+}
+
 int attention_launch(const AttnArgs& a, hipStream_t stream) {
   DFH_REQUIRE(a.Nq > 0 && a.Nk > 0 && a.B > 0 && a.H > 0, "empty attention");
   DFH_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldvt % 8 == 0 && a.ldo % 4 == 0, "leading dims must be 16-byte aligned");
   DFH_REQUIRE(a.ldvt >= ((a.Nk + 7) / 8) * 8, "V^T rows must be padded to a multiple of 8 keys");
   DFH_REQUIRE(a.O8 ? a.o_amax != nullptr : a.O != nullptr, "attention: no output (bf16 O, or e4m3 O8 with the per-batch maxima of V)");
   if (attention_fp8_eligible(a)) return attention_fp8_launch(a, stream);
-  const bool x32_off = !WalkKnobs::get().attn_x32;   // DFH_ATTN_X32=0: A/B switch for the microbenchmarks
-  if (!x32_off && attention_x32_eligible(a)) return attention_x32_launch(a, stream);
+  if (takes_x32(a)) return attention_x32_launch(a, stream);
   census(CK_ATTN_16);
   switch (a.D) {
     case 32: return launch<32>(a, stream);

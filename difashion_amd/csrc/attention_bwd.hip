@@ -111,6 +111,10 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
   constexpr int KS32 = (D + 8 + 15) / 16;
   constexpr float MASKV = -30000.0f;
   const float c = a.scale * 1.44269504088896340736f;
+  // QSC (d = 64 behind the 32x32 forward, AttnBwdArgs::q_scaled): Q is pre-scaled by c and rounded wherever it enters -- as the column
+  // operand of the dQ pass, as the streamed tile of the dK / dV pass (whose dK = dS^T Q then carries 1 / c, taken back at the store)
+  const bool qsc = !PADS && D == 64 && a.q_scaled != 0;
+  const float c_s = qsc ? 1.0f : c;                  // the factor still owed by the fp32 score (non-PADS)
   auto split2 = [](float v) {                       // v ~ hi + lo, both bf16
     const float hi = bf2f((bf16_t)(pack2bf(v, 0.f) & 0xffffu));
     return pack2bf(hi, v - hi);
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
       if (col < ncols && d0 < D) {
         v1 = *(const uint4*)(Y1 + (long)col * ldy1 + d0);
         v2 = *(const uint4*)(Y2 + (long)col * ldy2 + d0);
-        if (PADS) {                                  // the score scale on the column operand of S (K in the dK / dV pass, Q in the dQ pass)
+        if (PADS || (qsc && !KV_SIDE)) {             // the score scale on the column operand of S (K in the dK / dV pass, Q in the dQ pass)
           float f[8];
           unpack8(v1, f);
 #pragma unroll
@@ -252,7 +256,17 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
       return;
     }
 #pragma unroll
-    for (int i = 0; i < KS; ++i) { *(uint4*)(T1 + s_lds[i]) = r1[i]; *(uint4*)(T2 + s_lds[i]) = r2[i]; }
+    for (int i = 0; i < KS; ++i) {
+      uint4 w1 = r1[i];
+      if (KV_SIDE && qsc) {                          // the streamed Q rows carry the scale.  Here and not in load_tile: behind the loads the
+        float f[8];                                  // multiply puts an s_waitcnt ahead of the MFMAs the prefetch is meant to hide under
+        unpack8(w1, f);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] *= c;
+        w1 = pack8(f);
+      }
+      *(uint4*)(T1 + s_lds[i]) = w1; *(uint4*)(T2 + s_lds[i]) = r2[i];
+    }
     if (KV_SIDE && tid < XT) {
       float* st = (float*)(T2 + G::TILE);
       st[tid] = rl; st[XT + tid] = rd;
@@ -364,7 +378,7 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
             float L, Dl;
             if (KV_SIDE) { L = st[lr]; Dl = st[XT + lr]; }
             else { L = (FAST || row0 + lr < nrows) ? col_l[nt] : INFINITY; Dl = col_d[nt]; }
-            const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(tS[nt][u][r], c, -L));
+            const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(tS[nt][u][r], c_s, -L));
             p[u * 4 + r] = pv;
             ds[u * 4 + r] = pv * (tU[nt][u][r] - Dl);
           }
@@ -408,8 +422,9 @@ __global__ __launch_bounds__(256, ((D <= 40 && !KV_SIDE) ? 3 : 1)) void attentio
       const int d0 = f * 16 + fg * 4;
       if (d0 >= D) continue;
       uint2 o;
-      o.x = pack2bf(acc1[nt][f][0] * a.scale, acc1[nt][f][1] * a.scale);
-      o.y = pack2bf(acc1[nt][f][2] * a.scale, acc1[nt][f][3] * a.scale);
+      const float os = (KV_SIDE && qsc) ? a.scale / c : a.scale;      // dK from the pre-scaled Q tiles: scale / c = ln 2
+      o.x = pack2bf(acc1[nt][f][0] * os, acc1[nt][f][1] * os);
+      o.y = pack2bf(acc1[nt][f][2] * os, acc1[nt][f][3] * os);
       *(uint2*)(o1 + d0) = o;
       if (KV_SIDE) {
         bf16_t* o2 = a.dV + ((long)b * a.Nk + col) * a.lddv + h * D;
@@ -502,10 +517,16 @@ int attention_bwd_launch(const AttnBwdArgs& a, hipStream_t stream) {
   DFH_REQUIRE(a.ldq % 8 == 0 && a.ldk % 8 == 0 && a.ldv % 8 == 0 && a.ldo % 8 == 0, "leading dims must be 16-byte aligned");
   DFH_REQUIRE(a.lddq % 4 == 0 && a.lddk % 4 == 0 && a.lddv % 4 == 0, "gradient leading dims must be 8-byte aligned");
   DFH_REQUIRE(a.lse && a.delta && a.dQ && a.dK && a.dV, "null pointer");
+  if (a.D == 64) {
+    // d = 64 is the one head dim whose forward rounds Q c (32x32 kernel) while this backward scales the fp32 score.  The forward's own
+    // dispatch predicate (attention.hip) says whether that kernel produced `lse`; both passes then round Q the same way.
+    AttnBwdArgs b = a;
+    b.q_scaled = attention_fwd_q_prescaled(a.D, a.Nq, a.Nk);
+    return launch_bwd<64>(b, stream);
+  }
   switch (a.D) {
     case 32: return launch_bwd<32>(a, stream);
     case 40: return launch_bwd<40>(a, stream);
-    case 64: return launch_bwd<64>(a, stream);
     case 80: return launch_bwd<80>(a, stream);
     case 128: return launch_bwd<128>(a, stream);
     case 160: return launch_bwd<160>(a, stream);

@@ -430,7 +430,8 @@ int launch_x32(const AttnArgs& a, hipStream_t stream) {
 
 namespace dfh {
 
-// 0 = not handled here (the caller falls back to attention_kernel)
+// 0 = not handled here (the caller falls back to attention_kernel).  The backward depends on this answer too, through takes_x32 /
+// attention_fwd_q_prescaled in attention.hip: at d = 64 it rounds Q as this kernel does exactly where this says yes.
 bool attention_x32_eligible(const AttnArgs& a) {
   // 40 / 80: SD-1.5 (8 heads); 64: SD-2-base, the reference's own default (stabilityai/stable-diffusion-2-base, train.py:44,
   // inf4eval.py:65: head dim 64 at every level)
