@@ -179,7 +179,7 @@ __global__ void geglu_bwd_kernel(const bf16_t* __restrict__ pre, const bf16_t* _
     const float x = g[k];
     const float cdf = 0.5f * (1.0f + erf_as_f(x * 0.70710678118654752440f));
     const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
-    dv[k] = d[k] * x * cdf;
+    dv[k] = d[k] * (x * cdf);                        // (d * x) * cdf overflows to inf * 0 = NaN for a finite gate beyond 3.4e38 / |d|
     dg[k] = d[k] * v[k] * (cdf + x * pdf);
   }
   bf16_t* orow = dpre + m * N2 + blk * 32 + half * 8;
@@ -199,17 +199,27 @@ __global__ void geglu_fwd_kernel(const bf16_t* __restrict__ pre, bf16_t* __restr
   unpack8(*(const uint4*)prow, v);
   unpack8(*(const uint4*)(prow + 16), g);
 #pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = v[k] * gelu_erf_f(g[k]);
+  for (int k = 0; k < 8; ++k) {
+    // gelu_erf_f is good to 5.5e-7 ABSOLUTE, which is a relative error of up to a few per cent where gelu is 1e-4 and less (gates
+    // below -3.5) and moves the bf16 rounding elsewhere; the backward differentiates the exact function.  This kernel is bound by
+    // HBM, not the VALU, so it takes the library's erfc; the GEMM epilogues keep gelu_erf_f (tests/test_gpu_pointwise.py)
+    const float x = g[k];
+    v[k] = v[k] * (0.5f * x * erfcf(x * -0.70710678118654752440f));
+  }
   *(uint4*)(y + m * (N2 / 2) + blk * 16 + half * 8) = pack8(v);
 }
 
 // pointwise activation forward / backward on bf16 rows (time-embedding MLP, MutualEncoder)
 //   kind 1 silu (from pre-activation), 2 leaky_relu 0.01 (sign from the OUTPUT), 3 tanh (from the OUTPUT)
+//   silu below -87: 1 + e^-x overflows fp32 at x = -88.7 and x * sigmoid(x) would come out -0 where x e^x is still a bf16 number (down
+//   to x = -97.8); there sigmoid(x) = e^x to 1e-38, taken as e^(x + 32) * e^-32 so that only the last product is subnormal
+constexpr float SILU_TAIL = -87.0f, EXP_M32 = 1.2664165549094176e-14f;
 __global__ void act_fwd_kernel(const bf16_t* __restrict__ pre, bf16_t* __restrict__ y, long n, int kind) {
   const long i = gtid();
   if (i >= n) return;
   const float x = bf2f(pre[i]);
-  y[i] = f2bf(kind == 1 ? silu_f(x) : (kind == 2 ? (x > 0.f ? x : 0.01f * x) : tanhf(x)));
+  const float silu = x < SILU_TAIL ? x * __expf(x + 32.0f) * EXP_M32 : silu_f(x);
+  y[i] = f2bf(kind == 1 ? silu : (kind == 2 ? (x > 0.f ? x : 0.01f * x) : tanhf(x)));
 }
 __global__ void act_bwd_kernel(const bf16_t* __restrict__ ref, const float* __restrict__ ref_f32, const bf16_t* __restrict__ dy,
                                const float* __restrict__ dy_f32, bf16_t* __restrict__ dpre, long n, int kind, float scale) {
@@ -218,7 +228,10 @@ __global__ void act_bwd_kernel(const bf16_t* __restrict__ ref, const float* __re
   const float r = ref_f32 ? ref_f32[i] : bf2f(ref[i]);
   const float d = (dy_f32 ? dy_f32[i] : bf2f(dy[i])) * scale;
   float g;
-  if (kind == 1) { const float s = 1.0f / (1.0f + __expf(-r)); g = s * (1.0f + r * (1.0f - s)); }
+  if (kind == 1) {
+    const float s = 1.0f / (1.0f + __expf(-r));
+    g = r < SILU_TAIL ? __expf(r + 32.0f) * (1.0f + r) * EXP_M32 : s * (1.0f + r * (1.0f - s));   // the tail as in act_fwd_kernel
+  }
   else if (kind == 2) g = r > 0.f ? 1.0f : 0.01f;
   else g = 1.0f - r * r;
   dpre[i] = f2bf(d * g);
