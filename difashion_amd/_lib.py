@@ -83,6 +83,14 @@ class CLIPVHalfPlanC(C.Structure):
                 ("regions", CLIPVHalfRegionC * CLIPVH_MAX_REGIONS)]
 
 
+class CLIPTHalfPlanC(C.Structure):
+    """dfh_cliph_plan_info: the 16-bit text tower's plan (launches and regions in the image tower's record types)."""
+    _fields_ = [(n, C.c_int) for n in ("batch", "tokens", "hidden", "intermediate", "heads", "head_dim", "layers", "rows",
+                                       "attention_lds_bytes", "num_launches", "num_regions")] + \
+               [("workspace_bytes", C.c_size_t), ("packed_bytes", C.c_size_t), ("launches", CLIPVHalfLaunchC * CLIPVH_MAX_LAUNCHES),
+                ("regions", CLIPVHalfRegionC * CLIPVH_MAX_REGIONS)]
+
+
 class ImgProcConfigC(C.Structure):
     _fields_ = [("shortest_edge", C.c_int), ("crop_height", C.c_int), ("crop_width", C.c_int), ("resample", C.c_int)]
 
@@ -212,6 +220,13 @@ SIGNATURES = {
     "dfh_clipvh_pack": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp]),
     "dfh_clipvh_workspace_bytes": (_sz, [_vp, _i]),
     "dfh_clipvh_encode": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp, _i, _i, _vp, _vp, _vp, C.POINTER(_vp), _vp, _sz, _vp]),
+    "dfh_cliph_plan": (_i, [_vp, _i, _i, C.POINTER(CLIPTHalfPlanC)]),
+    "dfh_cliph_packed_bytes": (_sz, [_vp]),
+    "dfh_cliph_pack": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp]),
+    "dfh_cliph_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "dfh_cliph_encode": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _i, _i, _vp]),
+    "dfh_cliph_text_embeds": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _i, _i, _vp]),
+    "dfh_causal_attention": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "dfh_imgproc_create": (_i, [C.POINTER(ImgProcConfigC), _i, _i, _i, C.POINTER(_vp)]),
     "dfh_imgproc_destroy": (None, [_vp]),
     "dfh_imgproc_resized_height": (_i, [_vp]),

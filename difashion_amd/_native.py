@@ -222,7 +222,9 @@ class TupleOutput:
 
 class ClipTower(NativeModule):
     """What CLIPTextModel and CLIPVisionModelWithProjection share: fp32 masters read in place (no arenas, no pack step), one workspace
-    block, the transformers checkpoint directory.  A subclass supplies ``family``, ``architecture``, ``model_type``, ``_c_config()``."""
+    block, the transformers checkpoint directory, and the opt-in 16-bit compute mode (``torch_dtype=`` / ``set_compute_dtype`` /
+    ``.half()`` / ``.bfloat16()`` over a packed copy).  A subclass supplies ``family``, ``half_family``, ``architecture``, ``model_type``,
+    ``_c_config()`` and ``_check_half_config()``."""
     weights_name = "model.safetensors"
     _fp32_rule = "parameters must stay fp32 (the kernels read them in place)"
     _ACT = {"quick_gelu": 1, "gelu": 2}
@@ -253,14 +255,98 @@ class ClipTower(NativeModule):
         require_params_on(dev, plist)
         return self._pointers(plist), len(plist)
 
+    # ------------------------------------------------------------------ compute precision (the parameters are never cast)
+    # A tower computes in float32 (the default walk, dfh_<family>_*) or, opt-in, in the process's 16-bit storage format (the walk of
+    # dfh_<half_family>_* over a packed 16-bit copy of the weights).  The masters, state_dict() and checkpoints stay fp32 either way.
+    half_family: str = ""                # entry-point prefix of the 16-bit walk: dfh_<half_family>_plan / _packed_bytes / _pack / ...
+    _compute_dtype = torch.float32
+    _packed = None
+
+    @property
+    def compute_dtype(self) -> torch.dtype:
+        """``torch.float32`` (the default tower) or the process's 16-bit storage dtype.  ``.dtype`` stays the parameters' float32."""
+        return self._compute_dtype
+
+    def _check_half_config(self) -> None:
+        """Refuse a config the 16-bit walk cannot run (host-only work: the plan of the 16-bit family says)."""
+        raise NotImplementedError
+
+    def set_compute_dtype(self, dtype):
+        """Select the tower ``forward`` runs: ``torch.float32``, or the 16-bit storage format of this process (``torch.bfloat16`` under
+        the default library, ``torch.float16`` under ``DFH_STORAGE=fp16``)."""
+        if isinstance(dtype, str):
+            dtype = getattr(torch, dtype, dtype)
+        if not isinstance(dtype, torch.dtype) or not dtype.is_floating_point:
+            raise TypeError(f"set_compute_dtype: a floating torch.dtype is expected, got {dtype!r}")
+        if dtype == torch.float32:
+            self._compute_dtype = torch.float32          # the packed copy stays: its signature says whether it is still current
+            return self
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise _lib.DfhError(f"{self.architecture} computes in float32 or in {_lib.storage_dtype()}, not in {dtype}; the "
+                                "parameters stay fp32 either way")
+        if dtype != _lib.storage_dtype():
+            raise _lib.DfhError(f"{dtype} is not this process's 16-bit format: the {_lib.storage()}-storage kernel library is selected, and "
+                                f"the format is a property of the process (DFH_STORAGE / set_storage() choose it before first use), so the "
+                                f"tower computes in float32 or {_lib.storage_dtype()} here.  Whatever the mode, the parameters stay fp32 "
+                                "(the 16-bit weights are a packed copy)")
+        self._check_half_config()
+        self._compute_dtype = dtype
+        return self
+
+    def half(self):
+        return self.set_compute_dtype(torch.float16)
+
+    def bfloat16(self):
+        return self.set_compute_dtype(torch.bfloat16)
+
+    def float(self):
+        return self.set_compute_dtype(torch.float32)
+
+    def double(self):
+        return self.set_compute_dtype(torch.float64)
+
+    def to(self, *args, **kwargs):
+        """``nn.Module.to`` whose dtype part selects the compute precision instead of casting the parameters."""
+        device, dtype, non_blocking, _ = torch._C._nn._parse_to(*args, **kwargs)
+        if dtype is not None:
+            self.set_compute_dtype(dtype)
+        return super().to(device, non_blocking=non_blocking) if device is not None else self
+
+    def _prepare_half(self, dev: torch.device, *batch_args):
+        """``_prepare`` of the 16-bit tower: its workspace, and a packed 16-bit copy of the weights that is current -- remade when a
+        parameter was written, replaced or moved since the last pack (the pack signature), never saved."""
+        if self._ctx is None:
+            self._ctx = self._make_ctx()
+        fam = f"dfh_{self.half_family}"
+        need = getattr(_lib.raw(), fam + "_workspace_bytes")(self._ctx, *batch_args)
+        if need == 0:
+            raise _lib.DfhError(f"{fam}_workspace_bytes refused: {_lib.last_error()}")
+        grow_buffer(self, "_ws", need, dev)
+        plist = self._plist()
+        require_params_on(dev, plist)
+        packed = self._packed
+        grow_buffer(self, "_packed", getattr(_lib.raw(), fam + "_packed_bytes")(self._ctx), dev)
+        if self._packed is not packed:
+            self._packed_sig = None                      # a new block holds no packed copy yet
+        arr, sig = self._pointers(plist), self._signature(plist)
+        if sig != self._packed_sig:
+            _lib.call(fam + "_pack", self._ctx, arr, len(plist), _lib.ptr(self._packed), _lib.stream_ptr())
+            self._packed_sig = sig
+        return arr, len(plist)
+
     # ------------------------------------------------------------------ checkpoints (transformers directory layout)
     def save_pretrained(self, save_directory: str, **unused):
         save_checkpoint(self, save_directory, dict(architectures=[self.architecture], model_type=self.model_type))
 
     @classmethod
-    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, revision=None, **unused):
+    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, revision=None,
+                        torch_dtype: Optional[torch.dtype] = None, **unused):
+        """Only the caller's ``torch_dtype=`` selects the 16-bit tower.  The ``torch_dtype`` / ``dtype`` key that transformers writes into
+        ``config.json`` records the dtype of the saved weights; as in transformers it does not choose the precision of the model."""
         from ._ckpt import TRANSFORMERS_STEMS, load_weights
         d, cfg = read_checkpoint_config(cls, path, subfolder)
+        for key in ("torch_dtype", "dtype"):
+            cfg.pop(key, None)
         model = cls(init_seed=None, **cfg)
         model.load_state_dict(load_weights(d, variant, TRANSFORMERS_STEMS))
-        return model
+        return model if torch_dtype is None else model.set_compute_dtype(torch_dtype)

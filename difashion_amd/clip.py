@@ -7,12 +7,18 @@ What the reference requires of ``self.text_encoder`` (DiFashion/models/difashion
     empty prompt (:234, :352) and the prompts of the slots a sampling call fills (:340-342); no attention mask is passed;
   * ``text_encoder.dtype`` (:342, :411-425), ``.requires_grad_(False)`` (:107), ``.to(device)``.
 
-All arithmetic runs in libdifashion_hip.so (``dfh_clip_encode``, csrc/clip.hip) in fp32 on the fp32 matrix instruction: the
+All arithmetic runs in the kernel library.  fp32 by default (``dfh_clip_encode``, csrc/clip.hip) on the fp32 matrix instruction: the
 prompts are a closed set encoded once per run (``prompts.PromptTable``), so the encoder is built to agree with the fp32 class
-to summation-order noise.  The fp32 ``nn.Parameter``s are read in place (no packed copy).  No PyTorch / CPU fallback.
+to summation-order noise; the fp32 ``nn.Parameter``s are read in place (no packed copy).  Opt-in, what the reference's
+``--mixed_precision fp16`` autocast and transformers' ``torch_dtype=`` / ``.half()`` give: the tower in the process's 16-bit storage
+format (``dfh_cliph_encode``, csrc/clip_text_half.hip; head dim 64, at most 128 tokens) -- ``torch_dtype=`` at construction or in
+``from_pretrained``, ``set_compute_dtype(dtype)``, ``.half()`` / ``.bfloat16()`` / ``.float()`` / ``.to(dtype=...)`` (``ClipTower``).
+None of these casts a parameter: masters, ``state_dict()`` and checkpoints stay fp32, the 16-bit weights are a packed copy that is
+remade whenever a parameter changes and is never saved, and every output is an fp32 tensor in both modes.  No PyTorch / CPU fallback.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional
 
 import torch
@@ -37,13 +43,26 @@ class CLIPTextModel(ClipTower):
     def __init__(self, vocab_size: int = 49408, hidden_size: int = 768, intermediate_size: int = 3072, num_hidden_layers: int = 12,
                  num_attention_heads: int = 12, max_position_embeddings: int = 77, hidden_act: str = "quick_gelu",
                  layer_norm_eps: float = 1e-5, eos_token_id: int = 2, bos_token_id: int = 49406, pad_token_id: int = 1,
-                 init_seed: Optional[int] = 0, init_std: float = 0.02, **unused):
+                 init_seed: Optional[int] = 0, init_std: float = 0.02, torch_dtype: Optional[torch.dtype] = None, **unused):
         super().__init__()
         self._init_tower(init_seed, init_std, "the CLIP text towers of SD-1.5 / SD-2 use 'quick_gelu' / 'gelu'",
                          vocab_size=vocab_size, hidden_size=hidden_size, intermediate_size=intermediate_size,
                          num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads,
                          max_position_embeddings=max_position_embeddings, hidden_act=hidden_act, layer_norm_eps=layer_norm_eps,
                          eos_token_id=eos_token_id, bos_token_id=bos_token_id, pad_token_id=pad_token_id)
+        if torch_dtype is not None:
+            self.set_compute_dtype(torch_dtype)
+
+    # ------------------------------------------------------------------ compute precision (ClipTower; the parameters are never cast)
+    half_family = "cliph"
+
+    def _check_half_config(self) -> None:
+        """Head dim 64, sizes that are multiples of 8: the plan's to say, at the longest sequence the config allows (host-only work)."""
+        ctx = self._make_ctx()
+        try:
+            _lib.call("dfh_cliph_plan", ctx, 1, min(int(self.config["max_position_embeddings"]), 128), C.byref(_lib.CLIPTHalfPlanC()))
+        finally:
+            self._entry("destroy")(ctx)
 
     # ------------------------------------------------------------------ plumbing
     def _c_config(self) -> _lib.CLIPConfigC:
@@ -84,13 +103,18 @@ class CLIPTextModel(ClipTower):
                 output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None):
         dev, ids, B, T = self._ids_on_device("CLIPTextModel", input_ids, attention_mask, position_ids, output_attentions)
         cfg = self.config
-        arr, count = self._prepare(dev, B, T)
+        half = self._compute_dtype != torch.float32
+        arr, count = self._prepare_half(dev, B, T) if half else self._prepare(dev, B, T)
         D, L = cfg["hidden_size"], cfg["num_hidden_layers"]
         last = torch.empty((B, T, D), dtype=torch.float32, device=dev)
         pooled = torch.empty((B, D), dtype=torch.float32, device=dev)
         hs = torch.empty((L + 1, B, T, D), dtype=torch.float32, device=dev) if output_hidden_states else None
-        _lib.call("dfh_clip_encode", self._ctx, arr, count, _lib.ptr(ids), _lib.ptr(last), _lib.ptr(pooled), int(cfg["eos_token_id"]),
-                  _lib.ptr(hs), _lib.ptr(self._ws), self._ws.numel(), B, T, _lib.stream_ptr())
+        tail = (_lib.ptr(ids), _lib.ptr(last), _lib.ptr(pooled), int(cfg["eos_token_id"]), _lib.ptr(hs), _lib.ptr(self._ws), self._ws.numel(), B, T,
+                _lib.stream_ptr())
+        if half:
+            _lib.call("dfh_cliph_encode", self._ctx, arr, count, _lib.ptr(self._packed), *tail)
+        else:
+            _lib.call("dfh_clip_encode", self._ctx, arr, count, *tail)
         out = BaseModelOutputWithPooling(last, pooled, tuple(hs[i] for i in range(L + 1)) if hs is not None else None)
         return out if return_dict is None or return_dict else out.to_tuple()
 
@@ -113,6 +137,7 @@ class CLIPTextModelWithProjection(CLIPTextModel):
     architecture = "CLIPTextModelWithProjection"
 
     def __init__(self, projection_dim: int = 1024, init_seed: Optional[int] = 0, init_std: float = 0.02, **text_config):
+        # text_config may carry torch_dtype=: CLIPTextModel's constructor selects the mode (text_projection is read in fp32 either way)
         super().__init__(init_seed=init_seed, init_std=init_std, **text_config)
         if projection_dim < 1:
             raise ValueError(f"projection_dim must be positive, got {projection_dim}")
@@ -131,16 +156,12 @@ class CLIPTextModelWithProjection(CLIPTextModel):
                 output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None):
         dev, ids, B, T = self._ids_on_device("CLIPTextModelWithProjection", input_ids, attention_mask, position_ids, output_attentions)
         cfg = self.config
-        arr, count = self._prepare(dev, B, T)
-        proj = self.text_projection.weight
-        require_params_on(dev, [proj])
         D, L, Pd = cfg["hidden_size"], cfg["num_hidden_layers"], cfg["projection_dim"]
         embeds = torch.empty((B, Pd), dtype=torch.float32, device=dev)
         last = torch.empty((B, T, D), dtype=torch.float32, device=dev)
         pooled = torch.empty((B, D), dtype=torch.float32, device=dev)
         hs = torch.empty((L + 1, B, T, D), dtype=torch.float32, device=dev) if output_hidden_states else None
-        _lib.call("dfh_clip_text_embeds", self._ctx, arr, count, _lib.ptr(proj), Pd, _lib.ptr(ids), _lib.ptr(embeds), _lib.ptr(pooled),
-                  _lib.ptr(last), int(cfg["eos_token_id"]), _lib.ptr(hs), _lib.ptr(self._ws), self._ws.numel(), B, T, _lib.stream_ptr())
+        self._text_embeds(dev, ids, B, T, embeds, pooled, last, hs)
         out = CLIPTextModelOutput(embeds, last, pooled, tuple(hs[i] for i in range(L + 1)) if hs is not None else None)
         return out if return_dict is None or return_dict else out.to_tuple()
 
@@ -149,11 +170,19 @@ class CLIPTextModelWithProjection(CLIPTextModel):
         """``open_clip``'s name for the projected text embedding (what ``CLIPScore.calculate_clip_score`` calls): only the pooled rows
         go through the final LayerNorm, ``last_hidden_state`` is not formed."""
         dev, ids, B, T = self._ids_on_device("CLIPTextModelWithProjection", input_ids, None, None, None)
-        arr, count = self._prepare(dev, B, T)
+        embeds = torch.empty((B, self.config["projection_dim"]), dtype=torch.float32, device=dev)
+        self._text_embeds(dev, ids, B, T, embeds, None, None, None)
+        return embeds
+
+    def _text_embeds(self, dev, ids, B, T, embeds, pooled, last, hs):
+        """One ``dfh_clip_text_embeds`` / ``dfh_cliph_text_embeds`` call of the selected tower; ``pooled`` / ``last`` / ``hs`` may be None."""
+        half = self._compute_dtype != torch.float32
+        arr, count = self._prepare_half(dev, B, T) if half else self._prepare(dev, B, T)
         proj = self.text_projection.weight
         require_params_on(dev, [proj])
-        embeds = torch.empty((B, self.config["projection_dim"]), dtype=torch.float32, device=dev)
-        _lib.call("dfh_clip_text_embeds", self._ctx, arr, count, _lib.ptr(proj), self.config["projection_dim"], _lib.ptr(ids),
-                  _lib.ptr(embeds), None, None, int(self.config["eos_token_id"]), None, _lib.ptr(self._ws), self._ws.numel(), B, T,
-                  _lib.stream_ptr())
-        return embeds
+        tail = (_lib.ptr(proj), self.config["projection_dim"], _lib.ptr(ids), _lib.ptr(embeds), _lib.ptr(pooled), _lib.ptr(last),
+                int(self.config["eos_token_id"]), _lib.ptr(hs), _lib.ptr(self._ws), self._ws.numel(), B, T, _lib.stream_ptr())
+        if half:
+            _lib.call("dfh_cliph_text_embeds", self._ctx, arr, count, _lib.ptr(self._packed), *tail)
+        else:
+            _lib.call("dfh_clip_text_embeds", self._ctx, arr, count, *tail)

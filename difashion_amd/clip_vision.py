@@ -15,7 +15,8 @@ in both storage builds, the fp32 ``nn.Parameter``s read in place (no packed copy
 (``dfh_clipvh_encode``, csrc/clip_vision_half.hip) -- ``torch_dtype=`` at construction or in ``from_pretrained``,
 ``set_compute_dtype(dtype)``, ``.half()`` / ``.bfloat16()`` / ``.float()`` / ``.to(dtype=...)``.  None of these casts a parameter: the
 masters, ``state_dict()`` and checkpoints stay fp32, and the 16-bit weights are a packed copy that is remade whenever a parameter
-changes and is never saved.  Every output is an fp32 tensor in both modes.  The text tower stays fp32.  No PyTorch / CPU fallback.
+changes and is never saved.  Every output is an fp32 tensor in both modes.  The switch itself is ``ClipTower``'s (_native.py), shared with the text tower (clip.py).
+No PyTorch / CPU fallback.
 """
 from __future__ import annotations
 
@@ -25,7 +26,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._native import ClipTower, TupleOutput, grow_buffer, require_params_on
+from ._native import ClipTower, TupleOutput
 
 
 class CLIPVisionModelOutput(TupleOutput):
@@ -54,34 +55,11 @@ class CLIPVisionModelWithProjection(ClipTower):
         if torch_dtype is not None:
             self.set_compute_dtype(torch_dtype)
 
-    # ------------------------------------------------------------------ compute precision (the parameters are never cast)
+    # ------------------------------------------------------------------ compute precision (ClipTower; the parameters are never cast)
+    half_family = "clipvh"
     HALF_HEAD_DIMS = (32, 40, 64, 80, 128, 160)          # the head dims dfh_attention's kernels are built for
-    _compute_dtype = torch.float32
-    _packed = None
 
-    @property
-    def compute_dtype(self) -> torch.dtype:
-        """``torch.float32`` (the default tower) or the process's 16-bit storage dtype.  ``.dtype`` stays the parameters' float32."""
-        return self._compute_dtype
-
-    def set_compute_dtype(self, dtype):
-        """Select the tower ``forward`` / ``encode_image`` run: ``torch.float32``, or the 16-bit storage format of this process
-        (``torch.bfloat16`` under the default library, ``torch.float16`` under ``DFH_STORAGE=fp16``)."""
-        if isinstance(dtype, str):
-            dtype = getattr(torch, dtype, dtype)
-        if not isinstance(dtype, torch.dtype) or not dtype.is_floating_point:
-            raise TypeError(f"set_compute_dtype: a floating torch.dtype is expected, got {dtype!r}")
-        if dtype == torch.float32:
-            self._compute_dtype = torch.float32          # the packed copy stays: its signature says whether it is still current
-            return self
-        if dtype not in (torch.float16, torch.bfloat16):
-            raise _lib.DfhError(f"CLIPVisionModelWithProjection computes in float32 or in {_lib.storage_dtype()}, not in {dtype}; the "
-                                "parameters stay fp32 either way")
-        if dtype != _lib.storage_dtype():
-            raise _lib.DfhError(f"{dtype} is not this process's 16-bit format: the {_lib.storage()}-storage kernel library is selected, and "
-                                f"the format is a property of the process (DFH_STORAGE / set_storage() choose it before first use), so the "
-                                f"tower computes in float32 or {_lib.storage_dtype()} here.  Whatever the mode, the parameters stay fp32 "
-                                "(the 16-bit weights are a packed copy)")
+    def _check_half_config(self) -> None:
         d = self.config["hidden_size"] // self.config["num_attention_heads"]
         if d not in self.HALF_HEAD_DIMS:
             raise _lib.DfhError(f"the 16-bit tower runs on the 16-bit attention kernels, which are built for head dims "
@@ -93,41 +71,6 @@ class CLIPVisionModelWithProjection(ClipTower):
             _lib.call("dfh_clipvh_plan", ctx, 1, C.byref(_lib.CLIPVHalfPlanC()))
         finally:
             self._entry("destroy")(ctx)
-        self._compute_dtype = dtype
-        return self
-
-    def half(self):
-        return self.set_compute_dtype(torch.float16)
-
-    def bfloat16(self):
-        return self.set_compute_dtype(torch.bfloat16)
-
-    def float(self):
-        return self.set_compute_dtype(torch.float32)
-
-    def double(self):
-        return self.set_compute_dtype(torch.float64)
-
-    def to(self, *args, **kwargs):
-        """``nn.Module.to`` whose dtype part selects the compute precision instead of casting the parameters."""
-        device, dtype, non_blocking, _ = torch._C._nn._parse_to(*args, **kwargs)
-        if dtype is not None:
-            self.set_compute_dtype(dtype)
-        return super().to(device, non_blocking=non_blocking) if device is not None else self
-
-    @classmethod
-    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, revision=None,
-                        torch_dtype: Optional[torch.dtype] = None, **unused):
-        """Only the caller's ``torch_dtype=`` selects the 16-bit tower.  The ``torch_dtype`` / ``dtype`` key that transformers writes into
-        ``config.json`` records the dtype of the saved weights; as in transformers it does not choose the precision of the model."""
-        from ._ckpt import TRANSFORMERS_STEMS, load_weights
-        from ._native import read_checkpoint_config
-        d, cfg = read_checkpoint_config(cls, path, subfolder)
-        for key in ("torch_dtype", "dtype"):
-            cfg.pop(key, None)
-        model = cls(init_seed=None, **cfg)
-        model.load_state_dict(load_weights(d, variant, TRANSFORMERS_STEMS))
-        return model if torch_dtype is None else model.set_compute_dtype(torch_dtype)
 
     # ------------------------------------------------------------------ plumbing
     def _c_config(self) -> _lib.CLIPVisionConfigC:
@@ -188,27 +131,6 @@ class CLIPVisionModelWithProjection(ClipTower):
                       taps, _lib.ptr(self._ws), self._ws.numel(), _lib.stream_ptr())
         out = CLIPVisionModelOutput(embeds, last, pooled, tuple(hs[i] for i in range(L + 1)) if hs is not None else None)
         return out if return_dict is None or return_dict else out.to_tuple()
-
-    def _prepare_half(self, dev: torch.device, batch: int):
-        """``_prepare`` of the 16-bit tower: its workspace, and a packed 16-bit copy of the weights that is current -- remade when a
-        parameter was written, replaced or moved since the last pack (the pack signature), never saved."""
-        if self._ctx is None:
-            self._ctx = self._make_ctx()
-        need = _lib.raw().dfh_clipvh_workspace_bytes(self._ctx, batch)
-        if need == 0:
-            raise _lib.DfhError(f"dfh_clipvh_workspace_bytes refused: {_lib.last_error()}")
-        grow_buffer(self, "_ws", need, dev)
-        plist = self._plist()
-        require_params_on(dev, plist)
-        packed = self._packed
-        grow_buffer(self, "_packed", _lib.raw().dfh_clipvh_packed_bytes(self._ctx), dev)
-        if self._packed is not packed:
-            self._packed_sig = None                      # a new block holds no packed copy yet
-        arr, sig = self._pointers(plist), self._signature(plist)
-        if sig != self._packed_sig:
-            _lib.call("dfh_clipvh_pack", self._ctx, arr, len(plist), _lib.ptr(self._packed), _lib.stream_ptr())
-            self._packed_sig = sig
-        return arr, len(plist)
 
     def encode_image(self, pixel_values: torch.Tensor) -> torch.Tensor:
         """``open_clip``'s name for the projected image embedding (what the reference's evaluation scripts call)."""

@@ -12,8 +12,7 @@
 // (v_mfma_f32_16x16x4_f32, 256 FLOP / clk / CU), weights are read in place from the fp32 master parameters (nn.Linear layout [N][K],
 // K contiguous: no packed copy, no arena), and the result agrees with the fp32 reference class to summation-order noise (1e-6),
 // not to bf16 noise.  No atomics: reruns are bit-identical.
-#include "../../include/difashion_hip.h"
-#include "clip_tower.h"
+#include "clip_text_model.h"
 #include "f32_tile.h"
 
 namespace {
@@ -140,15 +139,6 @@ __global__ __launch_bounds__(256) void clip_pool_kernel(const int64_t* __restric
 }
 
 }  // namespace
-
-struct dfh_clip : dfh::ParamList {
-  dfh_clip_config cfg{};
-  int tok = 0, pos = 0, fw = 0, fb = 0;
-  std::vector<dfh::ClipLayer> layers;
-  dfh::ClipWorkspace workspace(void* base, int batch, int T) const {
-    return dfh::ClipWorkspace(base, (size_t)batch * T, cfg.hidden_size, cfg.intermediate_size, 3 * (size_t)cfg.hidden_size, 0);
-  }
-};
 
 extern "C" {
 

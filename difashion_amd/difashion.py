@@ -38,12 +38,15 @@ class DiFashion(nn.Module):
             raise ValueError("either text_encoder + tokenizer or a prompt_table is needed")
 
     @classmethod
-    def from_pretrained_pipeline(cls, args, logger=None, cate_num: int = 50, device=None, tokenizer=None, prompt_table=None):
+    def from_pretrained_pipeline(cls, args, logger=None, cate_num: int = 50, device=None, tokenizer=None, prompt_table=None,
+                                 text_encoder_dtype=None):
         """What the reference's constructor does (difashion.py:52-120, ``DiFashion(args, logger, cate_num, device)``) on the MI355X classes:
         scheduler / text encoder / VAE / U-Net from the sub-folders of ``args.pretrained_model_name_or_path`` (a Stable-Diffusion snapshot
         directory), the U-Net's ``conv_in`` widened to 8 input channels with the pretrained weights in the first four and zeros behind
         (:82-93), a fresh ``MutualEncoder`` with xavier-normal linears (:95-102), the VAE and the text encoder frozen (:106-107).  The
-        tokenizer is host-side string processing and stays transformers' ``CLIPTokenizer`` (loaded from ``tokenizer/`` when none is passed)."""
+        tokenizer is host-side string processing and stays transformers' ``CLIPTokenizer`` (loaded from ``tokenizer/`` when none is passed).
+        ``text_encoder_dtype`` is handed to ``CLIPTextModel.from_pretrained`` as ``torch_dtype=``: the process's 16-bit storage dtype selects
+        the 16-bit text tower (the arithmetic mode of the reference's fp16 autocast), ``None`` keeps the fp32 tower."""
         from .clip import CLIPTextModel
         from .mutual import MutualEncoder
         from .schedulers import PNDMScheduler
@@ -58,7 +61,8 @@ class DiFashion(nn.Module):
             from transformers import CLIPTokenizer            # host-only; not part of the compute path
             tokenizer = CLIPTokenizer.from_pretrained(root, subfolder="tokenizer", revision=getattr(args, "revision", None))
         info("text encoder <- text_encoder/ (HIP CLIPTextModel)")
-        text = CLIPTextModel.from_pretrained(root, subfolder="text_encoder", revision=getattr(args, "revision", None))
+        text = CLIPTextModel.from_pretrained(root, subfolder="text_encoder", revision=getattr(args, "revision", None),
+                                             torch_dtype=text_encoder_dtype)
         info("VAE <- vae/ (HIP AutoencoderKL)")
         vae = AutoencoderKL.from_pretrained(root, subfolder="vae")
         info("U-Net <- unet/ (HIP UNet2DConditionModel)")

@@ -413,6 +413,52 @@ int dfh_clipvh_encode(dfh_clipv* c, const float* const* master_params, int count
                       int pixel_dtype, int batch, float* last_hidden_state, float* pooler_output, float* image_embeds,
                       float* const* hidden_states, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the CLIP text encoder in the library's 16-bit storage format, opt-in (csrc/clip_text_half.hip): the
+ * `dfh_cliph_*` family works on a dfh_clip context (the `dfh_clip_*` name set above is the fp32 tower's and stays as it is).  What
+ * transformers' torch_dtype= / .half() and the reference's `--mixed_precision fp16` autocast give: 16-bit weights and a 16-bit residual
+ * stream between launches, every accumulation, LayerNorm statistic, softmax and activation in fp32.  The walk: token gather + position
+ * add in fp32, rounded once -> per block LayerNorm, ONE q | k | v launch into [rows][3 hidden], the causal attention kernel (one
+ * workgroup per (sequence, head), head dim 64, at most 128 tokens), out-proj + residual, LayerNorm, fc1 + GELU / quick-GELU in the GEMM
+ * epilogue, fc2 + residual -> final_layer_norm and (text_embeds) text_projection in fp32 arithmetic.  No atomics: a rerun is bit-identical.
+ *   packed copy  : dfh_cliph_packed_bytes(c) bytes, 256-byte aligned, written by dfh_cliph_pack from the fp32 masters and remade by the
+ *                  caller whenever a master changes: per layer q | k | v stacked as one [3 hidden][hidden] matrix, out_proj, fc1, fc2
+ *                  ([N][K] 16-bit, K-contiguous) and the q | k | v biases stacked as one fp32 [3 hidden] vector.  Token / position
+ *                  embeddings, all other biases, the LayerNorm affines and text_projection are read from the fp32 masters in place.
+ *   outputs      : as dfh_clip_encode / dfh_clip_text_embeds, all fp32, each 16-byte aligned; hidden_states are exact upcasts of the
+ *                  16-bit stream, last_hidden_state = final_layer_norm (fp32 arithmetic) of the upcast stream
+ *   workspace    : >= dfh_cliph_workspace_bytes(c, batch, seq_len) (0: refused, see dfh_last_error), 256-byte aligned
+ * Refused by every entry point of the family, dfh_cliph_plan included, before anything is launched (each message names the fp32 tower as
+ * the alternative): a head dim other than 64, hidden / intermediate sizes that are no multiples of 8, a sequence length outside
+ * [1, min(128, max_position_embeddings)].
+ * dfh_cliph_plan is the host function both size queries and the walk are built on (no GPU needed): every GEMM launch's M / N / K /
+ * leading dims (dfh_clipvh_launch; n_split / ld_out2 / out2_region unused) and the byte range of every workspace region. */
+typedef struct dfh_cliph_plan_info {
+  int batch, tokens, hidden, intermediate, heads, head_dim, layers;
+  int rows;                        /* batch * tokens */
+  int attention_lds_bytes;         /* static LDS of one workgroup of the causal attention kernel */
+  int num_launches, num_regions;
+  size_t workspace_bytes, packed_bytes;
+  dfh_clipvh_launch launches[DFH_CLIPVH_MAX_LAUNCHES];   /* qkv, out_proj, fc1, fc2 */
+  dfh_clipvh_region regions[DFH_CLIPVH_MAX_REGIONS];
+} dfh_cliph_plan_info;
+int dfh_cliph_plan(const dfh_clip* c, int batch, int seq_len, dfh_cliph_plan_info* out);   /* host-only work */
+size_t dfh_cliph_packed_bytes(const dfh_clip* c);
+int dfh_cliph_pack(dfh_clip* c, const float* const* master_params, int count, void* packed, void* stream);
+size_t dfh_cliph_workspace_bytes(const dfh_clip* c, int batch, int seq_len);
+/* arguments as dfh_clip_encode, plus the packed copy */
+int dfh_cliph_encode(dfh_clip* c, const float* const* master_params, int count, const void* packed, const int64_t* input_ids,
+                     float* last_hidden_state, float* pooler_output, int eos_token_id, float* hidden_states, void* workspace,
+                     size_t workspace_bytes, int batch, int seq_len, void* stream);
+/* arguments as dfh_clip_text_embeds, plus the packed copy: the eos rows are gathered from the 16-bit stream first, final_layer_norm and
+ * text_projection run in fp32 on those rows only; last_hidden_state (NULL: not formed) and pooler_output have dfh_cliph_encode's bits */
+int dfh_cliph_text_embeds(dfh_clip* c, const float* const* master_params, int count, const void* packed, const float* text_projection,
+                          int projection_dim, const int64_t* input_ids, float* text_embeds, float* pooler_output, float* last_hidden_state,
+                          int eos_token_id, float* hidden_states, void* workspace, size_t workspace_bytes, int batch, int seq_len, void* stream);
+/* The causal attention kernel of the 16-bit text tower on its own (tests, microbenchmarks): O = softmax(mask(Q K^T * scale)) V per
+ * (batch, head), key j > query i masked.  qkv [batch * T][3 * heads * 64] in the storage format (q | k | v, heads contiguous inside
+ * each), out [batch * T][heads * 64] in the storage format, both 16-byte aligned; head_dim must be 64, T in [1, 128]. */
+int dfh_causal_attention(const void* qkv, void* out, int batch, int T, int heads, int head_dim, float scale, void* stream);
+
 /* ------------------------------------------------------------------ CLIP image preprocessing
  * Replaces (arithmetic) open_clip's / transformers' image transform in front of the tower (Evaluation/extract_hist_embs.py:83-100,
  * evaluate_gor.py:193-236): PIL's antialiased 8-bit resize (horizontal pass, then vertical pass, integer arithmetic over 22-bit
