@@ -8,7 +8,8 @@
 // "16-bit" is the storage format of the library this file is compiled into (bf16; fp16 under -DDFH_F16).  The walk runs on the tile GEMM
 // (gemm.hip, planned by gemm_plan.hip) and dfh_layernorm's kernel (norm.hip); the residual stream is 16-bit between launches, every
 // accumulation, LayerNorm statistic, softmax and activation is fp32.  New here:
-//   * cliph_plan(): ONE host function with the geometry of every launch and the workspace carve (C ABI: dfh_cliph_plan);
+//   * cliph_plan(): ONE host function with the geometry of every launch and the workspace carve (C ABI: dfh_cliph_plan), recorded
+//     through clip_tower_half.h, which also holds the per-layer packed copy and the walk over the blocks (shared with the image tower);
 //   * token gather + position add in fp32, rounded once to the 16-bit stream;
 //   * causal self-attention for sequences of at most 128 tokens at head dim 64 on the 16-bit 16x16x32 MFMA: one workgroup per
 //     (sequence, head), the whole score row resident (exact maximum, no online rescaling);
@@ -19,9 +20,7 @@
 #include <cstring>
 
 #include "clip_text_model.h"
-#include "elementwise.h"
-#include "gemm.h"
-#include "norm.h"
+#include "clip_tower_half.h"
 #include "norm_steps.h"
 
 namespace {
@@ -220,35 +219,14 @@ int upcast(const bf16_t* x, float* out, long elems, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------ the plan: geometry of every launch, workspace carve, packed layout
-constexpr size_t ALIGN = 256;
-size_t round_up(size_t n) { return (n + ALIGN - 1) / ALIGN * ALIGN; }
 enum Region { R_ZERO = 0, R_X, R_LN, R_QKV, R_ATT, R_HID, R_PARTIAL, R_X32, R_ROWS, R_POOLED, R_COUNT };
 enum Launch { L_QKV = 0, L_OUT, L_FC1, L_FC2, L_COUNT };
 const char* const kFp32 = "; the fp32 tower (dfh_clip_encode) takes this config";
 
-// one plain-segment linear of the walk as the GEMM launcher takes it (pointers filled in by the walk; null in the plan)
-GemmArgs linear_args(const dfh_clipvh_launch& l) {
-  GemmArgs g;
-  std::memset(&g, 0, sizeof(g));
-  g.nplain = 1; g.p_c[0] = l.K; g.ldw = l.ldw; g.M = l.M; g.N = l.N; g.act = l.act;
-  g.ld_out = l.ld_out; g.ld_res = l.ld_out; g.out_mode = OUT_BF16; g.rows_per_b = l.rows_per_b;
-  return g;
-}
-
-// packed copy, per layer: wqkv [3 D][D], wo [D][D], w1 [I][D], w2 [D][I] (16-bit) and bqkv [3 D] (fp32)
-struct PackedLayout {
-  size_t wqkv, wo, w1, w2, bqkv, per_layer, total;
-  PackedLayout(int D, int I, int L) {
-    wqkv = 0; wo = wqkv + round_up((size_t)3 * D * D * 2); w1 = wo + round_up((size_t)D * D * 2); w2 = w1 + round_up((size_t)I * D * 2);
-    bqkv = w2 + round_up((size_t)D * I * 2); per_layer = bqkv + round_up((size_t)3 * D * 4);
-    total = (size_t)L * per_layer;
-  }
-};
-
+// the packed copy is the layers alone (clip_tower_half.h), layer 0 at its base
 int cliph_plan(const dfh_clip* c, int batch, int seq_len, dfh_cliph_plan_info* p) {
-  DFH_REQUIRE(c && p, "null argument");
-  std::memset(p, 0, sizeof(*p));
-  DFH_REQUIRE(batch > 0 && batch <= 65535, "batch must be in [1, 65535]");
+  dfh::HalfPlanRecorder<dfh_cliph_plan_info> r{p, __func__};
+  if (int rc = r.open(c, batch)) return rc;
   const dfh_clip_config& g = c->cfg;
   const int D = g.hidden_size, I = g.intermediate_size, H = g.num_attention_heads, d = D / H, T = seq_len;
   DFH_REQUIRE(T >= 1 && T <= CA_TMAX && T <= g.max_position_embeddings,
@@ -259,50 +237,27 @@ int cliph_plan(const dfh_clip* c, int batch, int seq_len, dfh_cliph_plan_info* p
                                             std::to_string(D) + " / " + std::to_string(I) + kFp32);
   DFH_REQUIRE(d == CA_D, "the 16-bit tower's causal attention kernel is built for head dim 64 (CLIP-L/14, OpenCLIP-H/14, B/32): head dim " +
                              std::to_string(d) + " is not built" + kFp32);
-  DFH_REQUIRE((double)batch * T * (3.0 * D > I ? 3.0 * D : I) < 2.0e9, "batch x tokens x width beyond 32-bit element offsets");
+  if (int rc = r.offsets_fit(batch, T, D, I)) return rc;
   const int M = batch * T;
-  p->batch = batch; p->tokens = T; p->hidden = D; p->intermediate = I; p->heads = H; p->head_dim = d; p->layers = g.num_hidden_layers;
-  p->rows = M; p->attention_lds_bytes = CA_LDS_BYTES;
-  const int gact = g.hidden_act == dfh::CLIP_ACT_GELU ? ACT_GELU : ACT_QUICK_GELU;
-  auto launch = [&](int id, const char* name, int N, int K_, int act, int resid, int a_reg, int out_reg) {
-    dfh_clipvh_launch& l = p->launches[id];
-    std::strncpy(l.name, name, sizeof(l.name) - 1);
-    l.M = M; l.N = N; l.K = K_; l.lda = K_; l.ldw = K_; l.ld_out = N; l.rows_per_b = M; l.act = act; l.resid = resid;
-    l.per_layer = 1; l.a_region = a_reg; l.out_region = out_reg; l.out2_region = -1;
-  };
-  launch(L_QKV, "qkv", 3 * D, D, ACT_NONE, 0, R_LN, R_QKV);
-  launch(L_OUT, "out_proj", D, D, ACT_NONE, 1, R_ATT, R_X);
-  launch(L_FC1, "fc1", I, D, gact, 0, R_LN, R_HID);
-  launch(L_FC2, "fc2", D, I, ACT_NONE, 1, R_HID, R_X);
-  p->num_launches = L_COUNT;
-  // split-K slabs of the launches that follow the heuristics (fc1's activation epilogue is single-pass by construction)
-  size_t partial = 0;
-  for (int id : {(int)L_QKV, (int)L_OUT, (int)L_FC2}) {
-    GemmArgs a = linear_args(p->launches[id]);
-    if (p->launches[id].resid) a.resid = (const bf16_t*)p;           // presence only
-    const size_t f = dfh::gemm_partial_floats(a);
-    partial = f > partial ? f : partial;
-  }
-  size_t off = 0;
-  auto region = [&](int id, const char* name, size_t bytes) {
-    dfh_clipvh_region& r = p->regions[id];
-    std::strncpy(r.name, name, sizeof(r.name) - 1);
-    r.offset = off; r.bytes = bytes;
-    off += round_up(bytes);
-  };
-  region(R_ZERO, "zero", 256);
-  region(R_X, "x", (size_t)M * D * 2);
-  region(R_LN, "ln", (size_t)M * D * 2);
-  region(R_QKV, "qkv", (size_t)M * 3 * D * 2);
-  region(R_ATT, "attention", (size_t)M * D * 2);
-  region(R_HID, "mlp_hidden", (size_t)M * I * 2);
-  region(R_PARTIAL, "splitk_partial", partial * sizeof(float));
-  region(R_X32, "x_fp32", (size_t)M * D * sizeof(float));
-  region(R_ROWS, "eos_rows", (size_t)batch * D * sizeof(float));
-  region(R_POOLED, "pooled", (size_t)batch * D * sizeof(float));
-  p->num_regions = R_COUNT;
-  p->workspace_bytes = off;                                           // the caller hands in a 256-byte aligned block
-  p->packed_bytes = PackedLayout(D, I, g.num_hidden_layers).total;
+  r.scalars(batch, T, D, I, H, g.num_hidden_layers);
+  p->attention_lds_bytes = CA_LDS_BYTES;
+  r.launch(L_QKV, "qkv", M, 3 * D, D, 3 * D, ACT_NONE, 0, 1, R_LN, R_QKV);
+  r.launch(L_OUT, "out_proj", M, D, D, D, ACT_NONE, 1, 1, R_ATT, R_X);
+  r.launch(L_FC1, "fc1", M, I, D, I, dfh::half_act(g.hidden_act), 0, 1, R_LN, R_HID);
+  r.launch(L_FC2, "fc2", M, D, I, D, ACT_NONE, 1, 1, R_HID, R_X);
+  // fc1's activation epilogue is single-pass by construction
+  const size_t partial = r.partial_floats({L_QKV, L_OUT, L_FC2});
+  r.region(R_ZERO, "zero", 256);
+  r.region(R_X, "x", (size_t)M * D * 2);
+  r.region(R_LN, "ln", (size_t)M * D * 2);
+  r.region(R_QKV, "qkv", (size_t)M * 3 * D * 2);
+  r.region(R_ATT, "attention", (size_t)M * D * 2);
+  r.region(R_HID, "mlp_hidden", (size_t)M * I * 2);
+  r.region(R_PARTIAL, "splitk_partial", partial * sizeof(float));
+  r.region(R_X32, "x_fp32", (size_t)M * D * sizeof(float));
+  r.region(R_ROWS, "eos_rows", (size_t)batch * D * sizeof(float));
+  r.region(R_POOLED, "pooled", (size_t)batch * D * sizeof(float));
+  p->packed_bytes = (size_t)g.num_hidden_layers * dfh::HalfLayerPack(D, I).per_layer;
   return 0;
 }
 
@@ -312,32 +267,15 @@ int cliph_walk(dfh_clip* c, const float* const* master_params, int count, const 
                void* workspace, size_t workspace_bytes, int batch, int seq_len, hipStream_t s, dfh_cliph_plan_info& p) {
   if (int rc = dfh::require_params(*c, master_params, count, "dfh_clip")) return rc;
   if (int rc = cliph_plan(c, batch, seq_len, &p)) return rc;
-  DFH_REQUIRE(workspace_bytes >= p.workspace_bytes, "workspace smaller than dfh_cliph_workspace_bytes");
-  DFH_REQUIRE((((uintptr_t)workspace | (uintptr_t)packed) & 255) == 0, "workspace / packed copy must be 256-byte aligned");
+  const dfh::HalfWalk<dfh_cliph_plan_info> w{(unsigned char*)workspace, (const unsigned char*)packed, p, s, R_ZERO, R_PARTIAL};
+  if (int rc = w.check_buffers(__func__, "dfh_cliph_workspace_bytes", workspace_bytes)) return rc;
   DFH_REQUIRE(((uintptr_t)input_ids & 7) == 0, "input_ids must be 8-byte aligned");
   DFH_REQUIRE(((uintptr_t)hidden_states & 15) == 0, "hidden_states must be 16-byte aligned");
-  const int T = p.tokens, D = p.hidden, I = p.intermediate, H = p.heads, M = p.rows;
-  const float eps = c->cfg.layer_norm_eps, scale = 1.0f / sqrtf((float)p.head_dim);
+  const int T = p.tokens, D = p.hidden, H = p.heads, M = p.rows;
+  const float scale = 1.0f / sqrtf((float)p.head_dim);
   const float* const* P = master_params;
-  unsigned char* ws = (unsigned char*)workspace;
-  auto reg = [&](int id) { return ws + p.regions[id].offset; };
-  const bf16_t* zero = (const bf16_t*)reg(R_ZERO);
-  bf16_t* x = (bf16_t*)reg(R_X);
-  bf16_t* ln = (bf16_t*)reg(R_LN);
-  const PackedLayout lay(D, I, p.layers);
-  const unsigned char* pk = (const unsigned char*)packed;
-  if (hipMemsetAsync(reg(R_ZERO), 0, 256, s) != hipSuccess) { dfh::set_error("dfh_cliph_encode: memset failed"); return -2; }
-
-  // one GEMM launch of the plan: A rows and the output are regions of the workspace, W a matrix of the packed copy
-  auto linear = [&](int id, const void* W, const float* bias) {
-    const dfh_clipvh_launch& l = p.launches[id];
-    GemmArgs a = linear_args(l);
-    a.p_src[0] = (const bf16_t*)reg(l.a_region); a.W = (const bf16_t*)W; a.bias = bias; a.zero = zero;
-    a.out = reg(l.out_region);
-    if (l.resid) a.resid = (const bf16_t*)reg(l.out_region);
-    a.partial = (float*)reg(R_PARTIAL);
-    return dfh::gemm_launch(a, s, 0, gemm_act_is_xact(l.act) ? 1 : 0);    // the activation epilogues are single-pass launches
-  };
+  bf16_t* x = (bf16_t*)w.reg(R_X);
+  if (int rc = w.clear_zero_page("dfh_cliph_encode")) return rc;
   auto tap = [&](int l) { return hidden_states ? upcast(x, hidden_states + (size_t)l * M * D, (long)M * D, s) : 0; };
 
   {
@@ -349,19 +287,10 @@ int cliph_walk(dfh_clip* c, const float* const* master_params, int count, const 
     if (int rc = dfh::check_launch("cliph_embed_kernel")) return rc;
   }
   if (int rc = tap(0)) return rc;
-  for (size_t l = 0; l < c->layers.size(); ++l) {
-    const dfh::ClipLayer& L = c->layers[l];
-    const unsigned char* lb = pk + l * lay.per_layer;
-    if (int rc = dfh::layernorm_launch(x, P[L.ln1w], P[L.ln1b], ln, M, D, eps, s)) return rc;
-    if (int rc = linear(L_QKV, lb + lay.wqkv, (const float*)(lb + lay.bqkv))) return rc;
-    if (int rc = causal_attention_launch((const bf16_t*)reg(R_QKV), (bf16_t*)reg(R_ATT), batch, T, H, 3 * D, D, 2 * D, D, scale, s)) return rc;
-    if (int rc = linear(L_OUT, lb + lay.wo, P[L.ob])) return rc;                    // x += out_proj(attention)
-    if (int rc = dfh::layernorm_launch(x, P[L.ln2w], P[L.ln2b], ln, M, D, eps, s)) return rc;
-    if (int rc = linear(L_FC1, lb + lay.w1, P[L.f1b])) return rc;
-    if (int rc = linear(L_FC2, lb + lay.w2, P[L.f2b])) return rc;                   // x += fc2(act(fc1(.)))
-    if (int rc = tap((int)l + 1)) return rc;
-  }
-  return 0;
+  auto attention = [&]() {
+    return causal_attention_launch((const bf16_t*)w.reg(R_QKV), (bf16_t*)w.reg(R_ATT), batch, T, H, 3 * D, D, 2 * D, D, scale, s);
+  };
+  return dfh::half_blocks(w, L_QKV, P, c->layers, dfh::HalfLayerPack(D, p.intermediate), w.pk, c->cfg.layer_norm_eps, attention, tap);
 }
 
 // final_layer_norm over all rows in fp32 arithmetic on the upcast stream -> last_hidden_state
@@ -395,26 +324,7 @@ int dfh_cliph_pack(dfh_clip* c, const float* const* master_params, int count, vo
   DFH_REQUIRE(((uintptr_t)packed & 255) == 0, "the packed copy must be 256-byte aligned");
   dfh_cliph_plan_info p;
   if (int rc = cliph_plan(c, 1, 1, &p)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  const int D = p.hidden, I = p.intermediate;
-  const PackedLayout lay(D, I, p.layers);
-  unsigned char* base = (unsigned char*)packed;
-  const float* const* P = master_params;
-  for (size_t l = 0; l < c->layers.size(); ++l) {
-    const dfh::ClipLayer& L = c->layers[l];
-    unsigned char* lb = base + l * lay.per_layer;
-    bf16_t* wqkv = (bf16_t*)(lb + lay.wqkv);
-    float* bqkv = (float*)(lb + lay.bqkv);
-    const int w3[3] = {L.qw, L.kw, L.vw}, b3[3] = {L.qb, L.kb, L.vb};
-    for (int j = 0; j < 3; ++j) {
-      if (int rc = dfh::pack_matrix_launch(P[w3[j]], wqkv, D, D, D, j * D, 0, 0, s)) return rc;
-      if (int rc = dfh::pack_vector_launch(P[b3[j]], bqkv, D, j * D, 0, 0, s)) return rc;
-    }
-    if (int rc = dfh::pack_matrix_launch(P[L.ow], (bf16_t*)(lb + lay.wo), D, D, D, 0, 0, 0, s)) return rc;
-    if (int rc = dfh::pack_matrix_launch(P[L.f1w], (bf16_t*)(lb + lay.w1), I, D, D, 0, 0, 0, s)) return rc;
-    if (int rc = dfh::pack_matrix_launch(P[L.f2w], (bf16_t*)(lb + lay.w2), D, I, I, 0, 0, 0, s)) return rc;
-  }
-  return 0;
+  return dfh::pack_encoder_layers(master_params, c->layers, dfh::HalfLayerPack(p.hidden, p.intermediate), (unsigned char*)packed, (hipStream_t)stream);
 }
 
 int dfh_cliph_encode(dfh_clip* c, const float* const* master_params, int count, const void* packed, const int64_t* input_ids,

@@ -8,7 +8,8 @@
 // runs on the project's 16-bit kernels: the tile GEMM (gemm.hip, planned by gemm_plan.hip), dfh_layernorm's kernel (norm.hip) and
 // the flash attention kernels (attention.hip / attention_x32.hip).  The residual stream is 16-bit between launches, as in the real
 // half-precision classes; every accumulation, LayerNorm statistic, softmax and activation is fp32.  New here:
-//   * half_plan(): ONE host function with the geometry of every launch and the workspace carve (C ABI: dfh_clipvh_plan);
+//   * half_plan(): ONE host function with the geometry of every launch and the workspace carve (C ABI: dfh_clipvh_plan), recorded
+//     through clip_tower_half.h, which also holds the per-layer packed copy and the walk over the blocks (shared with the text tower);
 //   * im2col into 16-bit rows whose K is zero-padded to a multiple of 8 (16-byte rows for the GEMM's staging);
 //   * class token + position embeddings + pre_layrnorm in one launch (16-bit patch rows in, fp32 arithmetic, 16-bit out);
 //   * the fp32 upcasts that leave as last_hidden_state / hidden_states, and the class rows for the fp32 tail.
@@ -31,11 +32,9 @@
 #include <cstring>
 
 #include "attention.h"
+#include "clip_tower_half.h"
 #include "clip_vision_model.h"
-#include "elementwise.h"
-#include "gemm.h"
 #include "gemm_plan.h"
-#include "norm.h"
 #include "norm_steps.h"
 #include "walk_knobs.h"
 
@@ -140,70 +139,45 @@ int upcast(const bf16_t* x, float* out, long rows, int D, long row_stride, hipSt
 }
 
 // ------------------------------------------------------------------ the plan: geometry of every launch, workspace carve, packed layout
-constexpr size_t ALIGN = 256;
-size_t round_up(size_t n) { return (n + ALIGN - 1) / ALIGN * ALIGN; }
 enum Region { R_ZERO = 0, R_COL, R_PATCH, R_X, R_LN, R_QK, R_VT, R_ATT, R_HID, R_PARTIAL, R_CLS, R_POOLED, R_COUNT };
 enum Launch { L_PATCH = 0, L_QKV, L_OUT, L_FC1, L_FC2, L_COUNT };
 
 bool head_dim_supported(int d) { return d == 32 || d == 40 || d == 64 || d == 80 || d == 128 || d == 160; }
 
-// one plain-segment linear of the walk as the GEMM launcher takes it (pointers filled in by the walk; null in the plan)
-GemmArgs linear_args(const dfh_clipvh_launch& l) {
-  GemmArgs g;
-  std::memset(&g, 0, sizeof(g));
-  g.nplain = 1; g.p_c[0] = l.K; g.ldw = l.ldw; g.M = l.M; g.N = l.N; g.act = l.act;
-  g.ld_out = l.ld_out; g.ld_res = l.ld_out; g.out_mode = OUT_BF16; g.rows_per_b = l.rows_per_b;
-  g.n_split = l.n_split; g.ld_out2 = l.ld_out2;
-  return g;
-}
-
-// packed copy: patch [D][Kpad]; per layer wqkv [3 D][D], wo [D][D], w1 [I][D], w2 [D][I] (16-bit) and bqkv [3 D] (fp32)
-struct PackedLayout {
-  size_t patch, layer0, wqkv, wo, w1, w2, bqkv, per_layer, total;
-  PackedLayout(int D, int I, int Kpad, int L) {
-    patch = 0; layer0 = round_up((size_t)D * Kpad * 2);
-    wqkv = 0; wo = wqkv + round_up((size_t)3 * D * D * 2); w1 = wo + round_up((size_t)D * D * 2); w2 = w1 + round_up((size_t)I * D * 2);
-    bqkv = w2 + round_up((size_t)D * I * 2); per_layer = bqkv + round_up((size_t)3 * D * 4);
-    total = layer0 + (size_t)L * per_layer;
-  }
+// packed copy: patch [D][Kpad] (16-bit), then the layers (clip_tower_half.h)
+struct PackedLayout : dfh::HalfLayerPack {
+  size_t patch = 0, layer0, total;
+  PackedLayout(int D, int I, int Kpad, int L) : dfh::HalfLayerPack(D, I), layer0(dfh::half_round_up((size_t)D * Kpad * 2)) { total = layer0 + L * per_layer; }
 };
 
 int half_plan(const dfh_clipv* c, int batch, dfh_clipvh_plan_info* p) {
-  DFH_REQUIRE(c && p, "null argument");
-  std::memset(p, 0, sizeof(*p));
-  DFH_REQUIRE(batch > 0 && batch <= 65535, "batch must be in [1, 65535]");
+  dfh::HalfPlanRecorder<dfh_clipvh_plan_info> r{p, __func__};
+  if (int rc = r.open(c, batch)) return rc;
   const dfh_clipv_config& g = c->cfg;
   const int D = g.hidden_size, I = g.intermediate_size, H = g.num_attention_heads, d = D / H, T = c->T, K = c->Kp;
   DFH_REQUIRE(head_dim_supported(d), "the 16-bit tower runs on dfh_attention's kernels: head dim " + std::to_string(d) +
                                          " is not built (supported: 32, 40, 64, 80, 128, 160); the fp32 tower takes any multiple of 4 up to 128");
   DFH_REQUIRE(D % 8 == 0 && I % 8 == 0 && D <= 2048, "the 16-bit tower needs hidden / intermediate sizes that are multiples of 8, hidden <= 2048");
-  DFH_REQUIRE((double)batch * T * (3.0 * D > I ? 3.0 * D : I) < 2.0e9, "batch x tokens x width beyond 32-bit element offsets");
+  if (int rc = r.offsets_fit(batch, T, D, I)) return rc;
   const int Kpad = (K + 7) / 8 * 8, M = batch * T, Mp = batch * (T - 1), ldvt = (T + 7) / 8 * 8;
-  p->batch = batch; p->tokens = T; p->hidden = D; p->intermediate = I; p->heads = H; p->head_dim = d; p->layers = g.num_hidden_layers;
-  p->projection_dim = g.projection_dim; p->patch_k = K; p->patch_k_padded = Kpad; p->rows = M; p->patch_rows = Mp; p->ldvt = ldvt;
+  r.scalars(batch, T, D, I, H, g.num_hidden_layers);
+  p->projection_dim = g.projection_dim; p->patch_k = K; p->patch_k_padded = Kpad; p->patch_rows = Mp; p->ldvt = ldvt;
   {
     AttnArgs a; std::memset(&a, 0, sizeof(a));
     a.B = batch; a.H = H; a.D = d; a.Nq = T; a.Nk = T;
     p->attention_x32 = dfh::WalkKnobs::get().attn_x32 && dfh::attention_x32_eligible(a) ? 1 : 0;
   }
-  const int gact = g.hidden_act == dfh::CLIP_ACT_GELU ? ACT_GELU : ACT_QUICK_GELU;
-  auto launch = [&](int id, const char* name, int M_, int N, int K_, int ld_out, int act, int resid, int per_layer, int a_reg, int out_reg) {
-    dfh_clipvh_launch& l = p->launches[id];
-    std::strncpy(l.name, name, sizeof(l.name) - 1);
-    l.M = M_; l.N = N; l.K = K_; l.lda = K_; l.ldw = K_; l.ld_out = ld_out; l.rows_per_b = M_; l.act = act; l.resid = resid;
-    l.per_layer = per_layer; l.a_region = a_reg; l.out_region = out_reg; l.out2_region = -1;
-  };
-  launch(L_PATCH, "patch", Mp, D, Kpad, D, ACT_NONE, 0, 0, R_COL, R_PATCH);
-  launch(L_QKV, "qkv", M, 3 * D, D, 2 * D, ACT_NONE, 0, 1, R_LN, R_QK);
-  p->launches[L_QKV].n_split = 2 * D; p->launches[L_QKV].ld_out2 = ldvt; p->launches[L_QKV].rows_per_b = T; p->launches[L_QKV].out2_region = R_VT;
-  launch(L_OUT, "out_proj", M, D, D, D, ACT_NONE, 1, 1, R_ATT, R_X);
-  launch(L_FC1, "fc1", M, I, D, I, gact, 0, 1, R_LN, R_HID);
-  launch(L_FC2, "fc2", M, D, I, D, ACT_NONE, 1, 1, R_HID, R_X);
-  p->num_launches = L_COUNT;
+  r.launch(L_PATCH, "patch", Mp, D, Kpad, D, ACT_NONE, 0, 0, R_COL, R_PATCH);
+  // q | k row-major; V leaves transposed per image through the GEMM's second destination
+  dfh_clipvh_launch& qkv = r.launch(L_QKV, "qkv", M, 3 * D, D, 2 * D, ACT_NONE, 0, 1, R_LN, R_QK);
+  qkv.n_split = 2 * D; qkv.ld_out2 = ldvt; qkv.rows_per_b = T; qkv.out2_region = R_VT;
+  r.launch(L_OUT, "out_proj", M, D, D, D, ACT_NONE, 1, 1, R_ATT, R_X);
+  r.launch(L_FC1, "fc1", M, I, D, I, dfh::half_act(g.hidden_act), 0, 1, R_LN, R_HID);
+  r.launch(L_FC2, "fc2", M, D, I, D, ACT_NONE, 1, 1, R_HID, R_X);
   {
     // the q | k | v launch writes V^T through the GEMM's second destination, which begins at a column-tile edge: 2 D must be a whole
     // number of the column tiles that launch gets (160 when 3 D is a multiple of 160 or no multiple of 128, else 128)
-    GemmArgs a = linear_args(p->launches[L_QKV]);
+    GemmArgs a = dfh::half_linear_args(p->launches[L_QKV]);
     int tile = 0;
     dfh::gemm_pick_split(a, &tile);
     const int bn = dfh::kGemmTiles[tile].bn;
@@ -211,35 +185,20 @@ int half_plan(const dfh_clipv* c, int batch, dfh_clipvh_plan_info* p) {
                                        " and writes V^T from column 2 x hidden on: 2 x hidden must be a multiple of " + std::to_string(bn) +
                                        " (hidden a multiple of 64 when 3 x hidden is a multiple of 128, else of 80); the fp32 tower takes this config");
   }
-  // split-K slabs of the launches that follow the heuristics (the q | k | v launch and fc1 are single-pass by construction)
-  size_t partial = 0;
-  for (int id : {(int)L_PATCH, (int)L_OUT, (int)L_FC2}) {
-    GemmArgs a = linear_args(p->launches[id]);
-    if (p->launches[id].resid) a.resid = (const bf16_t*)p;           // presence only
-    const size_t f = dfh::gemm_partial_floats(a);
-    partial = f > partial ? f : partial;
-  }
-  size_t off = 0;
-  auto region = [&](int id, const char* name, size_t bytes) {
-    dfh_clipvh_region& r = p->regions[id];
-    std::strncpy(r.name, name, sizeof(r.name) - 1);
-    r.offset = off; r.bytes = bytes;
-    off += round_up(bytes);
-  };
-  region(R_ZERO, "zero", 256);
-  region(R_COL, "im2col", (size_t)Mp * Kpad * 2);
-  region(R_PATCH, "patch", (size_t)Mp * D * 2);
-  region(R_X, "x", (size_t)M * D * 2);
-  region(R_LN, "ln", (size_t)M * D * 2);
-  region(R_QK, "qk", (size_t)M * 2 * D * 2);
-  region(R_VT, "vt", (size_t)batch * D * ldvt * 2);
-  region(R_ATT, "attention", (size_t)M * D * 2);
-  region(R_HID, "mlp_hidden", (size_t)M * I * 2);
-  region(R_PARTIAL, "splitk_partial", partial * sizeof(float));
-  region(R_CLS, "class_rows", (size_t)batch * D * sizeof(float));
-  region(R_POOLED, "pooled", (size_t)batch * D * sizeof(float));
-  p->num_regions = R_COUNT;
-  p->workspace_bytes = off;                                           // the caller hands in a 256-byte aligned block
+  // the q | k | v launch and fc1 are single-pass by construction
+  const size_t partial = r.partial_floats({L_PATCH, L_OUT, L_FC2});
+  r.region(R_ZERO, "zero", 256);
+  r.region(R_COL, "im2col", (size_t)Mp * Kpad * 2);
+  r.region(R_PATCH, "patch", (size_t)Mp * D * 2);
+  r.region(R_X, "x", (size_t)M * D * 2);
+  r.region(R_LN, "ln", (size_t)M * D * 2);
+  r.region(R_QK, "qk", (size_t)M * 2 * D * 2);
+  r.region(R_VT, "vt", (size_t)batch * D * ldvt * 2);
+  r.region(R_ATT, "attention", (size_t)M * D * 2);
+  r.region(R_HID, "mlp_hidden", (size_t)M * I * 2);
+  r.region(R_PARTIAL, "splitk_partial", partial * sizeof(float));
+  r.region(R_CLS, "class_rows", (size_t)batch * D * sizeof(float));
+  r.region(R_POOLED, "pooled", (size_t)batch * D * sizeof(float));
   p->packed_bytes = PackedLayout(D, I, Kpad, g.num_hidden_layers).total;
   return 0;
 }
@@ -267,28 +226,13 @@ int dfh_clipvh_pack(dfh_clipv* c, const float* const* master_params, int count, 
   dfh_clipvh_plan_info p;
   if (int rc = half_plan(c, 1, &p)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int D = p.hidden, I = p.intermediate, K = p.patch_k, Kpad = p.patch_k_padded;
-  const PackedLayout lay(D, I, Kpad, p.layers);
+  const int D = p.hidden, K = p.patch_k, Kpad = p.patch_k_padded;
+  const PackedLayout lay(D, p.intermediate, Kpad, p.layers);
   unsigned char* base = (unsigned char*)packed;
-  const float* const* P = master_params;
   // the K padding of the patch weight must read as zeros
   if (hipMemsetAsync(base + lay.patch, 0, (size_t)D * Kpad * 2, s) != hipSuccess) { dfh::set_error("dfh_clipvh_pack: memset failed"); return -2; }
-  if (int rc = dfh::pack_matrix_launch(P[c->patch], (bf16_t*)(base + lay.patch), D, K, Kpad, 0, 0, 0, s)) return rc;
-  for (size_t l = 0; l < c->layers.size(); ++l) {
-    const dfh::ClipLayer& L = c->layers[l];
-    unsigned char* lb = base + lay.layer0 + l * lay.per_layer;
-    bf16_t* wqkv = (bf16_t*)(lb + lay.wqkv);
-    float* bqkv = (float*)(lb + lay.bqkv);
-    const int w3[3] = {L.qw, L.kw, L.vw}, b3[3] = {L.qb, L.kb, L.vb};
-    for (int j = 0; j < 3; ++j) {
-      if (int rc = dfh::pack_matrix_launch(P[w3[j]], wqkv, D, D, D, j * D, 0, 0, s)) return rc;
-      if (int rc = dfh::pack_vector_launch(P[b3[j]], bqkv, D, j * D, 0, 0, s)) return rc;
-    }
-    if (int rc = dfh::pack_matrix_launch(P[L.ow], (bf16_t*)(lb + lay.wo), D, D, D, 0, 0, 0, s)) return rc;
-    if (int rc = dfh::pack_matrix_launch(P[L.f1w], (bf16_t*)(lb + lay.w1), I, D, D, 0, 0, 0, s)) return rc;
-    if (int rc = dfh::pack_matrix_launch(P[L.f2w], (bf16_t*)(lb + lay.w2), D, I, I, 0, 0, 0, s)) return rc;
-  }
-  return 0;
+  if (int rc = dfh::pack_matrix_launch(master_params[c->patch], (bf16_t*)(base + lay.patch), D, K, Kpad, 0, 0, 0, s)) return rc;
+  return dfh::pack_encoder_layers(master_params, c->layers, lay, base + lay.layer0, s);
 }
 
 int dfh_clipvh_encode(dfh_clipv* c, const float* const* master_params, int count, const void* packed, const void* pixel_values,
@@ -299,45 +243,23 @@ int dfh_clipvh_encode(dfh_clipv* c, const float* const* master_params, int count
   DFH_REQUIRE(pixel_dtype == 0 || pixel_dtype == 1, "pixel_dtype: 0 = fp32, 1 = the library's 16-bit storage format");
   dfh_clipvh_plan_info p;
   if (int rc = half_plan(c, batch, &p)) return rc;
-  DFH_REQUIRE(workspace_bytes >= p.workspace_bytes, "workspace smaller than dfh_clipvh_workspace_bytes");
-  DFH_REQUIRE((((uintptr_t)workspace | (uintptr_t)packed) & 255) == 0, "workspace / packed copy must be 256-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const dfh::HalfWalk<dfh_clipvh_plan_info> w{(unsigned char*)workspace, (const unsigned char*)packed, p, s, R_ZERO, R_PARTIAL};
+  if (int rc = w.check_buffers(__func__, "dfh_clipvh_workspace_bytes", workspace_bytes)) return rc;
   // im2col reads the pixels one element at a time; the outputs (and the taps) are written as float4; require_params has checked the masters
   DFH_REQUIRE(((uintptr_t)pixel_values & (pixel_dtype ? 1 : 3)) == 0, "pixel_values must be aligned to its element size");
   DFH_REQUIRE((((uintptr_t)last_hidden_state | (uintptr_t)pooler_output | (uintptr_t)image_embeds) & 15) == 0, "outputs must be 16-byte aligned");
   if (hidden_states)
     for (int l = 0; l <= p.layers; ++l)
       DFH_REQUIRE(((uintptr_t)hidden_states[l] & 15) == 0, "hidden_states[" + std::to_string(l) + "] must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
   const dfh_clipv_config& g = c->cfg;
-  const int T = p.tokens, D = p.hidden, I = p.intermediate, H = p.heads, d = p.head_dim, M = p.rows, Mp = p.patch_rows;
+  const int T = p.tokens, D = p.hidden, H = p.heads, d = p.head_dim, M = p.rows, Mp = p.patch_rows;
   const float eps = g.layer_norm_eps, scale = 1.0f / sqrtf((float)d);
   const float* const* P = master_params;
-  unsigned char* ws = (unsigned char*)workspace;
-  auto reg = [&](int id) { return ws + p.regions[id].offset; };
-  const bf16_t* zero = (const bf16_t*)reg(R_ZERO);
-  bf16_t* x = (bf16_t*)reg(R_X);
-  bf16_t* ln = (bf16_t*)reg(R_LN);
-  const PackedLayout lay(D, I, p.patch_k_padded, p.layers);
-  const unsigned char* pk = (const unsigned char*)packed;
-  if (hipMemsetAsync(reg(R_ZERO), 0, 256, s) != hipSuccess) { dfh::set_error("dfh_clipvh_encode: memset failed"); return -2; }
-
-  // one GEMM launch of the plan: A rows and the output are regions of the workspace, W a matrix of the packed copy
-  auto linear = [&](int id, const void* W, const float* bias) {
-    const dfh_clipvh_launch& l = p.launches[id];
-    GemmArgs a = linear_args(l);
-    a.p_src[0] = (const bf16_t*)reg(l.a_region); a.W = (const bf16_t*)W; a.bias = bias; a.zero = zero;
-    a.out = reg(l.out_region);
-    if (l.resid) a.resid = (const bf16_t*)reg(l.out_region);
-    a.partial = (float*)reg(R_PARTIAL);
-    if (l.out2_region >= 0) a.out2 = reg(l.out2_region);
-    // the second destination and the activation epilogues are single-pass launches: no K split
-    const int force_split = (l.out2_region >= 0 || gemm_act_is_xact(l.act)) ? 1 : 0;
-    return dfh::gemm_launch(a, s, 0, force_split);
-  };
-  auto tap = [&](int l) {
-    float* dst = hidden_states ? hidden_states[l] : nullptr;
-    return dst ? upcast(x, dst, M, D, D, s) : 0;
-  };
+  bf16_t* x = (bf16_t*)w.reg(R_X);
+  const PackedLayout lay(D, p.intermediate, p.patch_k_padded, p.layers);
+  if (int rc = w.clear_zero_page(__func__)) return rc;
+  auto tap = [&](int l) { return hidden_states && hidden_states[l] ? upcast(x, hidden_states[l], M, D, D, s) : 0; };
 
   // embeddings: im2col -> patch GEMM -> class token + positions + pre_layrnorm
   {
@@ -346,44 +268,35 @@ int dfh_clipvh_encode(dfh_clipv* c, const float* const* master_params, int count
     {
       dfh::ProfScope ps(dfh::PC_OTHER, 0.0, (pixel_dtype ? 2.0 : 4.0) * Mp * p.patch_k + 2.0 * Mp * p.patch_k_padded, s);
       const dim3 grid((unsigned)((chunks + 255) / 256));
-      if (pixel_dtype) hipLaunchKernelGGL(clipvh_im2col_kernel<true>, grid, dim3(256), 0, s, pixel_values, (bf16_t*)reg(R_COL), g.num_channels,
+      if (pixel_dtype) hipLaunchKernelGGL(clipvh_im2col_kernel<true>, grid, dim3(256), 0, s, pixel_values, (bf16_t*)w.reg(R_COL), g.num_channels,
                                           g.image_size, g.patch_size, c->grid, p.patch_k, p.patch_k_padded, chunks);
-      else hipLaunchKernelGGL(clipvh_im2col_kernel<false>, grid, dim3(256), 0, s, pixel_values, (bf16_t*)reg(R_COL), g.num_channels,
+      else hipLaunchKernelGGL(clipvh_im2col_kernel<false>, grid, dim3(256), 0, s, pixel_values, (bf16_t*)w.reg(R_COL), g.num_channels,
                               g.image_size, g.patch_size, c->grid, p.patch_k, p.patch_k_padded, chunks);
       if (int rc = dfh::check_launch("clipvh_im2col_kernel")) return rc;
     }
-    if (int rc = linear(L_PATCH, pk + lay.patch, nullptr)) return rc;
+    if (int rc = w.linear(L_PATCH, w.pk + lay.patch, nullptr)) return rc;
     {
       dfh::ProfScope ps(dfh::PC_LNORM, 8.0 * M * D, 12.0 * M * D, s);
-      hipLaunchKernelGGL(clipvh_embed_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, s, (const bf16_t*)reg(R_PATCH), P[c->cls], P[c->pos],
+      hipLaunchKernelGGL(clipvh_embed_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, s, (const bf16_t*)w.reg(R_PATCH), P[c->cls], P[c->pos],
                          P[c->prew], P[c->preb], x, M, T, D, eps);
       if (int rc = dfh::check_launch("clipvh_embed_ln_kernel")) return rc;
     }
   }
   if (int rc = tap(0)) return rc;
-  for (size_t l = 0; l < c->layers.size(); ++l) {
-    const dfh::ClipLayer& L = c->layers[l];
-    const unsigned char* lb = pk + lay.layer0 + l * lay.per_layer;
-    if (int rc = dfh::layernorm_launch(x, P[L.ln1w], P[L.ln1b], ln, M, D, eps, s)) return rc;
-    if (int rc = linear(L_QKV, lb + lay.wqkv, (const float*)(lb + lay.bqkv))) return rc;
-    {
-      AttnArgs a; std::memset(&a, 0, sizeof(a));
-      const bf16_t* qk = (const bf16_t*)reg(R_QK);
-      a.Q = qk; a.ldq = 2 * D; a.K = qk + D; a.ldk = 2 * D; a.Vt = (const bf16_t*)reg(R_VT); a.ldvt = p.ldvt;
-      a.O = (bf16_t*)reg(R_ATT); a.ldo = D; a.B = batch; a.H = H; a.D = d; a.Nq = T; a.Nk = T; a.scale = scale;
-      if (int rc = dfh::attention_launch(a, s)) return rc;
-    }
-    if (int rc = linear(L_OUT, lb + lay.wo, P[L.ob])) return rc;                    // x += out_proj(attention)
-    if (int rc = dfh::layernorm_launch(x, P[L.ln2w], P[L.ln2b], ln, M, D, eps, s)) return rc;
-    if (int rc = linear(L_FC1, lb + lay.w1, P[L.f1b])) return rc;
-    if (int rc = linear(L_FC2, lb + lay.w2, P[L.f2b])) return rc;                   // x += fc2(act(fc1(.)))
-    if (int rc = tap((int)l + 1)) return rc;
-  }
+  // dfh_attention's kernels over q k [M][2 D] | V^T [batch][D][ldvt]
+  auto attention = [&]() {
+    AttnArgs a; std::memset(&a, 0, sizeof(a));
+    const bf16_t* qk = (const bf16_t*)w.reg(R_QK);
+    a.Q = qk; a.ldq = 2 * D; a.K = qk + D; a.ldk = 2 * D; a.Vt = (const bf16_t*)w.reg(R_VT); a.ldvt = p.ldvt;
+    a.O = (bf16_t*)w.reg(R_ATT); a.ldo = D; a.B = batch; a.H = H; a.D = d; a.Nq = T; a.Nk = T; a.scale = scale;
+    return dfh::attention_launch(a, s);
+  };
+  if (int rc = dfh::half_blocks(w, L_QKV, P, c->layers, lay, w.pk + lay.layer0, eps, attention, tap)) return rc;
   if (int rc = upcast(x, last_hidden_state, M, D, D, s)) return rc;
   if (pooler_output || image_embeds) {
     // the tail in fp32 arithmetic on the pooled rows only: the fp32 tower's LayerNorm and linear kernels (clip_kernels.h)
-    float* cls32 = (float*)reg(R_CLS);
-    float* pl = pooler_output ? pooler_output : (float*)reg(R_POOLED);
+    float* cls32 = (float*)w.reg(R_CLS);
+    float* pl = pooler_output ? pooler_output : (float*)w.reg(R_POOLED);
     if (int rc = upcast(x, cls32, batch, D, (long)T * D, s)) return rc;
     {
       dfh::ProfScope ps(dfh::PC_LNORM, 8.0 * batch * D, 8.0 * batch * D, s);

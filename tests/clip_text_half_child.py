@@ -29,28 +29,12 @@ import json
 import numpy as np
 import torch
 
-FACTOR = 3.0
-GUARD = 4096                       # sentinel elements in front of and behind every op-level output
+from tests.helpers_clip_half import FACTOR, GUARD, _bands_untouched, _guarded, u16  # noqa: F401
+
 ATTENTION_T = (1, 16, 17, 20, 64, 77, 128)
 ATTENTION_BH = (2, 2)              # B x H = 4 workgroups
 CAUSAL_SHAPE = (2, 3, 64, 77)
 CAUSAL_T0 = (0, 15, 16, 31, 32, 63, 64, 75)
-
-
-def u16():
-    from difashion_amd import _lib
-    return 2.0 ** -11 if _lib.storage() == "fp16" else 2.0 ** -8
-
-
-def _guarded(shape, dtype, sentinel):
-    """A tensor of ``shape`` inside a flat buffer with GUARD sentinel elements on either side -> (buffer, view)."""
-    n = int(np.prod(shape))
-    buf = torch.full((GUARD + n + GUARD,), sentinel, dtype=dtype, device="cuda")
-    return buf, buf[GUARD:GUARD + n].view(*shape)
-
-
-def _bands_untouched(buf, sentinel):
-    return bool((buf[:GUARD] == sentinel).all() and (buf[-GUARD:] == sentinel).all())
 
 
 def hip_model(cfg, params, proj, dtype, with_projection=True):

@@ -34,27 +34,11 @@ import json
 import numpy as np
 import torch
 
-FACTOR = 3.0
-GUARD = 4096                       # sentinel elements in front of and behind every op-level output
+from tests.helpers_clip_half import FACTOR, GUARD, _bands_untouched, _guarded, u16  # noqa: F401
+
 ATTENTION_CASES = [(2, 3, 64, 197), (2, 3, 80, 257), (2, 2, 64, 50), (1, 2, 80, 129)]      # (B, H, d, Nq = Nk)
 GEMM_ROWS = (50, 257, 771)
 GEMM_NK = (320, 192)               # N: two column tiles of 160; K: three 64-deep k-steps, LEAN
-
-
-def u16():
-    from difashion_amd import _lib
-    return 2.0 ** -11 if _lib.storage() == "fp16" else 2.0 ** -8
-
-
-def _guarded(shape, dtype, sentinel):
-    """A tensor of ``shape`` inside a flat buffer with GUARD sentinel elements on either side -> (buffer, view)."""
-    n = int(np.prod(shape))
-    buf = torch.full((GUARD + n + GUARD,), sentinel, dtype=dtype, device="cuda")
-    return buf, buf[GUARD:GUARD + n].view(*shape)
-
-
-def _bands_untouched(buf, sentinel):
-    return bool((buf[:GUARD] == sentinel).all() and (buf[-GUARD:] == sentinel).all())
 
 
 def hip_model(cfg, params, dtype):

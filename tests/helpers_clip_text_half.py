@@ -22,10 +22,7 @@ import torch
 from oracle import clip_ref
 from tests.helpers_clip import CASES as FP32_CASES
 from tests.helpers_clip import GOLDEN, rel  # noqa: F401
-
-FACTOR = 3.0
-FORMATS = ("bf16", "fp16")
-TORCH_DTYPE = {"bf16": torch.bfloat16, "fp16": torch.float16}
+from tests.helpers_clip_half import FACTOR, FORMATS, TORCH_DTYPE, max_one_minus_cos, yardstick  # noqa: F401
 
 _TINY = dict(vocab_size=1000, hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=2, bos_token_id=998)
 THALF_TINY_77 = clip_ref.CLIPTextConfig(hidden_act="quick_gelu", eos_token_id=2, pad_token_id=999, **_TINY)
@@ -99,14 +96,3 @@ def load_fixture(name: str) -> Dict[str, np.ndarray]:
 
 def output_keys(fx) -> List[str]:
     return ["text_embeds", "pooler_output", "last_hidden_state"] + [f"hidden_{int(t)}" for t in fx["taps"]]
-
-
-def max_one_minus_cos(a: torch.Tensor, b: torch.Tensor) -> float:
-    a, b = a.double(), b.double()
-    return float((1.0 - (a * b).sum(-1) / (a.norm(dim=-1) * b.norm(dim=-1))).max())
-
-
-def yardstick(ys, name: str, fmt: str, key: str) -> float:
-    """The real class's own distance from fp64 in format ``fmt``: relative L2 of output ``key``, or ``key`` = "cos" for the
-    maximum of 1 - cos over the sequences' ``text_embeds``."""
-    return float(ys[f"{name}/{fmt}/{key}"])

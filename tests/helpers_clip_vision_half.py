@@ -15,14 +15,9 @@ import os
 from typing import Dict, List
 
 import numpy as np
-import torch
-
+from tests.helpers_clip_half import FACTOR, FORMATS, TORCH_DTYPE, max_one_minus_cos, yardstick  # noqa: F401
 from tests.helpers_clip_vision import CASES as FP32_CASES
 from tests.helpers_clip_vision import FULL_SIZE_ROWS, GOLDEN, VisionConfig, init_params, pixel_inputs, rel  # noqa: F401
-
-FACTOR = 3.0
-FORMATS = ("bf16", "fp16")
-TORCH_DTYPE = {"bf16": torch.bfloat16, "fp16": torch.float16}
 
 HALF_TINY_D64 = VisionConfig(128, 256, 2, 2, 112, 8, 32, "quick_gelu")        # T = 197, d = 64
 HALF_TINY_D80 = VisionConfig(160, 640, 2, 2, 224, 14, 64, "gelu")             # T = 257, d = 80, patch K = 588
@@ -62,14 +57,3 @@ def kept_rows(T: int) -> List[int]:
 
 def output_keys(fx) -> List[str]:
     return ["image_embeds", "pooler_output", "last_hidden_state"] + [f"hidden_{int(t)}" for t in fx["taps"]]
-
-
-def max_one_minus_cos(a: torch.Tensor, b: torch.Tensor) -> float:
-    a, b = a.double(), b.double()
-    return float((1.0 - (a * b).sum(-1) / (a.norm(dim=-1) * b.norm(dim=-1))).max())
-
-
-def yardstick(ys, name: str, fmt: str, key: str) -> float:
-    """The real class's own distance from fp64 in format ``fmt``: relative L2 of output ``key``, or ``key`` = "cos" for the
-    maximum of 1 - cos over the images' ``image_embeds``."""
-    return float(ys[f"{name}/{fmt}/{key}"])

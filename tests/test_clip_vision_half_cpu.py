@@ -103,6 +103,11 @@ def test_plan_geometry_and_workspace_bounds(name):
             # packed copy: every matrix once in 16 bits (the patch weight with its padded K) + the stacked fp32 q | k | v biases
             exact = D * p.patch_k_padded * 2 + cfg.num_hidden_layers * ((4 * D * D + 2 * D * I) * 2 + 3 * D * 4)
             assert exact <= p.packed_bytes == lib.dfh_clipvh_packed_bytes(h) <= exact + 256 * (1 + 5 * cfg.num_hidden_layers)
+            # the offsets the pack writes are the ones the walk reads: the patch matrix, then per layer wqkv | wo | w1 | w2 | bqkv, each
+            # rounded up to 256 bytes, computed by hand
+            up = lambda n: -(-n // 256) * 256
+            per_layer = up(3 * D * D * 2) + up(D * D * 2) + 2 * up(D * I * 2) + up(3 * D * 4)
+            assert p.packed_bytes == up(D * p.patch_k_padded * 2) + cfg.num_hidden_layers * per_layer and per_layer % 256 == 0
     finally:
         lib.dfh_clipv_destroy(h)
 
