@@ -10,7 +10,7 @@ from . import _lib, data, evalio, prompts
 from ._lib import DfhError, set_storage, storage
 from .mutual import MutualEncoder
 from .pipeline import OutfitSampler, guidance_plan, sample_outfits, sampling_tables, train_forward, training_tables
-from .schedulers import DDIMScheduler, PNDMScheduler
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler
 from .training import AdamW8bit, EMAModel, FusedAdamW, clip_grad_norm_, train_step
 from .unet import UNet2DConditionModel, UNet2DConditionOutput
 from .vae import AutoencoderKL
@@ -27,6 +27,7 @@ from .difashion import DiFashion
 
 __all__ = [
     "DfhError", "set_storage", "storage", "UNet2DConditionModel", "UNet2DConditionOutput", "DDIMScheduler", "PNDMScheduler",
+    "DPMSolverMultistepScheduler",
     "MutualEncoder", "OutfitSampler", "sample_outfits", "train_forward", "guidance_plan", "sampling_tables", "training_tables",
     "FusedAdamW", "AdamW8bit", "EMAModel", "clip_grad_norm_", "train_step", "AutoencoderKL", "CLIPTextModel", "DiFashion",
     "CLIPVisionModelWithProjection", "CLIPVisionModelOutput", "CLIPTextModelWithProjection", "CLIPTextModelOutput", "CLIPScore",

@@ -156,6 +156,12 @@ class StepCoef(C.Structure):
                 ("sqrt_a_prev", C.c_float), ("dir_coef", C.c_float), ("std_dev", C.c_float)]
 
 
+class MultistepCoef(C.Structure):
+    """dfh_multistep_coef: conversion, kind and scalar coefficients of one dfh_cfg_multistep call."""
+    _fields_ = [("conv", C.c_int), ("kind", C.c_int), ("terms", C.c_int), ("c0", C.c_float), ("c1", C.c_float), ("w", C.c_float * 4),
+                ("cx", C.c_float), ("ce", C.c_float), ("cd0", C.c_float), ("cr", C.c_float), ("cd1", C.c_float)]
+
+
 class ProfClass(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -385,6 +391,7 @@ SIGNATURES = {
     "dfh_mutual_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "dfh_assemble_input": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
     "dfh_cfg_step": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _f, _f, _f, C.POINTER(StepCoef), _vp]),
+    "dfh_cfg_multistep": (_i, [_vp] * 9 + [_sz, _i, _f, _f, _f, C.POINTER(MultistepCoef), _vp]),
     "dfh_noise_mix": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "dfh_mse_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
 }

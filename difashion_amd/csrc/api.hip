@@ -658,6 +658,34 @@ int dfh_cfg_step(const float* eps_all, float* latents, float* eps_out, const flo
   return dfh::cfg_step_launch(eps_all, latents, eps_out, noise, (long)n, mode, cate_scale, hist_scale, mutual_scale, c,
                               (hipStream_t)stream);
 }
+int dfh_cfg_multistep(const float* out_all, const float* x_src, float* latents, float* m_out, float* q_out, float* x_save,
+                      const float* h1, const float* h2, const float* h3, size_t n, int mode, float cate_scale, float hist_scale,
+                      float mutual_scale, const dfh_multistep_coef* k, void* stream) {
+  DFH_REQUIRE(out_all && x_src && latents && k, "null argument");
+  DFH_REQUIRE(n != 0, "n == 0: nothing to update");
+  DFH_REQUIRE(mode >= CFG_NONE && mode <= CFG_MUTUAL, "bad guidance mode");
+  DFH_REQUIRE(k->conv >= MS_CONV_NONE && k->conv <= MS_CONV_X0_V, "unknown conv (0 none, 1 x0 from eps, 2 x0 from v)");
+  DFH_REQUIRE(k->kind >= MS_PLMS && k->kind <= MS_DPM2, "unknown kind (0 PLMS, 1 DPM1, 2 DPM2)");
+  if (k->kind == MS_PLMS) {
+    DFH_REQUIRE(k->terms >= 1 && k->terms <= 4, "terms outside 1..4");
+    DFH_REQUIRE(k->terms < 2 || h1, "history pointer h1 missing: PLMS with 2 or more terms reads it");
+    DFH_REQUIRE(k->terms < 3 || h2, "history pointer h2 missing: PLMS with 3 or more terms reads it");
+    DFH_REQUIRE(k->terms < 4 || h3, "history pointer h3 missing: PLMS with 4 terms reads it");
+  }
+  DFH_REQUIRE(k->kind != MS_DPM2 || h1, "history pointer h1 missing: DPM2 reads it");
+  // the update of element i reads the history at i and writes q_out at i in the same launch as latents: none of them may share memory
+  // with latents (latents == x_src is the normal in-place call)
+  const float* apart[] = {h1, h2, h3, q_out};
+  const uintptr_t lat0 = (uintptr_t)latents, bytes = (uintptr_t)n * sizeof(float);
+  for (const float* p : apart)
+    DFH_REQUIRE(!p || (uintptr_t)p + bytes <= lat0 || lat0 + bytes <= (uintptr_t)p, "latents aliases a history slot or q_out");
+  MultistepArgs a;
+  a.out_all = out_all; a.x_src = x_src; a.lat = latents; a.m_out = m_out; a.q_out = q_out; a.x_save = x_save;
+  a.h1 = h1; a.h2 = h2; a.h3 = h3; a.n = (long)n; a.mode = mode; a.sc = cate_scale; a.sh = hist_scale; a.sm = mutual_scale;
+  static_assert(sizeof(MultistepCoef) == sizeof(dfh_multistep_coef), "MultistepCoef mirrors dfh_multistep_coef");
+  std::memcpy(&a.k, k, sizeof(a.k));
+  return dfh::cfg_multistep_launch(a, (hipStream_t)stream);
+}
 int dfh_noise_mix(const float* x0, const float* noise, const int64_t* t, const float* sqrt_acp, const float* sqrt_1m_acp,
                   float* noisy, float* velocity, int rows, int L, void* stream) {
   return dfh::noise_mix_launch(x0, noise, (const long*)t, sqrt_acp, sqrt_1m_acp, noisy, velocity, rows, L, (hipStream_t)stream);

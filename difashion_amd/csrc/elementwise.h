@@ -24,7 +24,34 @@ struct StepCoef {
   float std_dev;     // eta * variance ** 0.5
 };
 
+// dfh_cfg_multistep: guidance combine + conversion of the model output + a multistep update over a short device history
+enum MsConv { MS_CONV_NONE = 0, MS_CONV_X0_EPS = 1, MS_CONV_X0_V = 2 };
+enum MsKind { MS_PLMS = 0, MS_DPM1 = 1, MS_DPM2 = 2 };
+
+struct MultistepCoef {    // == dfh_multistep_coef (include/difashion_hip.h), field for field
+  int conv;          // MsConv
+  int kind;          // MsKind
+  int terms;         // PLMS: 1..4 blended outputs, the new one included
+  float c0, c1;      // conversion: X0_EPS q = (x - c1*m) / c0 | X0_V q = c0*x - c1*m
+  float w[4];        // PLMS blend weights, newest first
+  float cx, ce;      // x' = cx*x - ce*b (PLMS) | cx also the x coefficient of DPM1 / DPM2
+  float cd0, cr, cd1;  // DPM: x' = (cx*x - cd0*q) - cd1*(cr*(q - h1))
+};
+
+struct MultistepArgs {
+  const float* out_all;           // [branches][n] raw model outputs
+  const float* x_src;             // sample the update starts from (the latents, or a saved copy)
+  float* lat;                     // x' (may be x_src)
+  float *m_out, *q_out, *x_save;  // optional taps: combined output, converted output (newest history slot), the x that was read
+  const float *h1, *h2, *h3;      // earlier converted outputs, newest first
+  long n;
+  int mode;
+  float sc, sh, sm;
+  MultistepCoef k;
+};
+
 namespace dfh {
+int cfg_multistep_launch(const MultistepArgs& a, hipStream_t s);
 int timestep_embed_launch(const float* t, bf16_t* out, int B, int dim, hipStream_t s);
 int nchw_to_nhwc_launch(const void* x, int is_bf16, bf16_t* out, int B, int C, int HW, hipStream_t s);
 int cast_f32_to_bf16_launch(const float* x, bf16_t* y, long n, hipStream_t s);

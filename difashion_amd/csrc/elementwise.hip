@@ -147,6 +147,76 @@ __global__ void cfg_step_kernel(const float* __restrict__ eps_all, float* __rest
   lat[i] = prev;
 }
 
+// V consecutive floats at p[i]: one 16-byte access (V = 4) or the scalar form (V = 1)
+template <int V>
+DFH_DEVICE void ew_load(const float* p, long i, float (&v)[V]) {
+  if constexpr (V == 4) {
+    const float4 t = *(const float4*)(p + i);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+    v[0] = p[i];
+  }
+}
+template <int V>
+DFH_DEVICE void ew_store(float* p, long i, const float (&v)[V]) {
+  if constexpr (V == 4) *(float4*)(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+  else p[i] = v[0];
+}
+
+DFH_DEVICE int cfg_branches(int mode) {
+  return mode == CFG_NONE ? 1 : (mode == CFG_FULL ? 4 : ((mode == CFG_CATE_HIST || mode == CFG_CATE_MUTUAL) ? 3 : 2));
+}
+
+// df.py:525-569 for the multistep schedulers (PNDM's PLMS branch, DPM-Solver++ 2M) in one launch: guidance combine, conversion of
+// the combined output (none | x0 from eps | x0 from v), the update over the history h1..h3 (newest first) and the taps.  x_src may
+// be lat itself: every load of an element comes before its stores, and an element belongs to one thread.
+//   PLMS: b = w0*q; b = b + w_j*h_j (j = 1..terms-1); x' = cx*x - ce*b
+//   DPM1: x' = cx*x - cd0*q            DPM2: D1 = cr*(q - h1); x' = (cx*x - cd0*q) - cd1*D1
+template <int V>
+__global__ void cfg_multistep_kernel(MultistepArgs a) {
+  const long i = gtid() * V;
+  if (i >= a.n) return;
+  const MultistepCoef& k = a.k;
+  const int R = cfg_branches(a.mode);
+  float o[4 * V];                       // [branch][lane]: cfg_combine reads it with stride V
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float t[V] = {};
+    if (r < R) ew_load<V>(a.out_all + (long)r * a.n, i, t);
+#pragma unroll
+    for (int l = 0; l < V; ++l) o[r * V + l] = t[l];
+  }
+  const bool plms = k.kind == MS_PLMS;
+  const bool need1 = k.kind == MS_DPM2 || (plms && k.terms >= 2), need2 = plms && k.terms >= 3, need3 = plms && k.terms >= 4;
+  float x[V], h1[V] = {}, h2[V] = {}, h3[V] = {};
+  ew_load<V>(a.x_src, i, x);
+  if (need1) ew_load<V>(a.h1, i, h1);
+  if (need2) ew_load<V>(a.h2, i, h2);
+  if (need3) ew_load<V>(a.h3, i, h3);
+  float m[V], q[V], y[V];
+#pragma unroll
+  for (int l = 0; l < V; ++l) {
+    m[l] = cfg_combine(a.mode, o, V, l, a.sc, a.sh, a.sm);
+    if (k.conv == MS_CONV_X0_EPS) q[l] = __fdiv_rn(__fsub_rn(x[l], __fmul_rn(k.c1, m[l])), k.c0);
+    else if (k.conv == MS_CONV_X0_V) q[l] = __fsub_rn(__fmul_rn(k.c0, x[l]), __fmul_rn(k.c1, m[l]));
+    else q[l] = m[l];
+    if (plms) {
+      float b = __fmul_rn(k.w[0], q[l]);
+      if (need1) b = __fadd_rn(b, __fmul_rn(k.w[1], h1[l]));
+      if (need2) b = __fadd_rn(b, __fmul_rn(k.w[2], h2[l]));
+      if (need3) b = __fadd_rn(b, __fmul_rn(k.w[3], h3[l]));
+      y[l] = __fsub_rn(__fmul_rn(k.cx, x[l]), __fmul_rn(k.ce, b));
+    } else {
+      y[l] = __fsub_rn(__fmul_rn(k.cx, x[l]), __fmul_rn(k.cd0, q[l]));
+      if (k.kind == MS_DPM2) y[l] = __fsub_rn(y[l], __fmul_rn(k.cd1, __fmul_rn(k.cr, __fsub_rn(q[l], h1[l]))));
+    }
+  }
+  if (a.m_out) ew_store<V>(a.m_out, i, m);
+  if (a.x_save) ew_store<V>(a.x_save, i, x);
+  if (a.q_out) ew_store<V>(a.q_out, i, q);
+  ew_store<V>(a.lat, i, y);
+}
+
 // scheduler.add_noise / get_velocity (df.py:158,:244): per-row coefficients from device tables
 __global__ void noise_mix_kernel(const float* __restrict__ x0, const float* __restrict__ noise,
                                  const long* __restrict__ t, const float* __restrict__ sqrt_a, const float* __restrict__ sqrt_1ma,
@@ -249,6 +319,15 @@ int cfg_step_launch(const float* eps_all, float* lat, float* eps_out, const floa
   DFH_REQUIRE(mode >= CFG_NONE && mode <= CFG_MUTUAL, "bad guidance mode");
   hipLaunchKernelGGL(cfg_step_kernel, ew_grid(n), dim3(EW_BLOCK), 0, s, eps_all, lat, eps_out, noise, n, mode, sc, sh, sm, k);
   return check_launch("cfg_step_kernel");
+}
+
+int cfg_multistep_launch(const MultistepArgs& a, hipStream_t s) {
+  const void* ptrs[] = {a.out_all, a.x_src, a.lat, a.m_out, a.q_out, a.x_save, a.h1, a.h2, a.h3};
+  bool vec = a.n % 4 == 0;              // 16-byte accesses: whole groups of four, every buffer that is given 16-byte aligned
+  for (const void* p : ptrs) vec = vec && ((uintptr_t)p & 15) == 0;
+  if (vec) hipLaunchKernelGGL(cfg_multistep_kernel<4>, ew_grid(a.n / 4), dim3(EW_BLOCK), 0, s, a);
+  else hipLaunchKernelGGL(cfg_multistep_kernel<1>, ew_grid(a.n), dim3(EW_BLOCK), 0, s, a);
+  return check_launch("cfg_multistep_kernel");
 }
 
 int noise_mix_launch(const float* x0, const float* noise, const long* t, const float* sqrt_a, const float* sqrt_1ma,

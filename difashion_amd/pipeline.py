@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from .mutual import MutualEncoder
-from .schedulers import DDIMScheduler, PNDMScheduler, STEP_NONE
+from .schedulers import DDIMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, STEP_NONE, cfg_multistep
 
 # guidance modes, replica order and which conditions are real per replica (hist, mutual, prompt):
 # fashion_generation difashion.py:309-325 (mode), :388-427 and :494-512 (stacking), :525-566 (combine)
@@ -100,7 +100,9 @@ class OutfitSampler:
 
     ``prepare`` does the per-run setup (replica stacks, index tables, buffers); ``step(i)`` is one
     denoising step = sibling reduce + MutualEncoder + input assembly + U-Net forward at batch R*F +
-    guidance combine + scheduler update.  Nothing is allocated inside ``step`` on the DDIM path."""
+    guidance combine + scheduler update.  Nothing is allocated inside ``step`` with the three scheduler classes of this package:
+    the combine and the update are one launch (dfh_cfg_step for DDIM, dfh_cfg_multistep for PLMS and DPM-Solver++, whose output
+    history lives in slots allocated by ``prepare``).  Any other scheduler object goes through its own ``step``."""
 
     def __init__(self, unet, fashion_encoder: MutualEncoder, scheduler):
         self.unet, self.enc, self.sched = unet, fashion_encoder, scheduler
@@ -137,7 +139,13 @@ class OutfitSampler:
         self.is_ddim = isinstance(self.sched, DDIMScheduler)
         self.x_in = torch.empty((self.R * self.F, 2 * init_latents.shape[1], S, S), **f32)
         self.mutual_bf = torch.empty((self.F, self.CL), dtype=_lib.storage_dtype(), device=dev)
-        self.eps_comb = torch.empty_like(self.latents) if (keep_eps or not self.is_ddim) else None
+        # multistep schedulers: the history of (converted) outputs, rotated by pointer (scheduler.step_plan), and PLMS' saved sample
+        is_plms = isinstance(self.sched, PNDMScheduler)
+        self.is_multistep = is_plms or isinstance(self.sched, DPMSolverMultistepScheduler)
+        self.hist_slots = [torch.empty_like(self.latents) for _ in range(4 if is_plms else (2 if self.is_multistep else 0))]
+        self.x_saved = torch.empty_like(self.latents) if is_plms else None
+        # the combined output is kept for the taps, and for a scheduler object that is none of the three classes (its own step reads it)
+        self.eps_comb = torch.empty_like(self.latents) if (keep_eps or not (self.is_ddim or self.is_multistep)) else None
         self.mutual = self.null_lat.expand(self.F, -1, -1, -1).contiguous()   # stays when mutual guidance is off
         self.scales = (float(cate_scale), float(hist_scale), float(mutual_scale))
         self.one_minus_eta, self.eta = float(1 - eta), float(eta)
@@ -181,6 +189,12 @@ class OutfitSampler:
                 noise = torch.randn(lat.shape, generator=self.generator, device=lat.device, dtype=torch.float32)
             _lib.call("dfh_cfg_step", _lib.ptr(self.eps_all), _lib.ptr(lat), _lib.ptr(self.eps_comb), _lib.ptr(noise),
                       lat.numel(), self.mode, sc, sh, sm, C.byref(k), sp())
+        elif self.is_multistep:
+            k, roles = self.sched.step_plan(i)
+            cfg_multistep(self.eps_all, self.x_saved if roles["x_src"] == "saved" else lat, lat, k,
+                          reads=[self.hist_slots[j] for j in roles["reads"]],
+                          q_out=None if roles["push"] is None else self.hist_slots[roles["push"]],
+                          x_save=self.x_saved if roles["x_save"] else None, m_out=self.eps_comb, mode=self.mode, scales=self.scales)
         else:
             k = _lib.StepCoef()
             k.kind = STEP_NONE

@@ -1,11 +1,11 @@
-"""DDIMScheduler / PNDMScheduler with the diffusers call surface the reference glue uses
+"""DDIMScheduler / PNDMScheduler / DPMSolverMultistepScheduler with the diffusers call surface the reference glue uses
 (SURVEY.md 8b): ``config.num_train_timesteps`` / ``config.prediction_type``
 (DiFashion/models/difashion.py:154,:241), ``add_noise`` (:158), ``get_velocity`` (:244),
 ``alphas_cumprod`` (:270,:639), ``set_timesteps`` + ``timesteps`` (:356-357), ``scale_model_input``
 (:472), ``step(eps, t, x, **{eta, generator}, return_dict=False)[0]`` (:569, kwargs discovered by
 ``inspect.signature`` :665-673), ``order`` (:433,:574), ``init_noise_sigma`` (:632).
 
-The elementwise updates run in libdifashion_hip.so (dfh_cfg_step / dfh_noise_mix); the host side only
+The elementwise updates run in libdifashion_hip.so (dfh_cfg_step / dfh_cfg_multistep / dfh_noise_mix); the host side only
 derives the per-step scalar coefficients from the fp32 alpha-bar table, with the same fp32 operations
 the published diffusers code uses.  Device tensors only: no CPU fallback.
 """
@@ -24,10 +24,23 @@ from .unet import FrozenDict
 
 CFG_NONE = 0
 STEP_NONE, STEP_DDIM, STEP_LINEAR = -1, 0, 1
+# dfh_cfg_multistep: conversion of the model output and kind of the update (include/difashion_hip.h)
+MS_CONV_NONE, MS_CONV_X0_EPS, MS_CONV_X0_V = 0, 1, 2
+MS_PLMS, MS_DPM1, MS_DPM2 = 0, 1, 2
+PLMS_WEIGHTS = ((1.0,), (1.5, -0.5), (23 / 12, -16 / 12, 5 / 12), (55 / 24, -59 / 24, 37 / 24, -9 / 24))    # newest first
 
 
 class SchedulerOutput(dict):
     __getattr__ = dict.__getitem__
+
+
+def cfg_multistep(out_all, x_src, lat, coef: "_lib.MultistepCoef", *, reads=(), q_out=None, x_save=None, m_out=None,
+                  mode: int = CFG_NONE, scales=(1.0, 1.0, 1.0)):
+    """One dfh_cfg_multistep launch: ``lat`` <- update of ``x_src`` by the combined ``out_all`` and the history ``reads`` (newest first)."""
+    h = [_lib.ptr(t) for t in reads] + [None] * (3 - len(reads))
+    sc, sh, sm = scales
+    _lib.call("dfh_cfg_multistep", _lib.ptr(out_all), _lib.ptr(x_src), _lib.ptr(lat), _lib.ptr(m_out), _lib.ptr(q_out), _lib.ptr(x_save),
+              *h, lat.numel(), mode, sc, sh, sm, C.byref(coef), _lib.stream_ptr())
 
 
 def _require_cuda(*tensors):
@@ -68,6 +81,13 @@ class _SchedulerBase:
         with open(os.path.join(d, cls.config_name)) as f:
             cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
         cfg.update(kwargs)
+        return cls(**cfg)
+
+    @classmethod
+    def from_config(cls, config, **overrides):
+        """diffusers' scheduler swap, ``Other.from_config(pipe.scheduler.config)``: keys this class does not know are ignored."""
+        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_")}
+        cfg.update(overrides)
         return cls(**cfg)
 
     def save_pretrained(self, save_directory: str):
@@ -229,24 +249,168 @@ class PNDMScheduler(_SchedulerBase):
             model_output = self._blend([(23 / 12, e[-1]), (-16 / 12, e[-2]), (5 / 12, e[-3])])
         else:
             model_output = self._blend([(55 / 24, e[-1]), (-59 / 24, e[-2]), (37 / 24, e[-3]), (-9 / 24, e[-4])])
+        k = _lib.StepCoef()
+        k.kind = STEP_LINEAR
+        k.sqrt_a_t, k.sqrt_b_t = self._transfer_coef(t, prev_t)
+        prev = self._apply(k, model_output, sample)
+        self.counter += 1
+        return SchedulerOutput(prev_sample=prev) if return_dict else (prev,)
+
+    def _transfer_coef(self, t: int, prev_t: int):
+        """(c_x, c_e) of the transfer x' = c_x*x - c_e*out (diffusers _get_prev_sample) as host floats; the caller's c_float rounds them once."""
         a_t = self.alphas_cumprod[t]
         a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
         b_t, b_prev = 1 - a_t, 1 - a_prev
         coeff = float((a_prev / a_t) ** 0.5)
         denom = a_t * b_prev ** 0.5 + (a_t * b_t * a_prev) ** 0.5
         c_e = float((a_prev - a_t) / denom)
-        k = _lib.StepCoef()
-        k.kind = STEP_LINEAR
         if self.config.prediction_type == "v_prediction":
             # diffusers _get_prev_sample: eps = sqrt(a_t) v + sqrt(b_t) x first, then the same transfer -- still linear in (x, v):
             # x' = (coeff - c_e sqrt(b_t)) x - c_e sqrt(a_t) v   (difashion.py:241-247 trains the v target under this setting)
-            k.sqrt_a_t = coeff - c_e * float(b_t ** 0.5)
-            k.sqrt_b_t = c_e * float(a_t ** 0.5)
-        elif self.config.prediction_type == "epsilon":
-            k.sqrt_a_t = coeff
-            k.sqrt_b_t = c_e
+            return coeff - c_e * float(b_t ** 0.5), c_e * float(a_t ** 0.5)
+        if self.config.prediction_type == "epsilon":
+            return coeff, c_e
+        raise ValueError(f"prediction_type given as {self.config.prediction_type} must be one of `epsilon` or `v_prediction`")
+
+    def step_plan(self, index: int):
+        """Entry ``index`` of the PLMS list as ONE dfh_cfg_multistep call (what OutfitSampler launches): the filled coefficient struct and
+        the pointer roles, a pure function of the index for a run that starts at entry 0.  It restates the bookkeeping of ``step``:
+        entry 0 saves x and pushes its output; entry 1 pushes nothing and starts from the saved x with weights 0.5 / 0.5 over the new
+        output and entry 0's; later entries push and blend the newest 2, 3, 4 outputs.  The raw outputs are blended for both prediction
+        types (conv NONE); ``_transfer_coef`` folds the v-prediction into the transfer.
+
+        roles: ``push`` = history slot (of 4) that takes the new output, or None; ``reads`` = slots of the earlier outputs, newest first,
+        paired with ``coef.w[1:]``; ``x_src`` = 'latents' | 'saved'; ``x_save`` = whether x is stored to the saved-sample buffer."""
+        ratio = self.config.num_train_timesteps // self.num_inference_steps
+        t = int(self._timesteps_host[index])
+        prev_t = t - ratio
+        k = _lib.MultistepCoef()
+        k.conv, k.kind = MS_CONV_NONE, MS_PLMS
+        if index == 1:
+            prev_t, t = t, t + ratio
+            weights, roles = (0.5, 0.5), dict(push=None, reads=[0], x_src="saved", x_save=False)
         else:
-            raise ValueError(f"prediction_type given as {self.config.prediction_type} must be one of `epsilon` or `v_prediction`")
-        prev = self._apply(k, model_output, sample)
-        self.counter += 1
+            p = 0 if index == 0 else index - 1          # this entry's push number (entry 1 pushes nothing)
+            weights = PLMS_WEIGHTS[min(p, 3)]
+            roles = dict(push=p % 4, reads=[(p - j) % 4 for j in range(1, len(weights))], x_src="latents", x_save=index == 0)
+        k.terms = len(weights)
+        for j, w in enumerate(weights):
+            k.w[j] = w
+        k.cx, k.ce = self._transfer_coef(t, prev_t)
+        return k, roles
+
+
+class DPMSolverMultistepScheduler(_SchedulerBase):
+    """DPM-Solver++ multistep (2M), data-prediction form, deterministic.
+
+    The call surface is **recalled from diffusers 0.18.2** (DPMSolverMultistepScheduler), as in SURVEY.md Appendix B: that package is not
+    installed where this one is built, so the surface is restated from the published code and not pinned against it.  Supported:
+    ``solver_order`` 1 | 2, ``algorithm_type='dpmsolver++'``, ``solver_type`` 'midpoint' | 'heun', ``prediction_type`` 'epsilon' |
+    'v_prediction', ``lower_order_final``.  Order 3, 'dpmsolver', the 'sde-*' variants, thresholding, Karras sigmas, lambda-min clipping
+    and ``prediction_type='sample'`` raise ValueError.
+
+    ``step_plan`` derives the scalars of one update from the fp32 tables with fp32 torch scalar operations; the update itself is one
+    dfh_cfg_multistep launch (conversion to x0, history difference, linear update)."""
+
+    def __init__(self, *a, solver_order: int = 2, algorithm_type: str = "dpmsolver++", solver_type: str = "midpoint",
+                 lower_order_final: bool = True, thresholding: bool = False, use_karras_sigmas: bool = False,
+                 lambda_min_clipped: float = -float("inf"), **k):
+        super().__init__(*a, **k)
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order={solver_order!r}: orders 1 and 2 are supported")
+        if algorithm_type != "dpmsolver++":
+            raise ValueError(f"algorithm_type={algorithm_type!r}: only 'dpmsolver++' is supported")
+        if solver_type not in ("midpoint", "heun"):
+            raise ValueError(f"solver_type={solver_type!r}: 'midpoint' and 'heun' are supported")
+        if thresholding:
+            raise ValueError("thresholding=True is not supported (latent-space sampling does not use it)")
+        if use_karras_sigmas:
+            raise ValueError("use_karras_sigmas=True is not supported")
+        if lambda_min_clipped != -float("inf"):
+            raise ValueError(f"lambda_min_clipped={lambda_min_clipped!r} is not supported (no clipping of lambda)")
+        if self.config.prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"prediction_type={self.config.prediction_type!r}: 'epsilon' and 'v_prediction' are supported")
+        self.config.update(solver_order=solver_order, algorithm_type=algorithm_type, solver_type=solver_type,
+                           lower_order_final=bool(lower_order_final), thresholding=False)
+        self.alpha_t = self.alphas_cumprod ** 0.5
+        self.sigma_t = (1 - self.alphas_cumprod) ** 0.5
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+        self._reset()
+
+    def _reset(self):
+        self.model_outputs = [None, None]     # the two history slots (converted outputs); push number p writes slot p % 2
+        self.lower_order_nums = 0
+        self._pushes = 0
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        T = self.config.num_train_timesteps
+        ts = np.linspace(0, T - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
+        _, first = np.unique(ts, return_index=True)
+        ts = ts[np.sort(first)]                     # duplicates removed, order kept
+        self.num_inference_steps = len(ts)
+        self._timesteps_host = ts.tolist()
+        self.timesteps = torch.from_numpy(ts).to(device) if device is not None else torch.from_numpy(ts)
+        self._reset()
+
+    def step_index(self, timestep) -> int:
+        t = int(timestep)
+        return self._timesteps_host.index(t) if t in self._timesteps_host else len(self._timesteps_host) - 1
+
+    def step_plan(self, index: int, lower_order_nums: Optional[int] = None, pushes: Optional[int] = None):
+        """Step ``index`` of the timestep list as one dfh_cfg_multistep call: the filled coefficient struct and the pointer roles.
+        ``lower_order_nums`` (earlier outputs available, at most solver_order) and ``pushes`` (outputs pushed so far) default to
+        those of a run that started at entry 0, which makes the plan a pure function of the index.
+
+        roles: ``push`` = history slot (of 2) that takes the converted output; ``reads`` = [slot of the previous output] for a
+        second-order update, [] for a first-order one; ``x_src`` = 'latents'; ``x_save`` = False."""
+        ts = self._timesteps_host
+        last = index == len(ts) - 1
+        if lower_order_nums is None:
+            lower_order_nums = min(index, self.config.solver_order)
+        if pushes is None:
+            pushes = index
+        s0 = ts[index]
+        t = 0 if last else ts[index + 1]
+        first_order = (self.config.solver_order == 1 or lower_order_nums < 1
+                       or (last and self.config.lower_order_final and len(ts) < 15))
+        lam, alpha, sigma = self.lambda_t, self.alpha_t, self.sigma_t
+        h = lam[t] - lam[s0]
+        e = alpha[t] * (torch.exp(-h) - 1.0)
+        k = _lib.MultistepCoef()
+        k.conv = MS_CONV_X0_V if self.config.prediction_type == "v_prediction" else MS_CONV_X0_EPS
+        k.c0, k.c1 = float(alpha[s0]), float(sigma[s0])
+        k.terms = 1
+        k.cx, k.cd0 = float(sigma[t] / sigma[s0]), float(e)
+        roles = dict(push=pushes % 2, reads=[], x_src="latents", x_save=False)
+        if first_order:
+            k.kind = MS_DPM1
+            return k, roles
+        s1 = ts[index - 1]
+        r0 = (lam[s0] - lam[s1]) / h
+        k.kind = MS_DPM2
+        k.cr = float(1.0 / r0)
+        if self.config.solver_type == "midpoint":
+            k.cd1 = float(0.5 * e)
+        else:
+            k.cd1 = float(-(alpha[t] * ((torch.exp(-h) - 1.0) / h + 1.0)))
+        roles["reads"] = [(pushes - 1) % 2]
+        return k, roles
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True):
+        """One solver step.  ``generator`` is accepted and ignored: the solver is deterministic."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' first")
+        _require_cuda(model_output, sample)
+        if model_output.dtype != torch.float32 or sample.dtype != torch.float32:
+            raise TypeError("scheduler.step operates on float32 latents")
+        k, roles = self.step_plan(self.step_index(timestep), self.lower_order_nums, self._pushes)
+        out, x = model_output.contiguous(), sample.contiguous()
+        slots = self.model_outputs
+        if slots[roles["push"]] is None or slots[roles["push"]].shape != x.shape or slots[roles["push"]].device != x.device:
+            slots[roles["push"]] = torch.empty_like(x)
+        prev = torch.empty_like(x)
+        cfg_multistep(out, x, prev, k, reads=[slots[s] for s in roles["reads"]], q_out=slots[roles["push"]])
+        self._pushes += 1
+        if self.lower_order_nums < self.config.solver_order:
+            self.lower_order_nums += 1
         return SchedulerOutput(prev_sample=prev) if return_dict else (prev,)

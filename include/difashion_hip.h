@@ -957,6 +957,28 @@ typedef struct dfh_step_coef {
 } dfh_step_coef;
 int dfh_cfg_step(const float* eps_all, float* latents, float* eps_out, const float* noise, size_t n, int mode,
                  float cate_scale, float hist_scale, float mutual_scale, const dfh_step_coef* k, void* stream);
+/* Guidance combine fused with one step of a multistep scheduler (PNDM's PLMS branch, DPM-Solver++ 2M), fp32, one launch.  Per element i < n:
+ *   m = combine(mode, out_all, i)                      -> m_out[i] if given
+ *   x = x_src[i]                                       -> x_save[i] if given
+ *   q = m | (x - c1*m) / c0 | c0*x - c1*m   (conv 0|1|2) -> q_out[i] if given (the newest history slot)
+ *   kind 0 PLMS: b = w[0]*q; b = b + w[j]*h_j (j = 1..terms-1); x' = cx*x - ce*b
+ *   kind 1 DPM1: x' = cx*x - cd0*q        kind 2 DPM2: x' = (cx*x - cd0*q) - cd1*(cr*(q - h1))
+ *   latents[i] = x'
+ * h1..h3 are the earlier converted outputs, newest first; the caller rotates the pointers.  latents == x_src is the in-place call;
+ * latents must not share memory with h1..h3 or q_out.  Every product and sum is rounded on its own (no fused multiply-add). */
+typedef struct dfh_multistep_coef {
+  int conv;            /* 0 none, 1 x0 from an epsilon prediction, 2 x0 from a v prediction */
+  int kind;            /* 0 PLMS, 1 DPM1, 2 DPM2 */
+  int terms;           /* PLMS: 1..4 */
+  float c0, c1;
+  float w[4];
+  float cx, ce;
+  float cd0, cr, cd1;
+} dfh_multistep_coef;
+int dfh_cfg_multistep(const float* out_all, const float* x_src, float* latents, float* m_out /* may be NULL */,
+                      float* q_out /* may be NULL */, float* x_save /* may be NULL */, const float* h1, const float* h2,
+                      const float* h3, size_t n, int mode, float cate_scale, float hist_scale, float mutual_scale,
+                      const dfh_multistep_coef* k, void* stream);
 /* DDIMScheduler.add_noise / get_velocity df.py:158,:244 */
 int dfh_noise_mix(const float* x0, const float* noise, const int64_t* t, const float* sqrt_acp, const float* sqrt_1m_acp,
                   float* noisy, float* velocity, int rows, int L, void* stream);
