@@ -19,6 +19,8 @@ from .clip_vision import CLIPVisionModelOutput, CLIPVisionModelWithProjection
 from .image_processor import CLIPImageProcessor
 from .evalscores import (CLIPScore, CompatibilityEvaluator, FashionEvaluator, candidate_cosine, extract_image_features, lpips_given_data,
                          lpips_retrieval, pair_cosine)
+from .evalscores import (RankResult, clip_gor_retrieval_given_data, clip_og_retrieval_given_data, embed_row_norms, rank_candidates,
+                         recall_at)
 from .lpips import LPIPS
 from .evalscores import (activation_statistics, fid_given_data, frechet_distance, inception_rows, inception_score_from_probs,
                          inception_score_given_data)
@@ -33,6 +35,7 @@ __all__ = [
     "CLIPVisionModelWithProjection", "CLIPVisionModelOutput", "CLIPTextModelWithProjection", "CLIPTextModelOutput", "CLIPScore",
     "CompatibilityEvaluator", "FashionEvaluator", "pair_cosine", "candidate_cosine", "CLIPImageProcessor", "extract_image_features",
     "LPIPS", "lpips_given_data", "lpips_retrieval",
+    "RankResult", "rank_candidates", "embed_row_norms", "recall_at", "clip_og_retrieval_given_data", "clip_gor_retrieval_given_data",
     "FIDInceptionV3", "InceptionV3", "activation_statistics", "frechet_distance", "fid_given_data", "inception_rows",
     "inception_score_from_probs", "inception_score_given_data",
 ]

@@ -209,6 +209,10 @@ SIGNATURES = {
     "dfh_clip_text_embeds": (_i, [_vp, C.POINTER(_vp), _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _sz, _i, _i, _vp]),
     "dfh_embed_pair_cosine": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp]),
     "dfh_embed_candidates": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "dfh_embed_row_norms": (_i, [_vp, _vp, _i, _i, _vp]),
+    "dfh_embed_rank_workspace_bytes": (_sz, [_i, C.c_long, _i]),
+    "dfh_embed_rank": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "dfh_embed_recall": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "dfh_compat_workspace_bytes": (_sz, [_i, _i, _i]),
     "dfh_compat_score": (_i, [C.POINTER(_vp), _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dfh_compat_pred_score": (_i, [C.POINTER(_vp), _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),

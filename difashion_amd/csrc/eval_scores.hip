@@ -4,8 +4,8 @@
 // Replaces (arithmetic):
 //   * 100 * F.cosine_similarity of normalised rows -- CLIP score, CLIP image score (Evaluation/eval_utils.py:101-135) and the
 //     personalisation similarity (:503-538): dfh_embed_pair_cosine;
-//   * the retrieval of :652-723 (5 candidates a row) and :725-767 (thousands): cosine against gathered table rows + argmax:
-//     dfh_embed_candidates;
+//   * the retrieval of :652-723 (5 candidates a row): cosine against gathered table rows + argmax: dfh_embed_candidates (the ranking of
+//     a whole category per row, :725-767, is eval_rank.hip);
 //   * FashionEvaluator (Evaluation/compatibility_evaluator/compatibility_net.py:14-81) under the gather of
 //     CompatibilityEvaluator.evaluate_compatibility (eval_utils.py:574-588): dfh_compat_score.  The reference runs one outfit at a
 //     time in a Python loop; here all outfits of a call go through every layer together.

@@ -84,9 +84,11 @@ struct TileKahanSum {
 // multiple of 4, rows 16-byte aligned.  The next k-tile's global loads are issued before the current tile's MFMAs (register prefetch);
 // rows beyond M / N read the last row and are never stored.  store(m, n, value) is called for every in-range element with
 // value = sum + bias[n] (bias may be null: + 0; it is read once a column).
+// w_rows (null: W row n is row n): row n of the operand is W row w_rows[n], clamped into [0, w_row_count) before it addresses anything --
+// the gather rides in the tile's own global loads (eval_rank.hip).  The null default folds away in the callers that do not pass it.
 template <class Sum, class Store>
 DFH_DEVICE void gemm_tile(const float* __restrict__ A, int lda, const float* __restrict__ W, int ldw, const float* __restrict__ bias, int M,
-                          int N, int K, Store store) {
+                          int N, int K, Store store, const int64_t* __restrict__ w_rows = nullptr, int w_row_count = 0) {
   __shared__ float As[GT_K * GT_LD];
   __shared__ float Ws[GT_K * GT_LD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -95,7 +97,9 @@ DFH_DEVICE void gemm_tile(const float* __restrict__ A, int lda, const float* __r
   // staging: thread -> (row = tid % 64, k-quads tid / 64 and tid / 64 + 4)
   const int srow = tid & 63, sq = tid >> 6;
   const float* ap = A + (long)min(m0 + srow, M - 1) * lda;
-  const float* wp = W + (long)min(n0 + srow, N - 1) * ldw;
+  long wrow = min(n0 + srow, N - 1);
+  if (w_rows) wrow = min(max(w_rows[wrow], (int64_t)0), (int64_t)w_row_count - 1);
+  const float* wp = W + wrow * ldw;
   float4 ra[2], rw[2];
   auto fetch = [&](int k0) {
 #pragma unroll

@@ -3,8 +3,10 @@
 What the reference computes from the CLIP embeddings once ``encode_image`` / ``encode_text`` have run (Evaluation/eval_utils.py):
   * ``CLIPScore.calculate_clip_score`` (:101-114), ``calculate_clip_img_score`` (:117-135) and the personalisation similarity
     (:503-538): normalise, ``100 * F.cosine_similarity`` per row;
-  * the retrieval accuracy (:652-723, five candidates a row) and ranking (:725-767, thousands): cosine against ``cnn_features[candidates]``
-    and an argmax;
+  * the retrieval accuracy (:652-723, five candidates a row): cosine against ``cnn_features[candidates]`` and an argmax;
+  * the grounding retrieval (:725-767, ``clip_og_retrieval_given_data``): every image against ALL items of its category -- ragged
+    candidate sets -- the best 100 kept in order, recall@{10,20,50,100} (csrc/eval_rank.hip: ``rank_candidates``,
+    ``CLIPScore.grounding_retrieval``);
   * ``CompatibilityEvaluator.evaluate_compatibility`` (:574-588) over ``FashionEvaluator``
     (Evaluation/compatibility_evaluator/compatibility_net.py:14-81), which the reference runs one outfit at a time.
 And, over images and not embeddings:
@@ -83,6 +85,187 @@ def candidate_cosine(gen: torch.Tensor, table: torch.Tensor, candidates: torch.T
             _lib.call("dfh_embed_candidates", _lib.ptr(gen), _lib.ptr(table), _lib.ptr(cand), _lib.ptr(sims), _lib.ptr(preds), rows, K,
                       gen.shape[1], table.shape[0], _lib.stream_ptr())
     return sims, preds
+
+
+# ------------------------------------------------------------------ grounding retrieval: ragged top-N ranking, recall@N (csrc/eval_rank.hip)
+RANK_NMAX = 128                      # DFH_EMBED_RANK_NMAX
+RANK_WORKSPACE_CAP = 256 << 20       # bytes of similarities materialised at a time (rank_candidates cuts its rows into bands under it)
+_INT_DTYPES = (torch.int64, torch.int32, torch.int16, torch.uint8, torch.int8)
+
+
+class RankResult:
+    """What ``rank_candidates`` returns, in the caller's row order: ``ids [rows, top_n]`` int64 item ids, ``positions [rows, top_n]`` int64
+    indices into the row's candidate list, ``sims [rows, top_n]`` fp32 and ``counts [rows]`` int32 = min(len(candidates), top_n).  Slots
+    from ``counts[r]`` on hold id -1, position -1, similarity -inf.  ``preds`` is the best id of every row."""
+    __slots__ = ("ids", "positions", "sims", "counts")
+
+    def __init__(self, ids, positions, sims, counts):
+        self.ids, self.positions, self.sims, self.counts = ids, positions, sims, counts
+
+    @property
+    def preds(self) -> torch.Tensor:
+        return self.ids[:, 0]
+
+
+def _id_list(c, what: str) -> torch.Tensor:
+    t = c if isinstance(c, torch.Tensor) else torch.as_tensor(list(c), dtype=torch.int64)
+    if t.dtype not in _INT_DTYPES:
+        raise TypeError(f"{what} must hold integer ids, got {t.dtype}")
+    if t.dim() != 1:
+        raise ValueError(f"{what} must be a 1-D list of ids, got shape {tuple(t.shape)}")
+    return t.to(torch.int64)
+
+
+def _candidate_sets(candidates, rows: int, table_rows: int):
+    """The ragged candidate lists of ``rows`` rows as the kernels take them -> ``(flat, set_off, row_set, order)``: ``flat`` the int64 ids
+    of the DISTINCT lists back to back (a CPU tensor unless a list lives on a device), ``set_off`` their ``nsets + 1`` offsets,
+    ``row_set[r]`` the set of caller row r and ``order`` the caller rows sorted by set (stable), which is how the kernels want them.
+
+    ``candidates``: one 1-D integer tensor or list per row, or the tuple ``(set_ids [rows], sets)`` with ``sets`` a dict or list of such
+    lists.  Equal lists are found by identity first (a dataset hands the same per-category tensor to every row of the category) and, for
+    lists on the CPU, by content second.  Ids outside [0, table_rows) raise IndexError, checked where the ids live: CPU ids on the CPU,
+    device ids with one ``aminmax``."""
+    if isinstance(candidates, tuple) and len(candidates) == 2 and (isinstance(candidates[1], dict) or (
+            isinstance(candidates[1], (list, tuple)) and len(candidates[1]) > 0 and not isinstance(candidates[1][0], int))):
+        set_ids, sets = candidates
+        set_ids = set_ids.tolist() if isinstance(set_ids, torch.Tensor) else list(set_ids)
+        try:
+            per_row = [sets[k] for k in set_ids]
+        except (KeyError, IndexError) as e:
+            raise IndexError(f"set id {e.args[0]!r} names no candidate set") from e
+    else:
+        per_row = list(candidates)
+    if len(per_row) != rows:
+        raise ValueError(f"candidates holds {len(per_row)} lists for {rows} rows")
+    uniq, by_identity, by_content, row_set = [], {}, {}, []
+    for r, c in enumerate(per_row):
+        s = by_identity.get(id(c))
+        if s is None:
+            t = _id_list(c, f"candidates of row {r}")
+            key = (t.numel(), t.numpy().tobytes()) if t.device.type == "cpu" else None
+            s = by_content.get(key) if key is not None else None
+            if s is None:
+                s = len(uniq)
+                uniq.append(t)
+                if key is not None:
+                    by_content[key] = s
+            by_identity[id(c)] = s
+        row_set.append(s)
+    set_off = [0]
+    for t in uniq:
+        set_off.append(set_off[-1] + t.numel())
+    devs = [t.device for t in uniq if t.device.type != "cpu"]
+    flat = torch.cat([t.to(devs[0]) for t in uniq]) if devs else (torch.cat(uniq) if uniq else torch.empty(0, dtype=torch.int64))
+    if flat.numel():
+        lo, hi = (int(v) for v in torch.aminmax(flat)) if devs else (int(flat.min()), int(flat.max()))
+        if lo < 0 or hi >= table_rows:
+            raise IndexError(f"candidate ids out of range [0, {table_rows}): min {lo}, max {hi}")
+    order = sorted(range(rows), key=row_set.__getitem__)
+    return flat, set_off, row_set, order
+
+
+def _rank_bands(lens, cap_bytes: int):
+    """Cut rows (their sets' lengths in kernel order) into bands ``(start, stop)`` whose similarity block -- rows x the band's longest set
+    rounded up to 64, fp32 -- stays under ``cap_bytes``; a band holds at least one row."""
+    bands, start, longest = [], 0, 0
+    for r, n in enumerate(lens):
+        ld = (max(longest, n, 1) + 63) // 64 * 64
+        if r > start and (r - start + 1) * ld * 4 > cap_bytes:
+            bands.append((start, r))
+            start, ld = r, (max(n, 1) + 63) // 64 * 64
+        longest = ld
+    if len(lens) > start:
+        bands.append((start, len(lens)))
+    return bands
+
+
+def embed_row_norms(x: torch.Tensor) -> torch.Tensor:
+    """``|x_r|`` of a [rows, dim] fp32 device matrix (dim a multiple of 4): the table norms ``rank_candidates`` takes, computed once for
+    many batches."""
+    x = _device_rows(x, "embed_row_norms: x")
+    if x.dim() != 2 or x.shape[1] % 4:
+        raise ValueError(f"embed_row_norms needs [rows, dim] with dim a multiple of 4, got {tuple(x.shape)}")
+    out = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
+    if x.shape[0]:
+        with torch.cuda.device(x.device):
+            _lib.call("dfh_embed_row_norms", _lib.ptr(x), _lib.ptr(out), x.shape[0], x.shape[1], _lib.stream_ptr())
+    return out
+
+
+@torch.no_grad()
+def rank_candidates(gen: torch.Tensor, table: torch.Tensor, candidates, top_n: int, table_norms: Optional[torch.Tensor] = None,
+                    workspace_cap: int = RANK_WORKSPACE_CAP) -> RankResult:
+    """Every row of ``gen [rows, dim]`` ranked by cosine similarity against ITS OWN candidate list of rows of ``table [table_rows, dim]``;
+    the best ``top_n`` (at most 128) kept in order -> ``RankResult``.  The ranking of ``clip_og_retrieval_given_data``
+    (eval_utils.py:733-750) for all rows at once, candidate lists of any lengths (``_candidate_sets`` says which forms).
+
+    Order: descending, a NaN above everything (``torch.topk``'s order), among equal values (-0.0 and +0.0, two NaNs) the lower position
+    in the candidate list first.  A zero row gives NaN in its own similarities only.  The rows of one list share matrix tiles; the result
+    of a row does not depend on the rows it is ranked with, on ``workspace_cap`` or on the order of the rows."""
+    gen, table = _device_rows(gen, "rank_candidates: gen"), _device_rows(table, "rank_candidates: table")
+    if gen.dim() != 2 or table.dim() != 2 or gen.shape[1] != table.shape[1] or gen.device != table.device or table.shape[0] < 1:
+        raise ValueError(f"gen [rows, dim] and table [table_rows >= 1, dim] must share dim and device, got {tuple(gen.shape)} and {tuple(table.shape)}")
+    rows, dim = gen.shape
+    if dim % 4:
+        raise ValueError(f"dim must be a multiple of 4 (the kernels read rows as float4), got {dim}")
+    if not 1 <= int(top_n) <= RANK_NMAX:
+        raise ValueError(f"top_n must be in 1 .. {RANK_NMAX}, got {top_n}")
+    top_n, dev = int(top_n), gen.device
+    flat, set_off, row_set, order = _candidate_sets(candidates, rows, table.shape[0])
+    if table_norms is None:
+        table_norms = embed_row_norms(table)
+    elif table_norms.shape != (table.shape[0],) or table_norms.device != dev or table_norms.dtype != torch.float32:
+        raise ValueError(f"table_norms must be embed_row_norms(table): fp32 [{table.shape[0]}] on {dev}")
+    ids = torch.empty((rows, top_n), dtype=torch.int64, device=dev)
+    pos, sims = torch.empty_like(ids), torch.empty((rows, top_n), dtype=torch.float32, device=dev)
+    counts = torch.empty((rows,), dtype=torch.int32, device=dev)
+    if rows == 0:
+        return RankResult(ids, pos, sims, counts)
+    flat = (flat if flat.numel() else torch.zeros(1, dtype=torch.int64)).to(dev).contiguous()
+    sorted_rows = order != list(range(rows))
+    order_t = torch.tensor(order, dtype=torch.int64, device=dev) if sorted_rows else None
+    gen_s = gen.index_select(0, order_t) if sorted_rows else gen            # rows grouped by set: a copy of rows, no arithmetic
+    gen_norms = embed_row_norms(gen_s)
+    row_set_s = [row_set[r] for r in order]
+    lens = [set_off[s + 1] - set_off[s] for s in row_set_s]
+    bands = _rank_bands(lens, int(workspace_cap))
+    lib = _lib.raw()
+    need = max(lib.dfh_embed_rank_workspace_bytes(b - a, max(lens[a:b]), top_n) for a, b in bands)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    c_off = (C.c_int64 * len(set_off))(*set_off)
+    out = (ids, pos, sims, counts) if not sorted_rows else (torch.empty_like(ids), torch.empty_like(pos), torch.empty_like(sims), torch.empty_like(counts))
+    with torch.cuda.device(dev):
+        for a, b in bands:
+            c_rows = (C.c_int * (b - a))(*row_set_s[a:b])
+            _lib.call("dfh_embed_rank", _lib.ptr(gen_s[a:]), _lib.ptr(gen_norms[a:]), b - a, dim, _lib.ptr(table), _lib.ptr(table_norms),
+                      table.shape[0], _lib.ptr(flat), c_off, len(set_off) - 1, c_rows, top_n, _lib.ptr(ws), ws.numel(), _lib.ptr(out[0][a:]),
+                      _lib.ptr(out[1][a:]), _lib.ptr(out[2][a:]), _lib.ptr(out[3][a:]), _lib.stream_ptr())
+    if sorted_rows:                                                        # back to the caller's row order
+        for dst, src in zip((ids, pos, sims, counts), out):
+            dst.index_copy_(0, order_t, src)
+    return RankResult(ids, pos, sims, counts)
+
+
+@torch.no_grad()
+def recall_at(ranked: RankResult, grds, cutoffs):
+    """``(hit_pos [rows] int32, hits)``: the first rank at which row r's list holds ``grds[r]`` (-1: nowhere), and per cutoff N the number
+    of rows with ``0 <= hit_pos < N`` -- the reference's ``grd in topN_iids[:N]`` (eval_utils.py:754-762) -- as Python ints."""
+    dev, rows = ranked.ids.device, ranked.ids.shape[0]
+    grd = (grds if isinstance(grds, torch.Tensor) else torch.as_tensor([int(g) for g in grds], dtype=torch.int64)).reshape(-1)
+    if grd.numel() != rows or grd.dtype not in _INT_DTYPES:
+        raise ValueError(f"grds must hold one integer id per row ({rows}), got {grd.numel()} of {grd.dtype}")
+    cuts = [int(c) for c in cutoffs]
+    if len(cuts) > 64:
+        raise ValueError(f"at most 64 cutoffs, got {len(cuts)}")
+    grd = grd.to(device=dev, dtype=torch.int64).contiguous()
+    hit_pos = torch.empty((rows,), dtype=torch.int32, device=dev)
+    hits = torch.zeros((len(cuts),), dtype=torch.int64, device=dev)
+    if rows:
+        cut_t = torch.tensor(cuts, dtype=torch.int32, device=dev) if cuts else None
+        with torch.cuda.device(dev):
+            _lib.call("dfh_embed_recall", _lib.ptr(ranked.ids), _lib.ptr(ranked.counts), rows, ranked.ids.shape[1], _lib.ptr(grd), _lib.ptr(cut_t),
+                      len(cuts), _lib.ptr(hit_pos), _lib.ptr(hits if cuts else None), _lib.stream_ptr())
+    return hit_pos, hits.tolist()
 
 
 @torch.no_grad()
@@ -320,10 +503,57 @@ class CLIPScore:
 
     @torch.no_grad()
     def retrieval(self, images: torch.Tensor, cnn_features: torch.Tensor, candidates: torch.Tensor, similarity_func: str = "cosine"):
-        """(sims [rows, K], preds [rows]) of ``calculate_clip_retrieval_acc_given_data2`` (eval_utils.py:702-715); the ranking of
-        ``clip_og_retrieval_given_data`` (:733-745) is a ``topk`` over the same sims."""
+        """(sims [rows, K], preds [rows]) of ``calculate_clip_retrieval_acc_given_data2`` (eval_utils.py:702-715): K candidates a row, the
+        best one.  The ranking of ``clip_og_retrieval_given_data`` (:733-750) -- a whole category per row, the best 100 in order -- is
+        ``grounding_retrieval`` below."""
         _require_cosine(similarity_func)
         return candidate_cosine(self.image_model.encode_image(images), cnn_features, candidates)
+
+    @torch.no_grad()
+    def grounding_retrieval_from_features(self, gen_feats: torch.Tensor, cnn_features: torch.Tensor, candidates, topN=(10, 20, 50, 100),
+                                          grds=None, table_norms: Optional[torch.Tensor] = None):
+        """``grounding_retrieval`` for a caller that holds the generated images' embeddings ``[rows, dim]`` already."""
+        cuts = [int(n) for n in topN]
+        if not cuts or any(n < 1 for n in cuts) or sorted(cuts) != cuts:
+            raise ValueError(f"topN must be ascending positive cutoffs, got {topN}")
+        ranked = rank_candidates(gen_feats, cnn_features, candidates, cuts[-1], table_norms)
+        all_recall = None
+        if grds is not None:
+            _, hits = recall_at(ranked, grds, cuts)
+            all_recall = [h / ranked.ids.shape[0] for h in hits]
+        return ranked.preds, all_recall, ranked
+
+    @torch.no_grad()
+    def grounding_retrieval(self, images, cnn_features: torch.Tensor, candidates, topN=(10, 20, 50, 100), grds=None, batch_size: int = 200,
+                            table_norms: Optional[torch.Tensor] = None, device=None):
+        """``clip_og_retrieval_given_data`` (eval_utils.py:725-767) for all images at once: ``encode_image`` in batches of ``batch_size``,
+        then ONE ranking of every row against its own candidate list at ``topN[-1]`` (at most 128) -> ``(preds [rows], all_recall,
+        ranked)``: the best id of each row (the "grounded" item), recall@N per cutoff as floats (None without ``grds``) and the
+        ``RankResult``.  ``images``: a tensor of preprocessed pixels or a list of per-image tensors, moved batch by batch to ``device``
+        (default: the image model's); ``candidates``: see ``rank_candidates``."""
+        dev = device if device is not None else getattr(self.image_model, "device", None)
+        feats = torch.cat([self.image_model.encode_image(b if dev is None else b.to(dev)) for b in _image_batches(images, batch_size, "images")])
+        return self.grounding_retrieval_from_features(feats, cnn_features, candidates, topN, grds, table_norms)
+
+
+@torch.no_grad()
+def clip_og_retrieval_given_data(gen4eval, grds, cnn_features, batch_size, topN, device=None, num_workers=1, similarity_func="cosine", *,
+                                 clip: CLIPScore):
+    """The reference's function under its own signature and return ``(preds, all_recall)`` (eval_utils.py:725-767).  ``gen4eval[i]`` is
+    ``(image, candidates)`` as ``FashionRetrievalDataset`` yields them; ``clip`` is the ``CLIPScore`` to use (the reference builds one
+    from OpenCLIP weights on every call).  ``num_workers`` is accepted and unused: nothing is loaded here."""
+    _require_cosine(similarity_func)
+    items = [gen4eval[i] for i in range(len(gen4eval))]
+    if not items:
+        raise ValueError("gen4eval holds no image")
+    if device is not None:
+        cnn_features = cnn_features.to(device)
+    preds, all_recall, _ = clip.grounding_retrieval([it[0] for it in items], cnn_features, [it[1] for it in items], topN, grds, batch_size,
+                                                    device=device)
+    return preds, all_recall
+
+
+clip_gor_retrieval_given_data = clip_og_retrieval_given_data      # the name Evaluation/evaluate_grounding_gor.py:255 calls
 
 
 # ------------------------------------------------------------------ FID and the Inception Score (DESIGN.md row f9; csrc/inception.hip)

@@ -290,6 +290,46 @@ int dfh_embed_pair_cosine(const float* a, const float* b, float* out, int rows, 
 int dfh_embed_candidates(const float* gen, const float* table, const int64_t* cand, float* sims, int64_t* pred, int rows, int K, int dim,
                          int table_rows, void* stream);
 
+/* Grounding retrieval (csrc/eval_rank.hip): the ranking of clip_og_retrieval_given_data (eval_utils.py:725-767, called
+ * by Evaluation/evaluate_grounding_gor.py:237-266) -- every generated row against ALL items of its category, the nmax best kept in
+ * order, then recall@N of the ground-truth item.  Candidate sets are ragged: a flat id list cut by offsets.  fp32 in both storage
+ * builds, no atomics, no allocation, no scratch; reruns are bit-identical and a row's result does not depend on the rows it rides with.
+ *
+ * norms[r] = |x_r| of x [rows][dim] fp32 (dim a multiple of 4, x 16-byte aligned), one wave a row.  A caller that ranks many batches
+ * against one table computes the table's norms once. */
+int dfh_embed_row_norms(const float* x, float* norms, int rows, int dim, void* stream);
+/* The largest top-N list a row keeps. */
+#define DFH_EMBED_RANK_NMAX 128
+/* Bytes of the similarity workspace of one dfh_embed_rank call: rows x (max_set_len rounded up to 64) floats + 256; 0 for arguments
+ * the call would refuse.  Host-only. */
+size_t dfh_embed_rank_workspace_bytes(int rows, long max_set_len, int nmax);
+/* For every row r, with S = row_set[r] and its candidates c_j = cand_ids[set_off[S] + j], j < len = set_off[S + 1] - set_off[S]:
+ *   sim_j = <gen_r, table[c_j]> / (|gen_r| |table[c_j]|)   on v_mfma_f32_16x16x4_f32: a 64 x 64 tile of rows THAT SHARE ONE SET by
+ *           candidates, the table rows gathered in the tile's loads, k-tiles of 32 summed with a compensated add; the similarities
+ *           of the call's rows are materialised in `workspace` ([rows][ld] floats) and read once by the selection;
+ *   out_ids / out_pos / out_sims [rows][nmax]: the best min(len, nmax) in order -- descending, a NaN above everything (torch.topk's
+ *           order), and among EQUAL values (-0.0 == +0.0, NaN == NaN for this purpose) the lower position j first -- as item id c_j
+ *           (int64), position j (int64) and similarity; slots from out_counts[r] = min(len, nmax) on hold id -1, position -1, sim -inf.
+ * A zero row (generated or table) gives NaN in its own similarities only.
+ *   gen [rows][dim], table [table_rows][dim] fp32, 16-byte aligned, dim a multiple of 4; gen_norms [rows], table_norms [table_rows]
+ *           from dfh_embed_row_norms;
+ *   cand_ids  : DEVICE int64 [set_off[nsets]].  Ids outside [0, table_rows) are CLAMPED before they address anything; refusing them,
+ *               as indexing does, is the caller's part (the ids live on the device: the Python side checks them where they live);
+ *   set_off   : HOST int64 [nsets + 1], monotone, from 0;  row_set: HOST int [rows], ascending (rows arrive grouped by set) -- both are
+ *               read before the launches: they are the launch geometry (one GEMM and one selection launch per run of equal row_set);
+ *   nmax      : 1 .. DFH_EMBED_RANK_NMAX;
+ *   workspace : >= dfh_embed_rank_workspace_bytes(rows, longest set of these rows, nmax), 256-byte aligned.  A caller bounds it by
+ *               ranking its rows in bands; the result does not depend on the cut. */
+int dfh_embed_rank(const float* gen, const float* gen_norms, int rows, int dim, const float* table, const float* table_norms, int table_rows,
+                   const int64_t* cand_ids, const int64_t* set_off, int nsets, const int* row_set, int nmax, void* workspace,
+                   size_t workspace_bytes, int64_t* out_ids, int64_t* out_pos, float* out_sims, int* out_counts, void* stream);
+/* hit_pos[r] = the first rank j < counts[r] with ids[r][j] == grd[r], -1 if none (the reference's `grd in topN_iids[:N]` is
+ * 0 <= hit_pos[r] < N); hits[c] = #{r : 0 <= hit_pos[r] < cutoffs[c]} from one workgroup's integer reduction.
+ * ids [rows][nmax] int64, counts [rows] int, grd [rows] int64, cutoffs [ncut] int (ncut <= 64; 0: hit_pos only), hit_pos [rows] int,
+ * hits [ncut] int64 -- all on the device. */
+int dfh_embed_recall(const int64_t* ids, const int* counts, int rows, int nmax, const int64_t* grd, const int* cutoffs, int ncut, int* hit_pos,
+                     int64_t* hits, void* stream);
+
 /* The compatibility scorer: FashionEvaluator (Evaluation/compatibility_evaluator/compatibility_net.py:14-81) under the gather of
  * CompatibilityEvaluator.evaluate_compatibility (eval_utils.py:574-588), all outfits of a call at once.  Inference: Dropout is the
  * identity.  Linears on v_mfma_f32_16x16x4_f32, LayerNorm + ReLU fused per row.
