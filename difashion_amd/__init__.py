@@ -26,6 +26,7 @@ from .evalscores import (activation_statistics, fid_given_data, frechet_distance
                          inception_score_given_data)
 from .inception import FIDInceptionV3, InceptionV3
 from .difashion import DiFashion
+from .itemstore import HistoryTable, ItemLatentStore
 
 __all__ = [
     "DfhError", "set_storage", "storage", "UNet2DConditionModel", "UNet2DConditionOutput", "DDIMScheduler", "PNDMScheduler",
@@ -38,4 +39,5 @@ __all__ = [
     "RankResult", "rank_candidates", "embed_row_norms", "recall_at", "clip_og_retrieval_given_data", "clip_gor_retrieval_given_data",
     "FIDInceptionV3", "InceptionV3", "activation_statistics", "frechet_distance", "fid_given_data", "inception_rows",
     "inception_score_from_probs", "inception_score_given_data",
+    "ItemLatentStore", "HistoryTable",
 ]

@@ -213,6 +213,8 @@ SIGNATURES = {
     "dfh_embed_rank_workspace_bytes": (_sz, [_i, C.c_long, _i]),
     "dfh_embed_rank": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "dfh_embed_recall": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "dfh_item_gather": (_i, [_vp, C.c_long, C.c_long, _i, _vp, C.c_long, _vp, _f, _vp, _vp]),
+    "dfh_history_rows": (_i, [_vp, C.c_long, C.c_long, _i, _vp, _vp, _vp, C.c_long, _vp, _f, _vp, _vp]),
     "dfh_compat_workspace_bytes": (_sz, [_i, _i, _i]),
     "dfh_compat_score": (_i, [C.POINTER(_vp), _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "dfh_compat_pred_score": (_i, [C.POINTER(_vp), _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),

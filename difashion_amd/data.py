@@ -60,6 +60,20 @@ def history_latents(all_latents: torch.Tensor, history: Dict) -> Dict:
     return hist
 
 
+def build_item_store(vae, img_dataset, device, batch_size: int = 64):
+    """Every item image -> its VAE posterior ``[mean | std]``, kept on the device (``itemstore.ItemLatentStore``): what
+    ``encode_item_latents`` does, without the trip to the host and with the std, so training can ``sample`` from it."""
+    from .itemstore import ItemLatentStore
+    return ItemLatentStore.build(vae, img_dataset, device, batch_size=batch_size)
+
+
+def history_table(store, history: Dict):
+    """The raw ``history`` dict (``uid -> category -> [iids]``) as an ``itemstore.HistoryTable`` over ``store``: what
+    ``history_latents`` pre-averages on the host, averaged per step on the device from the item table."""
+    from .itemstore import HistoryTable
+    return HistoryTable(history, store)
+
+
 def preprocess_dataset(data, data_path, id_cate_dict, history, img_dataset, tokenizer, vae, device):
     data["input_ids"] = tokenize_categories(data["category"], id_cate_dict, tokenizer)
     cache = os.path.join(data_path, "all_item_latents.npy")

@@ -4,6 +4,8 @@
     = the training loss (difashion.py:122-267): VAE-encode the outfit images, draw noise / timesteps, select the history
     latents, then ONE call of the fused ``pipeline.train_forward`` (sibling mean, MutualEncoder, condition masks, input
     assembly, U-Net, min-SNR loss -- with the native backward behind ``loss.backward()``);
+    ``img_dataset`` may be an ``itemstore.ItemLatentStore`` (cached posteriors: no encoder pass) and ``history`` an
+    ``itemstore.HistoryTable``, independently of each other; with a store ``null_img=None`` means item 0 (DESIGN.md 4.4d);
   * ``fashion_generation(...)`` = the guided sampler (difashion.py:277-616): resolve the blank slots, history rows and
     prompts, then the fused ``pipeline.sample_outfits`` loop and the VAE decode.
 
@@ -21,6 +23,7 @@ from typing import Callable, Optional
 import torch
 import torch.nn as nn
 
+from .itemstore import HistoryTable, ItemLatentStore
 from .pipeline import sample_outfits, train_forward
 
 
@@ -111,7 +114,18 @@ class DiFashion(nn.Module):
         ids = self.tokenizer([""], padding="max_length", max_length=length, truncation=True, return_tensors="pt").input_ids
         return self.text_encoder(ids.to(self.device))[0]
 
+    def _null_latent(self, null_img, store, dtype=None):
+        # a tensor ``null_img`` is encoded, as ever; ``None`` with an item store means item 0 (``null_img = img_dataset[0]`` there)
+        if null_img is None:
+            if store is None:
+                raise ValueError("null_img=None needs an ItemLatentStore: its item 0 is the null image")
+            return store.null_latent()
+        null_img = null_img.unsqueeze(0).to(self.device) if dtype is None else null_img.unsqueeze(0).to(self.device, dtype)
+        return self.vae.encode(null_img).latent_dist.mode()[0] * self.vae.config.scaling_factor
+
     def _history_rows(self, uids_of_rows, cates, history, null_latent, use_history):
+        if isinstance(history, HistoryTable):         # keys by integer value, one launch over the item table (itemstore.py)
+            return history.rows(uids_of_rows, cates, null_latent, use_history)
         # the reference's literal membership test (``cate in history[uid]`` with a 0-d tensor ``cate``), so containers that
         # hash tensors by identity fall back to the null latent exactly as they do there
         rows = []
@@ -124,10 +138,14 @@ class DiFashion(nn.Module):
                 weight_dtype=torch.float32, generator=None, taps: Optional[dict] = None):
         uids, outfits, category, input_ids = batch["uids"], batch["outfits"], batch["category"], batch["input_ids"]
         sf = self.vae.config.scaling_factor
-        null_latent = self.vae.encode(null_img.unsqueeze(0).to(self.device, weight_dtype)).latent_dist.mode()[0] * sf
+        store = img_dataset if isinstance(img_dataset, ItemLatentStore) else None
+        null_latent = self._null_latent(null_img, store, weight_dtype)
         bsz, olen = len(uids), len(outfits[0])
-        images = torch.stack([img_dataset[int(iid)] for i in range(bsz) for iid in outfits[i]]).to(self.device)
-        latents = self.vae.encode(images.to(weight_dtype)).latent_dist.sample() * sf
+        if store is not None:                         # the cached posteriors: the same draw at the same place of the RNG stream
+            latents = store.sample(torch.stack([torch.as_tensor(outfits[i]) for i in range(bsz)]).reshape(-1))
+        else:
+            images = torch.stack([img_dataset[int(iid)] for i in range(bsz) for iid in outfits[i]]).to(self.device)
+            latents = self.vae.encode(images.to(weight_dtype)).latent_dist.sample() * sf
         noise = self._randn_like(latents)
         if getattr(self.args, "noise_offset", 0):
             noise = noise + self.args.noise_offset * torch.randn((latents.shape[0], latents.shape[1], 1, 1), device=latents.device)
@@ -158,7 +176,7 @@ class DiFashion(nn.Module):
                            height=None, width=None, num_inference_steps: int = 50, category_guidance_scale: float = 7.5,
                            hist_guidance_scale: float = 7.5, mutual_guidance_scale: float = 7.5, null_img=None, eta: float = 0.0,
                            init_latents=None, generator=None, output_type: Optional[str] = "pil", return_dict: bool = True,
-                           callback: Optional[Callable] = None, callback_steps: int = 1):
+                           callback: Optional[Callable] = None, callback_steps: int = 1, item_store: Optional[ItemLatentStore] = None):
         dev = self.device
         S = self.unet.config.sample_size
         sf = self.vae.config.scaling_factor
@@ -177,11 +195,14 @@ class DiFashion(nn.Module):
             init_latents = torch.randn((fill_num, self.vae.config.latent_channels, lh, lw), generator=generator,
                                        device=dev if generator is None or generator.device.type != "cpu" else "cpu").to(dev)
             init_latents = init_latents * self.noise_scheduler.init_noise_sigma
-        null_latent = self.vae.encode(null_img.unsqueeze(0).to(dev)).latent_dist.mode()[0] * sf
+        null_latent = self._null_latent(null_img, item_store)
         hist = self._history_rows([uids[fill_idx[i][0]].item() for i in range(fill_num)], list(fill_cate), history, null_latent,
                                   self.args.use_history)
-        imgs = outfit_images.to(dev)
-        all_latents = self.vae.encode(imgs.reshape((-1,) + tuple(imgs.shape[-3:]))).latent_dist.mode() * sf
+        if item_store is not None:                    # ``outfit_images`` may be None: the outfits' items are rows of the store
+            all_latents = item_store.modes(olists.reshape(-1))
+        else:
+            imgs = outfit_images.to(dev)
+            all_latents = self.vae.encode(imgs.reshape((-1,) + tuple(imgs.shape[-3:]))).latent_dist.mode() * sf
         cb = (lambda i, t, lat: callback(i, t, lat) if i % callback_steps == 0 else None) if callback is not None else None
         latents = sample_outfits(self.unet, self.fashion_encoder, self.noise_scheduler, olists=olists, all_latents=all_latents.float(),
                                  init_latents=init_latents.float(), hist_latents=hist.float(), null_latent=null_latent.float(),

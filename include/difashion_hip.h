@@ -330,6 +330,31 @@ int dfh_embed_rank(const float* gen, const float* gen_norms, int rows, int dim, 
 int dfh_embed_recall(const int64_t* ids, const int* counts, int rows, int nmax, const int64_t* grd, const int* cutoffs, int ncut, int* hit_pos,
                      int64_t* hits, void* stream);
 
+/* ------------------------------------------------------------------ the device-resident item store
+ * csrc/item_store.hip.  The VAE posterior of every item is computed once and kept as one fp32 table row [mean | std] (row_stride
+ * floats apart, row_elems = C x H x W each half); the model's inputs are then row gathers.  fp32 in both storage builds and compiled
+ * without mul+add contraction: every result below is the stated chain of separate IEEE fp32 operations.  No atomics, nothing
+ * allocated, no scratch, no workspace, one launch each.  A lane owns one float4 of the output row; the grid is (row, 1024-float slab).
+ * All row offsets are 64-bit.  Refused on the host, by message, before any HIP call: null pointers, row_elems or row_stride not a
+ * multiple of 4, row_stride < row_elems, a pointer that is not 16-byte aligned, negative counts.  rows == 0 is a no-op.
+ *
+ * out[r][j] = (table[iid_r][j] + table[iid_r][row_elems + j] * eps[r][j]) * scale: `latent_dist.sample() * scaling_factor` with the
+ * caller's eps.  eps == NULL: out[r][j] = table[iid_r][j] * scale, `latent_dist.mode() * scaling_factor`; the std half is then never
+ * read, so a means-only table (row_stride == row_elems) is legal -- with eps, row_stride < 2 * row_elems is refused.
+ *   table [table_rows][row_stride] fp32; iids [rows] int64 ON THE DEVICE; eps, out [rows][row_elems] fp32.
+ * An id outside [0, table_rows) writes a row of NaN and reads nothing (the ids live on the device: no sync for a check). */
+int dfh_item_gather(const float* table, long table_rows, long row_stride, int row_elems, const int64_t* iids, long rows, const float* eps,
+                    float scale, float* out, void* stream);
+/* The history condition (data_utils.py:142-155: the mean latent of a user's history items of one category) from the item table itself.
+ * Row r with segment s = row_seg[r], items i_k = seg_items[seg_offsets[s] + k], k < count = seg_offsets[s + 1] - seg_offsets[s]:
+ *   acc = 0;  for k in list order: t_k = table[i_k][j] * scale (rounded), acc = acc + t_k (rounded);  out[r][j] = acc / (float)count
+ * -- one accumulator, one IEEE division; at least four item loads in flight per lane, the adds still in list order.  A row with
+ * row_seg[r] == -1 or an empty segment copies null_row [row_elems].  Only the first row_elems floats of a table row are read.
+ *   seg_items int64, seg_offsets int64 [S + 1], row_seg int32 [rows]: all ON THE DEVICE; row_seg < S is the caller's part.  An item id
+ *   outside [0, table_rows) adds NaN and reads nothing. */
+int dfh_history_rows(const float* table, long table_rows, long row_stride, int row_elems, const int64_t* seg_items, const int64_t* seg_offsets,
+                     const int* row_seg, long rows, const float* null_row, float scale, float* out, void* stream);
+
 /* The compatibility scorer: FashionEvaluator (Evaluation/compatibility_evaluator/compatibility_net.py:14-81) under the gather of
  * CompatibilityEvaluator.evaluate_compatibility (eval_utils.py:574-588), all outfits of a call at once.  Inference: Dropout is the
  * identity.  Linears on v_mfma_f32_16x16x4_f32, LayerNorm + ReLU fused per row.
