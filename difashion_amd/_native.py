@@ -1,5 +1,6 @@
-"""What the native-backed model wrappers (unet.py, vae.py, clip.py, clip_vision.py; the checkpoint part also mutual.py) share: the
-Python counterpart of csrc/walk_common.h, and of csrc/clip_tower.h for the two CLIP towers (``ClipTower``, ``TupleOutput``).
+"""What the native-backed model wrappers (unet.py, vae.py, clip.py, clip_vision.py, lpips.py, inception.py; the checkpoint part also
+mutual.py) share: the Python counterpart of csrc/walk_common.h, of csrc/clip_tower.h for the two CLIP towers (``ClipTower``,
+``TupleOutput``), and the base of the models that run on a packed copy of their parameters (``PackedModule``: LPIPS, Inception v3).
 
 ``NativeModule`` drives one family of C entry points (``dfh_<family>_create / _destroy / _num_params / _param_name / _param_ndim /
 _param_dim``): handle lifecycle, the parameter tree built from the C table, the table-ordered parameter list, the pack signature and
@@ -67,6 +68,20 @@ def grow_buffer(holder, attr: str, nbytes: int, dev: torch.device) -> torch.Tens
         buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         setattr(holder, attr, buf)
     return buf
+
+
+def current_packed_copy(module, fam: str, plist, arr, dev: torch.device) -> torch.Tensor:
+    """The device block ``module._packed`` holding a packed copy of ``plist`` that is current: ``<fam>_pack`` runs when the block is new
+    (it holds no copy yet) or when a parameter was written, replaced or moved since the last pack (the pack signature)."""
+    old = module._packed
+    packed = grow_buffer(module, "_packed", getattr(_lib.raw(), fam + "_packed_bytes")(module._ctx), dev)
+    if packed is not old:
+        module._packed_sig = None
+    sig = pack_signature(plist)
+    if sig != module._packed_sig:
+        _lib.call(fam + "_pack", module._ctx, arr, len(plist), _lib.ptr(packed), _lib.stream_ptr())
+        module._packed_sig = sig
+    return packed
 
 
 def require_params_on(dev: torch.device, params) -> None:
@@ -324,14 +339,8 @@ class ClipTower(NativeModule):
         grow_buffer(self, "_ws", need, dev)
         plist = self._plist()
         require_params_on(dev, plist)
-        packed = self._packed
-        grow_buffer(self, "_packed", getattr(_lib.raw(), fam + "_packed_bytes")(self._ctx), dev)
-        if self._packed is not packed:
-            self._packed_sig = None                      # a new block holds no packed copy yet
-        arr, sig = self._pointers(plist), self._signature(plist)
-        if sig != self._packed_sig:
-            _lib.call(fam + "_pack", self._ctx, arr, len(plist), _lib.ptr(self._packed), _lib.stream_ptr())
-            self._packed_sig = sig
+        arr = self._pointers(plist)
+        current_packed_copy(self, fam, plist, arr, dev)
         return arr, len(plist)
 
     # ------------------------------------------------------------------ checkpoints (transformers directory layout)
@@ -350,3 +359,66 @@ class ClipTower(NativeModule):
         model = cls(init_seed=None, **cfg)
         model.load_state_dict(load_weights(d, variant, TRANSFORMERS_STEMS))
         return model if torch_dtype is None else model.set_compute_dtype(torch_dtype)
+
+
+class PackedModule(NativeModule):
+    """What the inference-only models that run on a packed copy of their parameters share (LPIPS, the two Inception variants): the
+    growable blocks ``_ws`` (the workspace of one call) and ``_packed`` (held across calls), ``_prepare``, the ``max_workspace_bytes``
+    limit, the refusal to train, the checkpoint directory and the checks of an image batch.  A subclass supplies ``family``,
+    ``_c_config()``, ``_inference_only`` and, where its constructor needs them, ``_from_pretrained_kw``."""
+    weights_name = "model.safetensors"
+    _inference_only = ""                 # the sentence train(True) is refused with; {name}: the class
+    _from_pretrained_kw: dict = {}       # what from_pretrained passes the constructor besides init_seed=None and the saved config
+    _ws = _packed = None
+
+    def _set_workspace_limit(self, max_workspace_bytes: int):
+        if max_workspace_bytes < 1:
+            raise ValueError(f"max_workspace_bytes must be positive, got {max_workspace_bytes}")
+        self.max_workspace_bytes = int(max_workspace_bytes)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise NotImplementedError(self._inference_only.format(name=type(self).__name__))
+        return super().train(False)
+
+    def save_pretrained(self, save_directory: str, **unused):
+        save_checkpoint(self, save_directory, dict(architectures=[type(self).__name__]))
+
+    @classmethod
+    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, **kw):
+        from ._ckpt import load_weights
+        d, cfg = read_checkpoint_config(cls, path, subfolder)
+        cfg.pop("architectures", None)
+        model = cls(init_seed=None, **cls._from_pretrained_kw, **cfg, **kw)
+        model.load_state_dict(load_weights(d, variant, ("model",)))
+        return model
+
+    def _context(self):
+        if self._ctx is None:
+            self._ctx = self._make_ctx()
+        return self._ctx
+
+    def _prepare(self, dev: torch.device):
+        """Context, checked parameters and a current packed copy -> (pointer array, count, packed)."""
+        self._context()
+        plist = self._plist()
+        require_params_on(dev, plist)
+        arr = self._pointers(plist)
+        return arr, len(plist), current_packed_copy(self, f"dfh_{self.family}", plist, arr, dev)
+
+    def _workspace(self, dev: torch.device, *batch_args) -> torch.Tensor:
+        """``_ws`` grown to ``dfh_<family>_workspace_bytes(ctx, *batch_args)``."""
+        return grow_buffer(self, "_ws", self._entry("workspace_bytes")(self._ctx, *batch_args), dev)
+
+    @staticmethod
+    def _chunk(x: torch.Tensor, i: int, n: int) -> torch.Tensor:
+        """Rows ``i .. i + n`` of a batch as the kernels read them: contiguous and 16-byte aligned."""
+        a = x[i:i + n].contiguous()
+        return a.clone() if a.data_ptr() % 16 else a       # a slice of a batch of odd-sized images
+
+    def _check_images(self, x, dev: torch.device, other_form: str = "", in_other_form: bool = False):
+        """``x`` lives on the model's device ``dev`` and is fp32 ``[N, 3, H, W]`` (or in the caller's ``other_form``)."""
+        if x.device != dev:
+            raise _lib.DfhError(f"the images live on {x.device}, the model on {dev}: move them to the model's device (no CPU fallback)")
+        if not in_other_form and (x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3):
+            raise TypeError(f"images must be float32 [N, 3, H, W]{other_form}, got {x.dtype} {tuple(x.shape)}")

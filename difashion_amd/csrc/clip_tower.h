@@ -7,13 +7,9 @@
 
 namespace dfh {
 
-// what an encode entry point requires of master_params; the kernels read every parameter as float4.  family: "dfh_clip" / "dfh_clipv"
+// what an encode entry point requires of master_params (dfh_common.h require_params).  family: "dfh_clip" / "dfh_clipv"
 inline int require_params(const ParamList& t, const float* const* master_params, int count, const std::string& family) {
-  if (count != t.num_params()) {
-    set_error(family + "_encode: master_params count does not match " + family + "_num_params");
-    return -1;
-  }
-  return check_param_pointers(master_params, count, family + "_encode", [&](int i) { return ": " + t.params[i].name; });
+  return require_params(t, master_params, count, family + "_encode", family + "_num_params", "master_params");
 }
 
 // table indices of one CLIPEncoderLayer

@@ -291,6 +291,15 @@ int check_param_pointers(const float* const* params, int count, const std::strin
   }
   return 0;
 }
+// What every entry point that takes the parameter table `t` of a model requires of it.  who: the entry point; count_query: how the
+// message names the count query ("dfh_lpips_num_params (33)"); arg: what the entry point calls the table
+inline int require_params(const ParamList& t, const float* const* params, int count, const std::string& who, const std::string& count_query,
+                          const std::string& arg = "params") {
+  if (!params) { set_error(who + ": null argument: " + arg); return -1; }
+  if (count != t.num_params()) { set_error(who + ": " + arg + " count does not match " + count_query); return -1; }
+  return check_param_pointers(params, count, who, [&](int i) { return ": " + t.params[i].name; });
+}
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }      // what a pointer the kernels read as float4 must be
 // Optional per-launch timing with HIP events recorded on the launch stream (bench.py roofline).
 enum ProfClass { PC_CONV3 = 0, PC_LINEAR = 1, PC_ATTN = 2, PC_GNORM = 3, PC_LNORM = 4, PC_SPLITK = 5, PC_OTHER = 6,
                  PC_WGRAD = 7, PC_ATTN_BWD = 8, PC_NORM_BWD = 9, PC_OPTIM = 10, PC_LINEAR_FP8 = 11, PC_COUNT = 12 };

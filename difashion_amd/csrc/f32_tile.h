@@ -1,8 +1,10 @@
 // The fp32 matrix steps of the evaluation rows on v_mfma_f32_16x16x4_f32, stated once (device code only): the k-tile step over a
-// k-major LDS image (mma_ktile), the two ways of summing k-tiles (ChainSum, TileKahanSum: DESIGN.md 4.4), the 64 x 64 tile that the
-// CLIP towers' and the compatibility scorer's Linears run (gemm_tile) and the one-wave-a-row LayerNorm (layernorm_row).
+// k-major LDS image (mma_ktile), the two ways of summing k-tiles (ChainSum, TileKahanSum: DESIGN.md 4.4), the walk of one 64 x 64 tile
+// with the caller's A rows and epilogue (tile_walk: the Inception convolution), its dense-row, + bias form that the CLIP towers', the
+// compatibility scorer's, the ranking's and the Inception classifier's Linears run (gemm_tile), the one-wave-a-row LayerNorm (layernorm_row) and the max-pool update of the two convnets (pool_max).
 // Users: clip.hip (clip_gemm_f32_kernel, clip_layernorm_kernel), eval_scores.hip (compat_gemm_f32_kernel, compat_ln_relu_kernel),
-// lpips.hip (lpips_conv3x3_relu_kernel, lpips_finish_kernel).  fp32 in both storage builds; whether a * b + c contracts is the
+// eval_rank.hip (the ranking GEMM), lpips.hip (lpips_conv3x3_relu_kernel, lpips_finish_kernel, lpips_maxpool2x2_kernel),
+// inception.hip (incep_conv_kernel: the im2col use of tile_walk; incep_fc_kernel, incep_pool_kernel).  fp32 in both storage builds; whether a * b + c contracts is the
 // including file's -ffp-contract setting (Makefile), nothing here sets it.
 #pragma once
 #include "dfh_common.h"
@@ -17,6 +19,9 @@ DFH_DEVICE void kahan_add(T& sum, T& comp, const T x) {
   comp = (s - sum) - y;
   sum = s;
 }
+
+// torch's max-pool update: a NaN wins and stays
+DFH_DEVICE float pool_max(float m, float v) { return (v > m || v != v) ? v : m; }
 
 // KT k-rows of a k-major LDS image pair: per k-quad q the lane reads MF A and NF B fragment values at k-row 4 q + fk and issues
 // MF x NF MFMAs into accumulator set q % NACC.  a / b: the lane's element of the first fragment at k-row 0; rows a_ld / b_ld floats
@@ -80,6 +85,75 @@ struct TileKahanSum {
   DFH_DEVICE float at(int i, int j, int r) const { return sum[0][i][j][r]; }
 };
 
+// The walk of one workgroup's tile (256 threads) whose origin is (m0, n0), stated once: two k-major LDS images, staging thread ->
+// (row tile_stage_row(), k-quads tid / 64 and tid / 64 + 4), the next k-tile's global loads issued before the current tile's MFMAs
+// (register prefetch), the k-tiles summed under Sum, and the walk over the C layout.  K is a multiple of 4.  The caller supplies
+//   a_quad(k)  : the four A values at k .. k + 3 of ITS staging row (called for k < K only; beyond K the image holds zeros);
+//   w_row      : the W row of its staging row, 16-byte aligned (read for k < K);
+//   column(n)  : what the epilogue needs of column n < N, read once a column;
+//   store(m, n, sum, column value) for every element with m < M, n < N.
+// Which row a staging row beyond M / N reads is the caller's choice (the GEMMs and the conv clamp to the last one): such rows are
+// never stored.  Row: the type of a row index (int for the GEMMs, long for the conv, whose rows are the pixels of a batch).
+DFH_DEVICE int tile_stage_row() { return threadIdx.x & 63; }
+
+template <class Sum, class Row, class AQuad, class Column, class Store>
+DFH_DEVICE void tile_walk(Row m0, int n0, Row M, int N, int K, const float* __restrict__ w_row, AQuad a_quad, Column column, Store store) {
+  __shared__ float As[GT_K * GT_LD];
+  __shared__ float Ws[GT_K * GT_LD];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  const int srow = tile_stage_row(), sq = tid >> 6;
+  float4 ra[2], rw[2];
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int k = k0 + (sq + 4 * j) * 4;
+      ra[j] = rw[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (k < K) {
+        rw[j] = *(const float4*)(w_row + k);
+        ra[j] = a_quad(k);
+      }
+    }
+  };
+  auto stash = [&]() {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int kk = (sq + 4 * j) * 4;
+      As[(kk + 0) * GT_LD + srow] = ra[j].x; As[(kk + 1) * GT_LD + srow] = ra[j].y;
+      As[(kk + 2) * GT_LD + srow] = ra[j].z; As[(kk + 3) * GT_LD + srow] = ra[j].w;
+      Ws[(kk + 0) * GT_LD + srow] = rw[j].x; Ws[(kk + 1) * GT_LD + srow] = rw[j].y;
+      Ws[(kk + 2) * GT_LD + srow] = rw[j].z; Ws[(kk + 3) * GT_LD + srow] = rw[j].w;
+    }
+  };
+  Sum sum;
+  const int fr = lane & 15, fk = lane >> 4;
+  fetch(0);
+  for (int k0 = 0; k0 < K; k0 += GT_K) {
+    __syncthreads();                       // the previous tile's fragment reads are done
+    stash();
+    __syncthreads();
+    if (k0 + GT_K < K) fetch(k0 + GT_K);
+    sum.tile(As + wm + fr, Ws + wn + fr, fk);
+  }
+  // C layout of 16x16x4: acc[r] = C[4 * (lane / 16) + r][lane % 16]
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int n = n0 + wn + 16 * j + fr;
+      if (n >= N) continue;
+      const auto cv = column(n);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const Row m = m0 + wm + 16 * i + 4 * fk + r;
+        if (m < M) store(m, n, sum.at(i, j, r), cv);
+      }
+    }
+}
+
+// gemm_tile is the dense-row, + bias form of the same walk and keeps a body of its own: written as a call of tile_walk its users measured
+// 0.4 - 2.2 % slower on an MI355X under both formulations of the fetch that were tried (profiles/eval_tile_walk/bench_ab.txt, DESIGN.md
+// 4.4), so the two bodies below and above must be changed together: same LDS images, staging, k loop and C-layout walk.
 // One workgroup's tile (blockIdx.x: N tile, blockIdx.y: M tile; 256 threads): A rows lda floats apart, W [N][K] rows ldw apart, K a
 // multiple of 4, rows 16-byte aligned.  The next k-tile's global loads are issued before the current tile's MFMAs (register prefetch);
 // rows beyond M / N read the last row and are never stored.  store(m, n, value) is called for every in-range element with

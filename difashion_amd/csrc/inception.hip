@@ -6,16 +6,17 @@
 //   * every BasicConv2d (conv without bias -> BatchNorm2d(eps 1e-3, running statistics) -> ReLU), whatever its filter, stride and
 //     padding: ONE implicit GEMM on v_mfma_f32_16x16x4_f32 (incep_conv_kernel), rows = output pixels of the whole batch, K = taps x input
 //     channels, BatchNorm as a per-channel scale / shift in the epilogue, written into a channel slice of the block's concatenation;
-//   * the four 3 x 3 pools (incep_pool_kernel) and the global spatial mean (incep_gmean_kernel);
+//   * the four 3 x 3 pools (incep_pool_kernel) and the global spatial mean (incep_mean_kernel<float>);
 //   * fc + softmax (incep_fc_kernel over gemm_tile, incep_softmax_kernel), the per-image terms of the customised Inception Score
 //     (incep_is_rows_kernel) and its split means (incep_is_splits_kernel);
-//   * np.mean / np.cov of the float64 copy of the activations on v_mfma_f64_16x16x4_f64 (incep_colmean_kernel, incep_cov_kernel).
+//   * np.mean / np.cov of the float64 copy of the activations on v_mfma_f64_16x16x4_f64 (incep_mean_kernel<double>, incep_cov_kernel).
 //
 // Activations are NHWC fp32; fp32 (statistics: fp64) only, the same in both storage builds; no atomics; nothing is allocated here.  Every
 // per-image value is a function of its image alone: an output element's products are summed in an order that depends on the layer only.
 //
-// Accumulation contract of the conv: K is walked in k-tiles of 32 (k = tap * C_in + channel); each tile is summed in fresh accumulators
-// and added to the running sum with a compensated add (f32_tile.h TileKahanSum), so the rounding error does not grow with K.
+// Accumulation contract of the conv: K is walked in k-tiles of 32 (k = tap * C_in + channel) by the tile walk of f32_tile.h (tile_walk);
+// each tile is summed in fresh accumulators and added to the running sum with a compensated add (TileKahanSum), so the rounding error
+// does not grow with K.
 //
 // The host side plans the whole walk in one pure function (build_plan): a list of launches with kind, geometry, source / destination
 // region, ldc and channel offset.  dfh_incep_forward runs exactly that list; dfh_incep_plan_* show it without a GPU.
@@ -111,24 +112,19 @@ __global__ __launch_bounds__(THREADS) void incep_pack_conv_kernel(const float* _
 }
 
 // ------------------------------------------------------------------ out slice = relu(conv(x) * scale + shift), NHWC fp32
-// The 64 x 64 tile of f32_tile.h (four waves, 32 x 32 each, k-tiles of 32 in k-major LDS images) with the A operand gathered from the
-// image: row m = output pixel (img, oy, ox) of the whole batch, k = tap * C_in + channel.  blockIdx.x = (M tile, N tile), the N tile fastest.
+// The im2col use of the tile walk of f32_tile.h (tile_walk under TileKahanSum): row m = output pixel (img, oy, ox) of the whole batch
+// (64-bit), k = tap * C_in + channel, the A quad of a row gathered from the image (zeros outside it and for rows beyond M), the epilogue
+// BatchNorm's scale / shift and ReLU into a channel slice.  blockIdx.x = (M tile, N tile), the N tile fastest.
 struct ConvGeom { int H, W, C_in, OH, OW, C_out, KW, stride, padH, padW, ldc, offset, K; long M; };
 
 __global__ __launch_bounds__(THREADS) void incep_conv_kernel(const float* __restrict__ x, const float* __restrict__ wp, const float* __restrict__ scale,
                                                              const float* __restrict__ shift, float* __restrict__ out, const ConvGeom g) {
   using namespace dfh;
-  __shared__ float As[GT_K * GT_LD];
-  __shared__ float Ws[GT_K * GT_LD];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ntn = (g.C_out + GT_N - 1) / GT_N;
   const long mt = blockIdx.x / ntn;
   const int n0 = (int)(blockIdx.x - mt * ntn) * GT_N;
   const long m0 = mt * GT_M;
-  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
-  // staging: thread -> (row = tid % 64, k-quads tid / 64 and tid / 64 + 4)
-  const int srow = tid & 63, sq = tid >> 6;
-  const long m = m0 + srow;
+  const long m = m0 + tile_stage_row();
   const bool row_ok = m < g.M;
   const long mm = row_ok ? m : g.M - 1;
   const long ohw = (long)g.OH * g.OW;
@@ -137,63 +133,25 @@ __global__ __launch_bounds__(THREADS) void incep_conv_kernel(const float* __rest
   const int oy = rem / g.OW, ox = rem - oy * g.OW;
   const int iy0 = oy * g.stride - g.padH, ix0 = ox * g.stride - g.padW;
   const float* xin = x + img * (long)g.H * g.W * g.C_in;
-  const float* wrow = wp + (long)min(n0 + srow, g.C_out - 1) * g.K;
-  float4 ra[2], rw[2];
-  auto fetch = [&](int k0) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int k = k0 + (sq + 4 * j) * 4;
-      ra[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-      rw[j] = ra[j];
-      if (k < g.K) {
-        rw[j] = *(const float4*)(wrow + k);
+  float* slice = out + g.offset;
+  const long ldc = g.ldc;
+  tile_walk<TileKahanSum>(
+      m0, n0, g.M, g.C_out, g.K, wp + (long)min(n0 + tile_stage_row(), g.C_out - 1) * g.K,
+      [&](int k) {
         const int tap = k / g.C_in, c = k - tap * g.C_in;
         const int ky = tap / g.KW, kx = tap - ky * g.KW;
         const int iy = iy0 + ky, ix = ix0 + kx;
-        if (row_ok && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) ra[j] = *(const float4*)(xin + ((long)iy * g.W + ix) * g.C_in + c);
-      }
-    }
-  };
-  auto stash = [&]() {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int kk = (sq + 4 * j) * 4;
-      As[(kk + 0) * GT_LD + srow] = ra[j].x; As[(kk + 1) * GT_LD + srow] = ra[j].y;
-      As[(kk + 2) * GT_LD + srow] = ra[j].z; As[(kk + 3) * GT_LD + srow] = ra[j].w;
-      Ws[(kk + 0) * GT_LD + srow] = rw[j].x; Ws[(kk + 1) * GT_LD + srow] = rw[j].y;
-      Ws[(kk + 2) * GT_LD + srow] = rw[j].z; Ws[(kk + 3) * GT_LD + srow] = rw[j].w;
-    }
-  };
-  TileKahanSum sum;
-  const int fr = lane & 15, fk = lane >> 4;
-  fetch(0);
-  for (int k0 = 0; k0 < g.K; k0 += GT_K) {
-    __syncthreads();                       // the previous tile's fragment reads are done
-    stash();
-    __syncthreads();
-    if (k0 + GT_K < g.K) fetch(k0 + GT_K);
-    sum.tile(As + wm + fr, Ws + wn + fr, fk);
-  }
-  // C layout of 16x16x4: acc[r] = C[4 * (lane / 16) + r][lane % 16]
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int n = n0 + wn + 16 * j + fr;
-      if (n >= g.C_out) continue;
-      const float sc = scale[n], sh = shift[n];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const long row = m0 + wm + 16 * i + 4 * fk + r;
-        const float v = sum.at(i, j, r) * sc + sh;
-        if (row < g.M) out[row * g.ldc + g.offset + n] = v <= 0.0f ? 0.0f : v;      // torch's relu: a NaN stays a NaN
-      }
-    }
+        if (row_ok && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W) return *(const float4*)(xin + ((long)iy * g.W + ix) * g.C_in + c);
+        return make_float4(0.f, 0.f, 0.f, 0.f);
+      },
+      [&](int n) { return make_float2(scale[n], shift[n]); },
+      [&](long row, int n, float sum, float2 ss) {
+        const float v = sum * ss.x + ss.y;
+        slice[row * ldc + n] = v <= 0.0f ? 0.0f : v;      // torch's relu: a NaN stays a NaN
+      });
 }
 
 // ------------------------------------------------------------------ the 3 x 3 pools, NHWC, float4 along channels, into a channel slice
-DFH_DEVICE float pool_max(float m, float v) { return (v > m || v != v) ? v : m; }      // torch's update: a NaN wins and stays
-
 __global__ __launch_bounds__(THREADS) void incep_pool_kernel(const float4* __restrict__ x, float* __restrict__ out, int mode, int H, int W, int C4,
                                                              int OH, int OW, int ldc, int offset, long total) {
   const long t = (long)blockIdx.x * THREADS + threadIdx.x;
@@ -216,7 +174,7 @@ __global__ __launch_bounds__(THREADS) void incep_pool_kernel(const float4* __res
       if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
       const float4 v = x[((n * H + iy) * W + ix) * C4 + c];
       ++inside;
-      if (is_max) { a.x = pool_max(a.x, v.x); a.y = pool_max(a.y, v.y); a.z = pool_max(a.z, v.z); a.w = pool_max(a.w, v.w); }
+      if (is_max) { using dfh::pool_max; a.x = pool_max(a.x, v.x); a.y = pool_max(a.y, v.y); a.z = pool_max(a.z, v.z); a.w = pool_max(a.w, v.w); }
       else { a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w; }
     }
   if (!is_max) {
@@ -226,10 +184,12 @@ __global__ __launch_bounds__(THREADS) void incep_pool_kernel(const float4* __res
   *(float4*)(out + ((n * OH + oy) * OW + ox) * ldc + offset + 4 * c) = a;
 }
 
-// ------------------------------------------------------------------ out [n][C] = mean over the pixels, fp64 sums in a fixed order
-// grid (ceil(C / 64), n); thread -> (channel tid % 64, pixel group tid / 64): the group sums pixels g, g + 4, ... in index order, the four
-// groups are added as ((g0 + g1) + g2) + g3, the mean is rounded to fp32 once.
-__global__ __launch_bounds__(THREADS) void incep_gmean_kernel(const float* __restrict__ x, float* __restrict__ out, int HW, int C) {
+// ------------------------------------------------------------------ out [n][C] = mean over the HW rows of image n, fp64 sums in a fixed order
+// grid (ceil(C / 64), n); thread -> (channel tid % 64, row group tid / 64): the group sums rows g, g + 4, ... in index order, the four
+// groups are added as ((g0 + g1) + g2) + g3 and divided in fp64; Out = float (the global spatial mean of a block's pixels) rounds that
+// once, Out = double with n = 1 is the column mean of the statistics.
+template <class Out>
+__global__ __launch_bounds__(THREADS) void incep_mean_kernel(const float* __restrict__ x, Out* __restrict__ out, int HW, int C) {
   __shared__ double part[4][64];
   const int c = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
   const long n = blockIdx.y;
@@ -240,7 +200,7 @@ __global__ __launch_bounds__(THREADS) void incep_gmean_kernel(const float* __res
   __syncthreads();
   if (grp == 0 && c < C) {
     const int l = threadIdx.x;
-    out[n * C + c] = (float)((((part[0][l] + part[1][l]) + part[2][l]) + part[3][l]) / (double)HW);
+    out[n * C + c] = (Out)((((part[0][l] + part[1][l]) + part[2][l]) + part[3][l]) / (double)HW);
   }
 }
 
@@ -331,22 +291,8 @@ __global__ __launch_bounds__(THREADS) void incep_is_splits_kernel(const float* _
   }
 }
 
-// ------------------------------------------------------------------ statistics in fp64: column means, then the covariance on the fp64 MFMA
-// mu[d] = (sum over the rows) / N: thread -> (column tid % 64, row group tid / 64), groups added as ((g0 + g1) + g2) + g3
-__global__ __launch_bounds__(THREADS) void incep_colmean_kernel(const float* __restrict__ act, double* __restrict__ mu, int N, int D) {
-  __shared__ double part[4][64];
-  const int d = blockIdx.x * 64 + (threadIdx.x & 63), grp = threadIdx.x >> 6;
-  double s = 0.0;
-  if (d < D)
-    for (int r = grp; r < N; r += 4) s += (double)act[(long)r * D + d];
-  part[grp][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (grp == 0 && d < D) {
-    const int l = threadIdx.x;
-    mu[d] = (((part[0][l] + part[1][l]) + part[2][l]) + part[3][l]) / (double)N;
-  }
-}
-
+// ------------------------------------------------------------------ statistics in fp64: column means (incep_mean_kernel<double>, one
+// "image" of N rows), then the covariance on the fp64 MFMA
 // sigma[i][j] = sum_r (act[r][i] - mu[i]) (act[r][j] - mu[j]) / (N - 1): 64 x 64 tile a workgroup (grid: (column tile, row tile), only
 // tiles with column tile >= row tile work), four waves of 32 x 32 = 2 x 2 blocks of v_mfma_f64_16x16x4_f64, rows in steps of 16 through
 // k-major LDS images of the centred values.  Elements on and above the diagonal are written together with their mirror image.
@@ -410,7 +356,7 @@ __global__ __launch_bounds__(THREADS) void incep_cov_kernel(const float* __restr
 // ------------------------------------------------------------------ host: the layer list
 struct ConvDesc { std::string name; int cin, cin_pad, cout, kh, kw, stride, ph, pw, wi; size_t packed_off; };      // wi: table index of conv.weight
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using dfh::aligned16;
 size_t conv_packed_floats(int cin_pad, int cout, int kh, int kw) { return (size_t)cout * ((size_t)kh * kw * cin_pad + 2); }
 
 // ------------------------------------------------------------------ host: launchers
@@ -452,9 +398,10 @@ int launch_pool(const float* x, float* out, int mode, int n, int H, int W, int C
   return dfh::check_launch("incep_pool_kernel");
 }
 
-int launch_gmean(const float* x, float* out, int n, int HW, int C, hipStream_t s) {
-  hipLaunchKernelGGL(incep_gmean_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)n), dim3(THREADS), 0, s, x, out, HW, C);
-  return dfh::check_launch("incep_gmean_kernel");
+template <class Out>
+int launch_mean(const float* x, Out* out, int n, int HW, int C, hipStream_t s) {
+  hipLaunchKernelGGL(incep_mean_kernel<Out>, dim3((unsigned)((C + 63) / 64), (unsigned)n), dim3(THREADS), 0, s, x, out, HW, C);
+  return dfh::check_launch("incep_mean_kernel");
 }
 
 int launch_fc(const float* feat, const float* w, const float* bias, float* logits, int n, int K, int classes, hipStream_t s) {
@@ -561,10 +508,7 @@ struct dfh_incep {
   }
 
   int require_params(const float* const* params, int count, const char* who) const {
-    auto refuse = [&](const std::string& msg) { dfh::set_error(std::string(who) + ": " + msg); return -1; };
-    if (!params) return refuse("null argument: params");
-    if (count != t.num_params()) return refuse("params count does not match dfh_incep_num_params (" + std::to_string(t.num_params()) + ")");
-    return dfh::check_param_pointers(params, count, who, [&](int i) { return ": " + t.params[i].name; });
+    return dfh::require_params(t, params, count, who, "dfh_incep_num_params (" + std::to_string(t.num_params()) + ")");
   }
 };
 
@@ -858,7 +802,7 @@ int dfh_incep_forward(dfh_incep* c, const float* const* params, int count, const
       case DFH_INCEP_K_PREP: rc = launch_prep(src, n, H, W, c->cfg.resize_input, c->cfg.normalize_input, tv, dst, s); break;
       case DFH_INCEP_K_CONV: rc = launch_conv(src, (const float*)packed + c->conv[L.conv].packed_off, dst, n, L, s); break;
       case DFH_INCEP_K_POOL: rc = launch_pool(src, dst, L.pool_mode, n, L.Hin, L.Win, L.Cin, L.Hout, L.Wout, L.ldc, L.offset, s); break;
-      case DFH_INCEP_K_GMEAN: rc = launch_gmean(src, dst, n, L.Hin * L.Win, L.Cin, s); break;
+      case DFH_INCEP_K_GMEAN: rc = launch_mean(src, dst, n, L.Hin * L.Win, L.Cin, s); break;
       case DFH_INCEP_K_FC: rc = launch_fc(src, params[c->fc_w], params[c->fc_b], dst, n, L.Cin, L.Cout, s); break;
       case DFH_INCEP_K_SOFTMAX: rc = launch_softmax(src, dst, n, L.Cout, s); break;
       default: DFH_REQUIRE(false, "unknown launch kind in the plan");
@@ -913,7 +857,7 @@ int dfh_incep_pool(const float* x, float* out, int mode, int n, int H, int W, in
 int dfh_incep_global_mean(const float* x, float* out, int n, int HW, int C, void* stream) {
   DFH_REQUIRE(x && out, "null argument");
   DFH_REQUIRE(n >= 1 && n <= 65535 && HW >= 1 && C >= 1, "n must be in [1, 65535], HW and C positive");
-  return launch_gmean(x, out, n, HW, C, (hipStream_t)stream);
+  return launch_mean(x, out, n, HW, C, (hipStream_t)stream);
 }
 
 int dfh_incep_fc_softmax(const float* feat, const float* weight, const float* bias, float* logits, float* probs, int n, int K, int classes,
@@ -946,8 +890,7 @@ int dfh_incep_stats(const float* act, int N, int D, double* mu, double* sigma, v
   DFH_REQUIRE(N >= 2, "the covariance needs at least two rows (N - 1 divides), got N = " + std::to_string(N));
   DFH_REQUIRE(D >= 1 && D <= 46336, "D must be in [1, 46336]");
   const unsigned tiles = (unsigned)((D + 63) / 64);
-  hipLaunchKernelGGL(incep_colmean_kernel, dim3(tiles), dim3(THREADS), 0, (hipStream_t)stream, act, mu, N, D);
-  if (int rc = dfh::check_launch("incep_colmean_kernel")) return rc;
+  if (int rc = launch_mean(act, mu, 1, N, D, (hipStream_t)stream)) return rc;
   hipLaunchKernelGGL(incep_cov_kernel, dim3(tiles, tiles), dim3(THREADS), 0, (hipStream_t)stream, act, mu, sigma, N, D);
   return dfh::check_launch("incep_cov_kernel");
 }

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(SLAB_LANES) void history_rows_kernel(const float* _
   *o = acc;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using dfh::aligned16;
 
 }  // namespace
 

@@ -179,8 +179,6 @@ __global__ __launch_bounds__(THREADS) void lpips_conv3x3_relu_kernel(const float
 }
 
 // ------------------------------------------------------------------ max_pool2d(2, 2), floor mode, NHWC, float4 along channels
-DFH_DEVICE float pool_max(float m, float v) { return (v > m || v != v) ? v : m; }      // torch's update: a NaN wins and stays
-
 __global__ __launch_bounds__(THREADS) void lpips_maxpool2x2_kernel(const float4* __restrict__ x, float4* __restrict__ out, int H, int W, int C4,
                                                                    int OH, int OW, long total) {
   const long t = (long)blockIdx.x * THREADS + threadIdx.x;
@@ -197,6 +195,7 @@ __global__ __launch_bounds__(THREADS) void lpips_maxpool2x2_kernel(const float4*
 #pragma unroll
     for (int dx = 0; dx < 2; ++dx) {
       const float4 v = x[((n * H + 2 * oy + dy) * W + 2 * ox + dx) * C4 + c];
+      using dfh::pool_max;
       m.x = pool_max(m.x, v.x); m.y = pool_max(m.y, v.y); m.z = pool_max(m.z, v.z); m.w = pool_max(m.w, v.w);
     }
   out[t] = m;
@@ -313,7 +312,7 @@ struct LpipsWorkspace : dfh::WorkspaceCarve {
   }
 };
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using dfh::aligned16;
 
 int launch_prep(const void* src, int src_kind, const float* lut, const float* shift, const float* scale, int normalize, float* out, long n,
                 int H, int W, hipStream_t s) {
@@ -389,10 +388,7 @@ struct dfh_lpips {
 
   // what every entry point that takes the parameter table requires of it, on the host, before any HIP call
   int require_params(const float* const* params, int count, const char* who) const {
-    auto refuse = [&](const std::string& msg) { dfh::set_error(std::string(who) + ": " + msg); return -1; };
-    if (!params) return refuse("null argument: params");
-    if (count != t.num_params()) return refuse("params count does not match dfh_lpips_num_params (" + std::to_string(DFH_LPIPS_NUM_PARAMS) + ")");
-    return dfh::check_param_pointers(params, count, who, [&](int i) { return ": " + t.params[i].name; });
+    return dfh::require_params(t, params, count, who, "dfh_lpips_num_params (" + std::to_string(DFH_LPIPS_NUM_PARAMS) + ")");
   }
 };
 

@@ -14,7 +14,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from ._native import FrozenDict, NativeModule, grow_buffer, read_checkpoint_config, require_params_on, save_checkpoint
+from ._native import FrozenDict, PackedModule
 
 VARIANT_TV, VARIANT_FID = 0, 1
 BLOCK_DIMS = (64, 192, 768, 2048)
@@ -32,16 +32,15 @@ def plan(ctx, n: int, H: int, W: int):
     return out
 
 
-class _Inception(NativeModule):
+class _Inception(PackedModule):
     family = "incep"
-    weights_name = "model.safetensors"
+    _inference_only = ("{name} is inference only on this path (BatchNorm runs on its running statistics, "
+                       "there is no backward kernel); .eval() is the only mode")
     _fp32_rule = "parameters must stay fp32 (the kernels pack their own fp32 copy)"
     _dropped = ()                                        # state-dict prefixes of the foreign checkpoint that never run here
 
     def _init_network(self, init_seed: Optional[int], max_workspace_bytes: int):
-        if max_workspace_bytes < 1:
-            raise ValueError(f"max_workspace_bytes must be positive, got {max_workspace_bytes}")
-        self.max_workspace_bytes = int(max_workspace_bytes)
+        self._set_workspace_limit(max_workspace_bytes)
         table = self.param_table()
         self._names = [n for n, _ in table]
         # seeded stand-ins: He-scaled conv weights, identity BatchNorm statistics; real weights come in through load_state_dict,
@@ -55,15 +54,8 @@ class _Inception(NativeModule):
                     p.mul_((2.0 / (p.shape[1] * p.shape[2] * p.shape[3])) ** 0.5)
                 elif name == "fc.weight":
                     p.mul_(0.02)
-        self._ws = self._packed = None
         super().train(False)
         self.requires_grad_(False)
-
-    def train(self, mode: bool = True):
-        if mode:
-            raise NotImplementedError(f"{type(self).__name__} is inference only on this path (BatchNorm runs on its running statistics, "
-                                      "there is no backward kernel); .eval() is the only mode")
-        return super().train(False)
 
     # ------------------------------------------------------------------ plumbing
     def _c_config(self) -> _lib.IncepConfigC:
@@ -101,43 +93,6 @@ class _Inception(NativeModule):
             mine[k].copy_(sd[k].reshape(mine[k].shape))
         return self
 
-    def save_pretrained(self, save_directory: str, **unused):
-        save_checkpoint(self, save_directory, dict(architectures=[type(self).__name__]))
-
-    @classmethod
-    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, **kw):
-        from ._ckpt import load_weights
-        d, cfg = read_checkpoint_config(cls, path, subfolder)
-        cfg.pop("architectures", None)
-        model = cls(init_seed=None, **cfg, **kw)
-        model.load_state_dict(load_weights(d, variant, ("model",)))
-        return model
-
-    def _buffer(self, name: str, nbytes: int, dev: torch.device) -> torch.Tensor:
-        packed = self._packed
-        buf = grow_buffer(self, name, nbytes, dev)
-        if self._packed is not packed:
-            self._packed_sig = None                      # a new block holds no packed copy yet
-        return buf
-
-    def _context(self):
-        if self._ctx is None:
-            self._ctx = self._make_ctx()
-        return self._ctx
-
-    def _prepare(self, dev: torch.device):
-        """Context, checked parameters and a current packed copy -> (pointer array, count, packed)."""
-        ctx = self._context()
-        plist = self._plist()
-        require_params_on(dev, plist)
-        packed = self._buffer("_packed", self._entry("packed_bytes")(ctx), dev)
-        arr = self._pointers(plist)
-        sig = self._signature(plist)
-        if sig != self._packed_sig:
-            _lib.call("dfh_incep_pack", ctx, arr, len(plist), _lib.ptr(packed), _lib.stream_ptr())
-            self._packed_sig = sig
-        return arr, len(plist), packed
-
     def images_per_call(self, H: int, W: int) -> int:
         """How many images one launch sequence takes so that its workspace stays under ``max_workspace_bytes``."""
         ctx = self._context()
@@ -156,20 +111,13 @@ class _Inception(NativeModule):
                 hi = mid - 1
         return lo
 
-    def _check_images(self, x, what: str):
-        if not isinstance(x, torch.Tensor):
-            raise TypeError(f"{what}: the images must be a tensor")
-        dev = self._require_hip_fp32(what)
-        if x.device != dev:
-            raise _lib.DfhError(f"the images live on {x.device}, the model on {dev}: move them to the model's device (no CPU fallback)")
-        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
-            raise TypeError(f"images must be float32 [N, 3, H, W], got {x.dtype} {tuple(x.shape)}")
-        return dev
-
     @torch.no_grad()
     def _run(self, x: torch.Tensor, what: str):
         """-> (taps: {block: [N, C]}, probs [N, classes] or None)"""
-        dev = self._check_images(x, what)
+        if not isinstance(x, torch.Tensor):
+            raise TypeError(f"{what}: the images must be a tensor")
+        dev = self._require_hip_fp32(what)
+        self._check_images(x, dev)
         N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
         mask = self._block_mask()
         taps = {b: torch.empty((N, BLOCK_DIMS[b]), dtype=torch.float32, device=dev) for b in range(4) if mask >> b & 1}
@@ -179,12 +127,10 @@ class _Inception(NativeModule):
             step = self.images_per_call(H, W)
             with torch.cuda.device(dev):
                 arr, count, packed = self._prepare(dev)
-                ws = self._buffer("_ws", self._entry("workspace_bytes")(self._ctx, min(step, N), H, W), dev)
+                ws = self._workspace(dev, min(step, N), H, W)
                 for i in range(0, N, step):
                     n = min(step, N - i)
-                    a = x[i:i + n].contiguous()
-                    if a.data_ptr() % 16:                # a slice of a batch of odd-sized images
-                        a = a.clone()
+                    a = self._chunk(x, i, n)
                     tp = (C.c_void_p * 4)(*[taps[b][i:].data_ptr() if b in taps else 0 for b in range(4)])
                     _lib.call("dfh_incep_forward", self._ctx, arr, count, _lib.ptr(packed), _lib.ptr(a), n, H, W, tp,
                               _lib.ptr(None if probs is None else probs[i:]), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())

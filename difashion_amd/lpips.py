@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._native import FrozenDict, NativeModule, grow_buffer, read_checkpoint_config, require_params_on, save_checkpoint
+from ._native import FrozenDict, PackedModule
 
 SRC_U8_HWC, SRC_F32_CHW = 0, 1
 SHIFT = (-.030, -.088, -.188)
@@ -31,9 +31,12 @@ def im2tensor_table() -> np.ndarray:
     return (np.arange(256, dtype=np.float64) / (255. / 2.) - 1.).astype(np.float32)
 
 
-class LPIPS(NativeModule):
+class LPIPS(PackedModule):
     family = "lpips"
-    weights_name = "model.safetensors"
+    _inference_only = ("LPIPS is inference only on this path (the lpips package's eval_mode=True): there is no Dropout "
+                       "and no backward kernel; .eval() is the only mode")
+    _from_pretrained_kw = dict(pretrained=False)
+    _lut = None
     _fp32_rule = "parameters must stay fp32 (the kernels read them in place or pack their own fp32 copy)"
 
     def __init__(self, pretrained: bool = True, net: str = "vgg", version: str = "0.1", lpips: bool = True, spatial: bool = False,
@@ -52,10 +55,8 @@ class LPIPS(NativeModule):
             raise NotImplementedError("pnet_tune=True: this path is inference only, there is no backward kernel")
         if not eval_mode:
             raise NotImplementedError("eval_mode=False: this path is inference only (Dropout is the identity)")
-        if max_workspace_bytes < 1:
-            raise ValueError(f"max_workspace_bytes must be positive, got {max_workspace_bytes}")
+        self._set_workspace_limit(max_workspace_bytes)
         self.config = FrozenDict(net="vgg", version=version)
-        self.max_workspace_bytes = int(max_workspace_bytes)
         table = self.param_table()
         self._names = [n for n, _ in table]
         # seeded stand-ins (the lin weights made non-negative, as the trained ones are); real weights come in through load_state_dict,
@@ -66,17 +67,10 @@ class LPIPS(NativeModule):
             self.scaling_layer.scale.copy_(torch.tensor(SCALE).view(1, 3, 1, 1))
             for k in range(NUM_LAYERS):
                 getattr(self, f"lin{k}").model._modules["1"].weight.abs_()
-        self._ws = self._packed = self._lut = None
         super().train(False)
         self.requires_grad_(False)
         if pretrained and model_path is not None:
             self.load_reference_weights(torch.load(model_path, map_location="cpu", weights_only=True), None)
-
-    def train(self, mode: bool = True):
-        if mode:
-            raise NotImplementedError("LPIPS is inference only on this path (the lpips package's eval_mode=True): there is no Dropout "
-                                      "and no backward kernel; .eval() is the only mode")
-        return super().train(False)
 
     # ------------------------------------------------------------------ plumbing
     def _c_config(self) -> _lib.LpipsConfigC:
@@ -110,43 +104,9 @@ class LPIPS(NativeModule):
                 mine[name].copy_(vgg16_state_dict[key].reshape(mine[name].shape))
         return self
 
-    def save_pretrained(self, save_directory: str, **unused):
-        save_checkpoint(self, save_directory, dict(architectures=["LPIPS"]))
-
-    @classmethod
-    def from_pretrained(cls, path: str, subfolder: Optional[str] = None, variant: Optional[str] = None, **kw):
-        from ._ckpt import load_weights
-        d, cfg = read_checkpoint_config(cls, path, subfolder)
-        cfg.pop("architectures", None)
-        model = cls(init_seed=None, pretrained=False, **cfg, **kw)
-        model.load_state_dict(load_weights(d, variant, ("model",)))
-        return model
-
-    def _buffer(self, name: str, nbytes: int, dev: torch.device) -> torch.Tensor:
-        packed = self._packed                            # 59 MB whatever the call: held across it, unlike the workspace
-        buf = grow_buffer(self, name, nbytes, dev)
-        if self._packed is not packed:
-            self._packed_sig = None                      # a new block holds no packed copy yet
-        return buf
-
-    def _prepare(self, dev: torch.device):
-        """Context, checked parameters and a current packed copy of the conv weights -> (pointer array, count, packed)."""
-        if self._ctx is None:
-            self._ctx = self._make_ctx()
-        plist = self._plist()
-        require_params_on(dev, plist)
-        packed = self._buffer("_packed", self._entry("packed_bytes")(self._ctx), dev)
-        arr = self._pointers(plist)
-        sig = self._signature(plist)
-        if sig != self._packed_sig:
-            _lib.call("dfh_lpips_pack", self._ctx, arr, len(plist), _lib.ptr(packed), _lib.stream_ptr())
-            self._packed_sig = sig
-        return arr, len(plist), packed
-
     def pairs_per_call(self, H: int, W: int) -> int:
         """How many pairs one launch sequence takes so that its workspace stays under ``max_workspace_bytes``."""
-        if self._ctx is None:
-            self._ctx = self._make_ctx()
+        self._context()
         need = self._entry("workspace_bytes")
         if need(self._ctx, 1, H, W) == 0:
             raise ValueError(f"images must be between 16 and 8192 pixels a side (four 2 x 2 pools leave the fifth level empty below 16), got {H} x {W}")
@@ -168,18 +128,16 @@ class LPIPS(NativeModule):
         if in0.shape != in1.shape or in0.dtype != in1.dtype or in0.device != in1.device:
             raise ValueError(f"in0 and in1 must share shape, dtype and device, got {tuple(in0.shape)} {in0.dtype} on {in0.device} and "
                              f"{tuple(in1.shape)} {in1.dtype} on {in1.device}")
-        if in0.device != dev:
-            raise _lib.DfhError(f"the images live on {in0.device}, the model on {dev}: move them to the model's device (no CPU fallback)")
-        if in0.dtype == torch.uint8 and in0.dim() == 4 and in0.shape[3] == 3:
+        u8 = in0.dtype == torch.uint8 and in0.dim() == 4 and in0.shape[3] == 3
+        self._check_images(in0, dev, " or uint8 [N, H, W, 3]", u8)
+        if u8:
             kind, (N, H, W) = SRC_U8_HWC, in0.shape[:3]
             if normalize:
                 raise ValueError("normalize=True applies to float images in [0, 1]; uint8 images go through im2tensor_lpips")
             if self._lut is None or self._lut.device != dev:
                 self._lut = torch.from_numpy(im2tensor_table()).to(dev)
-        elif in0.dtype == torch.float32 and in0.dim() == 4 and in0.shape[1] == 3:
-            kind, N, (H, W) = SRC_F32_CHW, in0.shape[0], in0.shape[2:]
         else:
-            raise TypeError(f"images must be float32 [N, 3, H, W] or uint8 [N, H, W, 3], got {in0.dtype} {tuple(in0.shape)}")
+            kind, N, (H, W) = SRC_F32_CHW, in0.shape[0], in0.shape[2:]
         N, H, W = int(N), int(H), int(W)
         step = self.pairs_per_call(H, W)
         dist = torch.empty((N,), dtype=torch.float32, device=dev)
@@ -187,16 +145,10 @@ class LPIPS(NativeModule):
         if N:
             with torch.cuda.device(dev):
                 arr, count, packed = self._prepare(dev)
-                n0 = min(step, N)
-                nbytes = self._entry("workspace_bytes")(self._ctx, n0, H, W)
-                ws = self._buffer("_ws", nbytes, dev)
+                ws = self._workspace(dev, min(step, N), H, W)
                 for i in range(0, N, step):
                     n = min(step, N - i)
-                    a, b = in0[i:i + n].contiguous(), in1[i:i + n].contiguous()
-                    if a.data_ptr() % 16:                # a slice of a batch of odd-sized images
-                        a = a.clone()
-                    if b.data_ptr() % 16:
-                        b = b.clone()
+                    a, b = self._chunk(in0, i, n), self._chunk(in1, i, n)
                     _lib.call("dfh_lpips_forward", self._ctx, arr, count, _lib.ptr(packed), _lib.ptr(a), _lib.ptr(b), kind,
                               _lib.ptr(self._lut if kind == SRC_U8_HWC else None), int(bool(normalize)), n, H, W, _lib.ptr(dist[i:]),
                               _lib.ptr(layers[i:]), _lib.ptr(ws), ws.numel(), _lib.stream_ptr())

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Output identity of the fp32 evaluation rows that share csrc/f32_tile.h (the CLIP towers' and the compatibility scorer's Linears and
-LayerNorms, the LPIPS convolution and its score sum) between two builds of the library (GPU only).
+LayerNorms, the LPIPS convolution and its score sum, the Inception convolution, classifier, means and statistics, the ragged ranking)
+between two builds of the library (GPU only).
 
 One process, one library (DFH_LIB chooses it): a fixed list of seeded cases goes through the public entry points, and one line per case
 carries the SHA-256 of every output.  Run it with each build and compare the two outputs line for line:
@@ -10,6 +11,7 @@ carries the SHA-256 of every output.  Run it with each build and compare the two
 
 Weights and inputs come from seeds (CPU generators): no fixtures.  The shapes are the smallest that reach every edge of the shared
 steps: ragged M and N tiles, a ragged last k-tile, one and many k-tiles, one M tile, both LPIPS chunk widths, partial spatial tiles."""
+import ctypes as C
 import hashlib
 import os
 import sys
@@ -19,6 +21,7 @@ import torch
 
 import difashion_amd as da
 from difashion_amd import _lib
+from tests.test_gpu_inception import CONV_CASES
 
 DEV = "cuda"
 
@@ -101,6 +104,61 @@ def lpips_forward(h, w):
     return dict(distance=val, per_layer=torch.cat(layers))
 
 
+def incep_conv(cin, cout, k, stride, pad, h, w, ldc, offset, n=3):
+    g = torch.Generator(device="cpu").manual_seed(cin * 131 + cout)
+    cin_pad = (cin + 3) // 4 * 4
+    x = torch.zeros((n, h, w, cin_pad))
+    x[..., :cin] = torch.randn((n, h, w, cin), generator=g)
+    wt = torch.randn((cout, cin, k[0], k[1]), generator=g) * (2.0 / (cin * k[0] * k[1])) ** 0.5
+    bn = [(0.75 + 0.5 * torch.rand(cout, generator=g)).to(DEV), (0.1 * torch.randn(cout, generator=g)).to(DEV),
+          (0.2 * torch.randn(cout, generator=g)).to(DEV), (0.5 + torch.rand(cout, generator=g)).to(DEV)]
+    x, wt = x.to(DEV), wt.to(DEV)
+    oh, ow = (h + 2 * pad[0] - k[0]) // stride + 1, (w + 2 * pad[1] - k[1]) // stride + 1
+    out = torch.full((n, oh, ow, ldc), float("nan"), device=DEV)
+    packed = torch.empty((cout * (k[0] * k[1] * cin_pad + 2),), device=DEV)
+    _lib.call("dfh_incep_conv_bn_relu", _lib.ptr(x), _lib.ptr(wt), cin, (C.c_void_p * 4)(*[t.data_ptr() for t in bn]), _lib.ptr(packed), _lib.ptr(out),
+              n, h, w, cin_pad, cout, k[0], k[1], stride, pad[0], pad[1], ldc, offset, _lib.stream_ptr())
+    return dict(out=out[..., offset:offset + cout], packed=packed)
+
+
+def incep_fc(n, K, classes):
+    feat, wt, bias = rnd(n, K, seed=71).to(DEV), (rnd(classes, K, seed=72) * K ** -0.5).to(DEV), rnd(classes, seed=73).to(DEV)
+    logits, probs = torch.empty((n, classes), device=DEV), torch.empty((n, classes), device=DEV)
+    _lib.call("dfh_incep_fc_softmax", _lib.ptr(feat), _lib.ptr(wt), _lib.ptr(bias), _lib.ptr(logits), _lib.ptr(probs), n, K, classes, _lib.stream_ptr())
+    return dict(logits=logits, probs=probs)
+
+
+def incep_gmean(n, hw, c):
+    x, out = rnd(n, hw, c, seed=74).to(DEV), torch.empty((n, c), device=DEV)
+    _lib.call("dfh_incep_global_mean", _lib.ptr(x), _lib.ptr(out), n, hw, c, _lib.stream_ptr())
+    return dict(mean=out)
+
+
+def incep_stats(N, D):
+    act = rnd(N, D, seed=75).to(DEV)
+    mu, sigma = torch.empty((D,), dtype=torch.float64, device=DEV), torch.empty((D, D), dtype=torch.float64, device=DEV)
+    _lib.call("dfh_incep_stats", _lib.ptr(act), N, D, _lib.ptr(mu), _lib.ptr(sigma), _lib.stream_ptr())
+    return dict(mu=mu, sigma=sigma)
+
+
+def incep_model(make):
+    m = make().to(DEV)                                      # the wrappers' own seeded stand-ins (init_seed=0)
+    x = torch.rand(2, 3, 80, 96, generator=torch.Generator(device="cpu").manual_seed(81)).to(DEV)
+    out = m(x)
+    return {f"block{b}": t for b, t in zip(m.output_blocks, out)} if isinstance(out, list) else dict(probs=out, feat=m.feature_extract(x))
+
+
+def ragged_rank():
+    gen, table = rnd(75, 44, seed=91).to(DEV), rnd(150, 44, seed=92).to(DEV)
+    perm = torch.randperm(150, generator=torch.Generator(device="cpu").manual_seed(93))
+    r = da.rank_candidates(gen, table, (torch.tensor([0] * 5 + [1] * 70), [perm[:3], perm[3:133]]), 100)
+    return dict(ids=r.ids, positions=r.positions, sims=r.sims, counts=r.counts)
+
+
+def all_finite(name, v):
+    return name == "sims" or not v.is_floating_point() or bool(torch.isfinite(v).all())       # empty rank slots hold -inf
+
+
 CASES = [
     ("text dfh_clip_encode 64/128 x3 B=5 T=77 quick_gelu (M=385)", lambda: text_encode(5, 77)),
     ("text dfh_clip_text_embeds 96/160 x2 B=4 T=77 gelu proj 48", text_embeds),
@@ -115,6 +173,14 @@ CASES = [
      for cin, cout, h, w in ((4, 64, 19, 23), (64, 128, 19, 23), (256, 256, 11, 13), (512, 512, 9, 10))] + [
     ("lpips dfh_lpips_forward 16x16, 2 pairs", lambda: lpips_forward(16, 16)),
     ("lpips dfh_lpips_forward 37x45, 2 pairs", lambda: lpips_forward(37, 45)),
+] + [("incep dfh_incep_conv_bn_relu n=3 " + str(c).replace(" ", ""), lambda c=c: incep_conv(*c)) for c in CONV_CASES] + [
+    ("incep dfh_incep_fc_softmax n=5 K=100 classes=50", lambda: incep_fc(5, 100, 50)),
+    ("incep dfh_incep_global_mean n=2 HW=35 C=70", lambda: incep_gmean(2, 35, 70)),
+    ("incep dfh_incep_stats (5, 70)", lambda: incep_stats(5, 70)),
+    ("incep dfh_incep_stats (33, 130)", lambda: incep_stats(33, 130)),
+    ("incep FIDInceptionV3((0, 1, 2, 3)) 2 x 80 x 96, resize", lambda: incep_model(lambda: da.FIDInceptionV3((0, 1, 2, 3)))),
+    ("incep InceptionV3(num_classes=50) 2 x 80 x 96, resize", lambda: incep_model(lambda: da.InceptionV3(num_classes=50, resize_input=True, normalize_input=True))),
+    ("rank rank_candidates 5 + 70 rows, 3 / 130 candidates, dim 44", ragged_rank),
 ]
 
 
@@ -127,5 +193,5 @@ if __name__ == "__main__":
             continue
         outs = run()
         torch.cuda.synchronize()
-        finite = all(bool(torch.isfinite(v).all()) for v in outs.values())
+        finite = all(all_finite(k, v) for k, v in outs.items())
         print(f"{name:62s} " + " ".join(f"{k} {sha(v)}" for k, v in outs.items()) + ("" if finite else " NOT-FINITE"), flush=True)

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """What the Python model wrappers build, as text: run it on two commits and diff the outputs (CPU; needs only the built library).
 
-Per model (U-Net at SD-1.5 defaults and tiny, VAE at defaults and tiny, CLIP tiny and CLIP-L, two tiny CLIP vision towers), once with
+Per model (U-Net at SD-1.5 defaults and tiny, VAE at defaults and tiny, CLIP tiny and CLIP-L, two tiny CLIP vision towers, LPIPS and the
+two Inception v3 variants), once with
 ``init_seed=0`` and once with ``init_seed=None``: the native ``param_table()``, the ``state_dict()`` key order and a SHA-256 over the
-parameter bytes; the ViT-H/14 vision table without its weights.  Then the five wrappers (MutualEncoder included) through
+parameter bytes; the ViT-H/14 vision table without its weights.  Then the eight wrappers (MutualEncoder included) through
 ``save_pretrained`` / ``from_pretrained``: file names, sorted ``config.json`` keys, what the reloaded object keeps in ``.config``,
-and whether the state dicts agree bit for bit.
+and whether the state dicts agree bit for bit.  ``--digest`` prints one SHA-256 line per table / key listing instead of the listing.
 
-A refactor of difashion_amd/{_native,unet,vae,clip,clip_vision,mutual}.py must leave this output unchanged
+A refactor of difashion_amd/{_native,unet,vae,clip,clip_vision,mutual,lpips,inception}.py must leave this output unchanged
 (profiles/native_module_identity.txt).
 The hashes are NOT a test: they would pin torch's CPU generator, not this code."""
 import hashlib
@@ -30,7 +31,20 @@ MODELS = [("unet sd15", da.UNet2DConditionModel, {}), ("unet tiny", da.UNet2DCon
           ("vae default", da.AutoencoderKL, {}), ("vae tiny", da.AutoencoderKL, TINY_VAE),
           ("clip tiny", da.CLIPTextModel, TINY_CLIP), ("clip L", da.CLIPTextModel, {}),
           ("clip vision tiny quick_gelu", da.CLIPVisionModelWithProjection, TINY_QUICKGELU.kwargs()),
-          ("clip vision tiny gelu", da.CLIPVisionModelWithProjection, TINY_GELU.kwargs())]
+          ("clip vision tiny gelu", da.CLIPVisionModelWithProjection, TINY_GELU.kwargs()),
+          ("lpips vgg16", da.LPIPS, {}), ("fid inception v3, four blocks", da.FIDInceptionV3, dict(output_blocks=(0, 1, 2, 3))),
+          ("inception v3, 50 classes", da.InceptionV3, dict(num_classes=50))]
+
+
+DIGEST = "--digest" in sys.argv      # one sha256 line per table / key listing instead of the listing: the form that is kept in profiles/
+
+
+def listing(lines):
+    lines = list(lines)
+    if DIGEST:
+        print(f"listing sha256 {hashlib.sha256(chr(10).join(lines).encode()).hexdigest()} ({len(lines)} lines)")
+    else:
+        print("\n".join(lines))
 
 
 def digest(sd):
@@ -49,10 +63,7 @@ def describe(title, cls, kw):
         print(f"== {title}, init_seed={seed}: {len(table)} table entries, {len(keys)} state-dict keys, "
               f"{sum(v.numel() for v in sd.values())} values, dtypes {sorted({str(v.dtype) for v in sd.values()})}")
         if first is None or first != (table, keys):
-            for name, shape in table:
-                print(f"table {name} {shape}")
-            for k in keys:
-                print(f"key {k} {tuple(sd[k].shape)}")
+            listing([f"table {name} {shape}" for name, shape in table] + [f"key {k} {tuple(sd[k].shape)}" for k in keys])
         else:
             print("table and key order: identical to the init_seed=0 build above")
         first = (table, keys)
@@ -87,8 +98,7 @@ def main():
     vit.register_to_config(**VIT_H_14.kwargs())                         # the full-size table from the library alone: no weights
     table = vit.param_table()
     print(f"== clip vision ViT-H/14: {len(table)} table entries, {sum(torch.Size(s).numel() for _, s in table)} values, no weights")
-    for name, shape in table:
-        print(f"table {name} {shape}")
+    listing(f"table {name} {shape}" for name, shape in table)
     unet = da.UNet2DConditionModel(init_seed=3, **TINY_UNET)
     unet.register_to_config(decay=0.9999, optimization_step=7)          # what diffusers' EMAModel.save_pretrained adds
     back = round_trip("unet tiny", unet, da.UNet2DConditionModel.from_pretrained, max_batch=3)
@@ -104,6 +114,10 @@ def main():
     round_trip("clip tiny", da.CLIPTextModel(init_seed=3, **TINY_CLIP), da.CLIPTextModel.from_pretrained)
     round_trip("clip vision tiny", da.CLIPVisionModelWithProjection(init_seed=3, **TINY_QUICKGELU.kwargs()),
                da.CLIPVisionModelWithProjection.from_pretrained)
+    round_trip("lpips vgg16", da.LPIPS(init_seed=3), da.LPIPS.from_pretrained)
+    round_trip("fid inception v3", da.FIDInceptionV3((1, 3), resize_input=False, init_seed=3), da.FIDInceptionV3.from_pretrained)
+    back = round_trip("inception v3", da.InceptionV3(num_classes=50, init_seed=3), da.InceptionV3.from_pretrained, max_workspace_bytes=1 << 30)
+    print(f"max_workspace_bytes {back.max_workspace_bytes}")
     torch.manual_seed(4)
     enc = da.MutualEncoder(cate_num=4, cate_emb_size=8, latent_channels=4, latent_size=16, hid_dim=32)
     enc.register_to_config(decay=0.9999)
