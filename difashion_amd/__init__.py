@@ -17,6 +17,7 @@ from .vae import AutoencoderKL
 from .clip import CLIPTextModel, CLIPTextModelOutput, CLIPTextModelWithProjection
 from .clip_vision import CLIPVisionModelOutput, CLIPVisionModelWithProjection
 from .image_processor import CLIPImageProcessor
+from .jpeg import jpeg_quant_tables, jpeg_roundtrip
 from .evalscores import (CLIPScore, CompatibilityEvaluator, FashionEvaluator, candidate_cosine, extract_image_features, lpips_given_data,
                          lpips_retrieval, pair_cosine)
 from .evalscores import (RankResult, clip_gor_retrieval_given_data, clip_og_retrieval_given_data, embed_row_norms, rank_candidates,
@@ -40,4 +41,5 @@ __all__ = [
     "FIDInceptionV3", "InceptionV3", "activation_statistics", "frechet_distance", "fid_given_data", "inception_rows",
     "inception_score_from_probs", "inception_score_given_data",
     "ItemLatentStore", "HistoryTable",
+    "jpeg_roundtrip", "jpeg_quant_tables",
 ]

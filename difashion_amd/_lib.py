@@ -252,6 +252,10 @@ SIGNATURES = {
     "dfh_imgproc_table_bytes": (_sz, [_vp]),
     "dfh_imgproc_fill_tables": (_i, [_vp, _vp, _sz]),
     "dfh_imgproc_run": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "dfh_jpeg_quant_tables": (_i, [_i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dfh_jpeg_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "dfh_jpeg_coef_count": (_sz, [_i, _i, _i, _i]),
+    "dfh_jpeg_roundtrip": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "dfh_lpips_create": (_i, [C.POINTER(LpipsConfigC), C.POINTER(_vp)]),
     "dfh_lpips_destroy": (None, [_vp]),
     "dfh_lpips_num_params": (_i, [_vp]),

@@ -565,6 +565,29 @@ int dfh_imgproc_fill_tables(const dfh_imgproc* p, void* host_buffer, size_t buff
 int dfh_imgproc_run(const dfh_imgproc* p, const void* tables_dev, const float* lut_dev, const void* src, int src_kind, int batch,
                     float* pixel_values, uint8_t* out_u8, void* stream);
 
+/* ------------------------------------------------------------------ the JPEG save / open round trip
+ * Replaces (arithmetic) `img.save("<i>.jpg")` of every generated item (inf4eval.py:787-790) followed by `Image.open` where the metrics
+ * read it back (evaluate_gor.py:207-215, evaluate_fitb.py): PIL's baseline JPEG through libjpeg's "islow" path in both directions,
+ * without the byte stream (entropy coding is lossless).  RGB -> YCbCr, 2 x 2 chroma downsampling, forward DCT, quantisation,
+ * dequantisation, inverse DCT with libjpeg's wrapping range limit, "fancy" chroma upsampling, YCbCr -> RGB: 32-bit integers with fixed
+ * rounding, equal to PIL bit for bit, the same in both storage builds.  csrc/jpeg.hip: two launches, no atomics, nothing allocated. */
+#define DFH_JPEG_SUBSAMPLING_444 0 /* PIL's numbering of `subsampling=` */
+#define DFH_JPEG_SUBSAMPLING_420 2
+/* Host only: the two quantisation tables libjpeg uses at `quality` (1 .. 100), 64 values each in natural (row-major) order. */
+int dfh_jpeg_quant_tables(int quality, int* luma64, int* chroma64);
+/* Bytes of the workspace of one call (the decoded Y, Cb, Cr planes, padded to whole tiles); 0 with a message for arguments the round
+ * trip refuses. */
+size_t dfh_jpeg_workspace_bytes(int batch, int h, int w, int subsampling);
+/* int16 elements `coef` receives: 64 for every real block, batch * (ceil(h/8) * ceil(w/8) + 2 * chroma blocks). */
+size_t dfh_jpeg_coef_count(int batch, int h, int w, int subsampling);
+/* src: uint8 [batch][h][w][3] (src_kind DFH_IMGPROC_SRC_U8_HWC) or fp32 [batch][3][h][w] in [-1, 1] (DFH_IMGPROC_SRC_F32_CHW, quantised
+ * as dfh_imgproc_run does).  dst_hwc: uint8 [batch][h][w][3].  coef (may be NULL): the quantised coefficients, int16 in natural order,
+ * [batch][Y, Cb, Cr][block row][block column][64], real blocks only (the dummy blocks that fill an MCU are not part of it).
+ * Refused on the host before any launch: quality outside 1 .. 100, a subsampling other than the two above, batch / h / w below 1, a null
+ * pointer or one that is not 16-byte aligned, a workspace smaller than dfh_jpeg_workspace_bytes, dst_hwc overlapping src. */
+int dfh_jpeg_roundtrip(const void* src, int src_kind, int batch, int h, int w, int quality, int subsampling, uint8_t* dst_hwc, int16_t* coef,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ LPIPS on VGG16
  * Replaces (arithmetic) lpips.LPIPS(net="vgg", version="0.1", spatial=False) as Evaluation/eval_utils.py:473-501 and :769-821 call it:
  * the ScalingLayer, torchvision's vgg16().features up to relu5_3 (thirteen 3x3 convolutions with ReLU, four 2x2 max-pools), per tap
