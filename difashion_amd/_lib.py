@@ -309,6 +309,9 @@ SIGNATURES = {
     "dfh_unet_grad32_bytes": (_sz, [_vp]),
     "dfh_unet_train_workspace_bytes": (_sz, [_vp, _i]),
     "dfh_unet_bind_train": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i]),
+    "dfh_unet_set_checkpointing": (_i, [_vp, _i]),
+    "dfh_unet_checkpointing": (_i, [_vp]),
+    "dfh_unet_train_workspace_regions": (_i, [_vp, _i, C.POINTER(_sz)]),
     "dfh_unet_pack_train": (_i, [_vp, C.POINTER(_vp), _i, _vp]),
     "dfh_unet_pack_all": (_i, [_vp, C.POINTER(_vp), _i, _vp]),
     "dfh_unet_grad_sumsq": (_i, [_vp, _vp]),
@@ -405,7 +408,7 @@ SIGNATURES = {
     "dfh_noise_mix": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "dfh_mse_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
 }
-_NO_STATUS = {"dfh_abi_version", "dfh_census_count", "dfh_unet_num_params", "dfh_unet_param_ndim", "dfh_unet_param_dim", "dfh_vae_num_params",
+_NO_STATUS = {"dfh_abi_version", "dfh_census_count", "dfh_unet_checkpointing", "dfh_unet_num_params", "dfh_unet_param_ndim", "dfh_unet_param_dim", "dfh_vae_num_params",
               "dfh_vae_param_ndim", "dfh_vae_param_dim", "dfh_clip_num_params", "dfh_clip_param_ndim", "dfh_clip_param_dim",
               "dfh_clipv_num_params", "dfh_clipv_param_ndim", "dfh_clipv_param_dim", "dfh_lpips_num_params", "dfh_lpips_param_ndim", "dfh_lpips_param_dim",
               "dfh_imgproc_resized_height", "dfh_imgproc_resized_width", "dfh_imgproc_out_height", "dfh_imgproc_out_width", "dfh_imgproc_crop_top",

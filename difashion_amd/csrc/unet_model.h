@@ -115,6 +115,9 @@ struct dfh_unet : ParamTable {
   bf16_t* arena16t = nullptr; float* grad16 = nullptr; float* grad32 = nullptr;   // grad16/32: fp32, packed layouts of arena16/32
   char* tws = nullptr; size_t tws_bytes = 0; int train_max_batch = 0;
   struct TrainRun; TrainRun* tr = nullptr;
+  // gradient checkpointing of the training walk (dfh_unet_set_checkpointing): 0 off, 1 recompute the internals of every resnet /
+  // transformer layer in the backward, 2 the same but the attention outputs are kept.  Read when a step begins (TrainRun) and by plan_train
+  int ckpt = 0;
   // backward walk: the weight-gradient GEMM of a layer runs on a second stream beside the data-gradient GEMM of the same layer
   // (both only read dY): the tail round of one is filled with blocks of the other (unet_train.hip TrainRun::wgrad / join)
   hipStream_t side_stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;

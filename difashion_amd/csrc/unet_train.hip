@@ -13,8 +13,12 @@
 //       weight gradients = gemm_wgrad_kernel over the forward K-segment description, fp32 atomics straight into a
 //                         gradient arena laid out like the packed weights (no per-layer temporaries);
 //       norm / attention = their dedicated backward kernels (GroupNorm from saved mean/rstd, attention from LSE).
-//   * 288 GB HBM: every activation of the step is kept (no recomputation / gradient checkpointing); layer-internal
-//     gradient buffers come from a stack allocator and overlap across layers.
+//   * 288 GB HBM: by default every activation of the step is kept; layer-internal gradient buffers come from a stack
+//     allocator and overlap across layers.
+//   * gradient checkpointing (dfh_unet_set_checkpointing, DESIGN.md "Gradient checkpointing"): a resnet / transformer
+//     layer then keeps only its output.  Its internal forward tensors live in one recompute region that every such layer
+//     re-uses from the start, and the backward walk runs the layer's forward closure again right before the layer's tape
+//     entry.  Each layer's forward launches are stated ONCE (that closure); mode 2 keeps the attention outputs as well.
 //   * nothing is allocated per step: a dry run of the same forward + tape sizes the workspace.
 #include <array>
 #include <functional>
@@ -33,8 +37,15 @@ struct dfh_unet::TrainRun : WalkBase {
   // persist: every activation of the step and the gradients that cross layers; temp: layer-internal gradient buffers, a stack
   // partial2 (WalkBase): slab region of the weight-gradient launches on the side stream
   hipStream_t s2 = nullptr; bool forked = false;               // see wgrad() / join()
-  TrainRun(dfh_unet* u_, int B_, hipStream_t s_, bool dry_) : WalkBase(*u_, u_->cfg.norm_num_groups, B_, s_, dry_), u(u_) {}
+  TrainRun(dfh_unet* u_, int B_, hipStream_t s_, bool dry_) : WalkBase(*u_, u_->cfg.norm_num_groups, B_, s_, dry_), u(u_), ckpt(u_->ckpt) {}
   std::vector<std::function<void()>> tape;
+  // Gradient checkpointing (the mode of the context when this step began; 0: off).  recomp (WalkBase): the recompute region, where the
+  // layer-internal forward buffers of resnet() / transformer() come from instead of persist; every such layer starts it from 0, so it is
+  // as large as the largest layer needs.  refwd[i]: the forward closure of tape entry i (empty: nothing to recompute), run again by
+  // backward_next right before the entry; replay is set while it does.
+  const int ckpt;
+  bool in_layer = false, replay = false;
+  std::vector<std::function<void()>> refwd;
   std::vector<char> gstate;
   const float* d_out = nullptr; float* d_sample = nullptr;   // set by backward()
   float* dtemb_all = nullptr; size_t dtemb_bytes = 0;
@@ -50,15 +61,32 @@ struct dfh_unet::TrainRun : WalkBase {
   bf16_t* w16t(const Mat& m) const { return u->arena16t + m.off; }
   float* g32(const Vec& v) const { return u->grad32 + v.off; }
 
-  bf16_t* buf(size_t elems) { return (bf16_t*)persist.alloc(elems * 2); }
-  float* fbuf(size_t elems) { return (float*)persist.alloc(elems * 4); }
+  // forward buffers: from persist -- except between layer_begin() and layer_end() of a checkpointing walk, where they come from the
+  // recompute region unless the caller keeps them (keep: what the backward needs and the recompute does not make again)
+  Bump& fwd_region(bool keep) { return in_layer && !keep ? recomp : persist; }
+  bf16_t* buf(size_t elems, bool keep = false) { return (bf16_t*)fwd_region(keep).alloc(elems * 2); }
+  float* fbuf(size_t elems, bool keep = false) { return (float*)fwd_region(keep).alloc(elems * 4); }
   bf16_t* gbuf(size_t elems) { return (bf16_t*)temp.alloc(elems * 2); }
+  // The internal buffers of a resnet / transformer are allocated between these two (its output before them).  Checkpointing: every layer
+  // allocates from the start of the recompute region, in the order the layer's code states -- so the tensors its forward closure writes
+  // when it runs again land where the backward closure of the same layer expects them.  Mode 0: nothing changes hands.
+  void layer_begin() { if (ckpt) { in_layer = true; recomp.off = 0; } }
+  void layer_end() { in_layer = false; }
+  // One layer = its forward launches (fwd, run now) and its backward launches (bwd, the tape entry).  A checkpointing walk keeps fwd
+  // beside the entry: it is the only statement of the layer's forward, and backward_next runs it again.
+  void layer(std::function<void()> fwd, std::function<void()> bwd) {
+    fwd();
+    tape.push_back(std::move(bwd));
+    if (ckpt) { refwd.resize(tape.size()); refwd.back() = std::move(fwd); }
+  }
+  // mode 2, running again: the attention outputs and their LSE were kept, the attention launches (and the V^T they alone read) are skipped
+  bool skip_attention() const { return replay && ckpt == 2; }
   // activation + gradient buffer; io tensors (layer inputs / outputs) keep their gradient across layers
-  GT act(int H, int W, int C, bool io = false) {
+  GT act(int H, int W, int C, bool io = false, bool keep = false) {
     GT t; t.H = H; t.W = W; t.C = C;
     const size_t n = (size_t)B * H * W * C;
-    t.p = buf(n);
-    t.g = io ? buf(n) : gbuf(n);
+    t.p = buf(n, keep);
+    t.g = io ? buf(n, true) : gbuf(n);     // a gradient that crosses layers is never recomputed
     t.gid = (int)gstate.size();
     gstate.push_back(0);
     return t;
@@ -275,23 +303,27 @@ struct dfh_unet::TrainRun : WalkBase {
     const GT x1 = has1 ? *x1p : GT{};
     GT out = act(H, W, r.cout, true);
     const size_t mark = temp.off;
+    layer_begin();
     GT g1 = act(H, W, r.cin);
     float* st1 = fbuf((size_t)B * G * 2);
-    groupnorm(x0, x1p, r.n1w, r.n1b, u->cfg.norm_eps, 1, g1.p, st1);
     GT h1 = act(H, W, r.cout);
     GemmArgs f1 = conv_desc(g1.p, r.cin, H, W, H, W, 1, 0, r.w1, r.b1);
     f1.rowvec = temb_all; f1.rv_ld = u->temb_total; f1.rv_off = r.temb_off; f1.rows_per_b = H * W;
     f1.out = h1.p;
-    gemm(f1);
     GT g2 = act(H, W, r.cout);
     float* st2 = fbuf((size_t)B * G * 2);
-    groupnorm(h1, nullptr, r.n2w, r.n2b, u->cfg.norm_eps, 1, g2.p, st2);
     GemmArgs f2 = conv2_desc(g2.p, H, W, r.cout, r.w2, r.b2, r.shortcut, x0.p, x0.C, has1 ? x1.p : nullptr, x1.C);
     f2.out = out.p;
-    gemm(f2);
+    layer_end();
     temp.off = mark;
     const ResL* rp = &r;
-    tape.push_back([=] {
+    layer([=] {
+      const ResL& r = *rp;
+      groupnorm(x0, has1 ? &x1 : nullptr, r.n1w, r.n1b, u->cfg.norm_eps, 1, g1.p, st1);
+      gemm(f1);
+      groupnorm(h1, nullptr, r.n2w, r.n2b, u->cfg.norm_eps, 1, g2.p, st2);
+      if (!replay) gemm(f2);             // the output was kept: running again stops at what the backward reads (g1, h1, g2 and the statistics)
+    }, [=] {
       const ResL& r = *rp;
       // out = conv2(g2) + shortcut(x)  |  conv2(g2) + x
       wgrad(f2, out.g, r.cout, r.w2.off, &r.b2);
@@ -319,60 +351,76 @@ struct dfh_unet::TrainRun : WalkBase {
     GT out = act(H, W, C, true);
     const size_t mark = temp.off;
     const size_t MC = (size_t)M * C;
+    // ---- the layer's buffers and launch descriptors, in forward order (the launches themselves: the forward closure below)
+    layer_begin();
+    const bool keep_at = ckpt == 2;              // mode 2: the two attention outputs and their LSE stay in persist
     GT gn = act(H, W, C);
     float* st = fbuf((size_t)B * G * 2);
-    groupnorm(x, nullptr, a.nw, a.nb, 1e-6f, 0, gn.p, st);
     bf16_t *h0 = buf(MC), *h1 = buf(MC), *h2 = buf(MC), *h3 = buf(MC);
     bf16_t* gh = gbuf(MC);                       // one gradient buffer walks the residual stream h3 -> h0
-    GemmArgs f_pin = linear(gn.p, M, C, a.pin, &a.pinb, nullptr, h0, C);
+    GemmArgs f_pin = linear_desc(gn.p, M, C, a.pin, &a.pinb, nullptr, h0, C);
     // --- self attention
     GT n1 = act(H, W, C);
-    layernorm(h0, a.l1w, a.l1b, n1.p, M, C);
     // q | k | v in one [M][3C] buffer (the three matrices are packed back to back: build_attn): one projection, one weight-gradient
     // launch over N = 3C, one data-gradient launch over K = 3C
     if (a.v.off != a.qk.off + (size_t)2 * C * C || a.v.K != a.qk.K) { dfh::set_error("to_q | to_k | to_v are not packed back to back"); rc = -1; }
     GT qkv = act(H, W, 3 * C);
-    GemmArgs f_qkv = linear(n1.p, M, C, a.qk, nullptr, nullptr, qkv.p, 3 * C);
+    GemmArgs f_qkv = linear_desc(n1.p, M, C, a.qk, nullptr, nullptr, qkv.p, 3 * C);
     const int Np = (N + 7) & ~7;
     bf16_t* vt = buf((size_t)B * C * Np);
-    transpose(qkv.p + 2 * C, vt, N, C, 3 * C, Np, (long)N * 3 * C, (long)C * Np);
-    GT at = act(H, W, C);
-    float* lse1 = fbuf((size_t)B * heads * N);
-    float* delta = fbuf((size_t)B * heads * N);
-    attention(qkv.p, 3 * C, qkv.p + C, 3 * C, vt, Np, at.p, C, heads, N, N, 0, lse1);
-    GemmArgs f_o1 = linear(at.p, M, C, a.o1, &a.o1b, h0, h1, C);
+    GT at = act(H, W, C, false, keep_at);
+    float* lse1 = fbuf((size_t)B * heads * N, keep_at);
+    float* delta = fbuf((size_t)B * heads * N, true);      // written and read by the backward only: stays where it was
+    GemmArgs f_o1 = linear_desc(at.p, M, C, a.o1, &a.o1b, h0, h1, C);
     // --- cross attention over the T text tokens
     const int Tp = (T + 7) & ~7;
     GT n2 = act(H, W, C);
-    layernorm(h1, a.l2w, a.l2b, n2.p, M, C);
     GT q2 = act(H, W, C);
-    GemmArgs f_q2 = linear(n2.p, M, C, a.q2, nullptr, nullptr, q2.p, C);
-    GT at2 = act(H, W, C);
-    float* lse2 = fbuf((size_t)B * heads * N);
-    attention(q2.p, C, kx + a.x_off, XT, vxt + (size_t)a.x_off * Tp, Tp, at2.p, C, heads, N, T, (long)XT * Tp, lse2);
-    GemmArgs f_o2 = linear(at2.p, M, C, a.o2, &a.o2b, h1, h2, C);
+    GemmArgs f_q2 = linear_desc(n2.p, M, C, a.q2, nullptr, nullptr, q2.p, C);
+    GT at2 = act(H, W, C, false, keep_at);
+    float* lse2 = fbuf((size_t)B * heads * N, keep_at);
+    GemmArgs f_o2 = linear_desc(at2.p, M, C, a.o2, &a.o2b, h1, h2, C);
     // --- GEGLU feed-forward (pre-activation kept for the backward)
     GT n3 = act(H, W, C);
-    layernorm(h2, a.l3w, a.l3b, n3.p, M, C);
     GT ffpre = act(H, W, 8 * C);
     GT ff = act(H, W, 4 * C);
     // ff.net.0: the GEMM epilogue gates (value x exact-erf GELU(gate)) into ff AND writes the bias-added pre-activations the backward
     // needs as a second output -- a separate gating pass read the 8C-wide tensor back (DFH_TRAIN_GEGLU_FUSED=0: the two-launch form, A/B)
-    const bool geglu_split = !dfh::WalkKnobs::get().train_geglu_fused;
+    const bool geglu_fused = dfh::WalkKnobs::get().train_geglu_fused && (8 * C) % 128 == 0;
     GemmArgs f_ff1;
-    if (!geglu_split && (8 * C) % 128 == 0) {
+    if (geglu_fused) {
       f_ff1 = linear_desc(n3.p, M, C, a.ff1, &a.ff1b, nullptr, ff.p, 8 * C);
       f_ff1.act = ACT_GEGLU; f_ff1.ld_out = 4 * C; f_ff1.pre_out = ffpre.p; f_ff1.ld_pre = 8 * C;
-      gemm(f_ff1);
     } else {
-      f_ff1 = linear(n3.p, M, C, a.ff1, &a.ff1b, nullptr, ffpre.p, 8 * C);
-      TR_OP(dfh::geglu_fwd_launch(ffpre.p, ff.p, M, 8 * C, s));
+      f_ff1 = linear_desc(n3.p, M, C, a.ff1, &a.ff1b, nullptr, ffpre.p, 8 * C);
     }
-    GemmArgs f_ff2 = linear(ff.p, M, 4 * C, a.ff2, &a.ff2b, h2, h3, C);
-    GemmArgs f_pout = linear(h3, M, C, a.pout, &a.poutb, x.p, out.p, C);
+    GemmArgs f_ff2 = linear_desc(ff.p, M, 4 * C, a.ff2, &a.ff2b, h2, h3, C);
+    GemmArgs f_pout = linear_desc(h3, M, C, a.pout, &a.poutb, x.p, out.p, C);
+    layer_end();
     temp.off = mark;
     const AttL* ap = &a;
-    tape.push_back([=] {
+    layer([=] {
+      const AttL& a = *ap;
+      groupnorm(x, nullptr, a.nw, a.nb, 1e-6f, 0, gn.p, st);
+      gemm(f_pin);
+      layernorm(h0, a.l1w, a.l1b, n1.p, M, C);
+      gemm(f_qkv);
+      if (!skip_attention()) {
+        transpose(qkv.p + 2 * C, vt, N, C, 3 * C, Np, (long)N * 3 * C, (long)C * Np);
+        attention(qkv.p, 3 * C, qkv.p + C, 3 * C, vt, Np, at.p, C, heads, N, N, 0, lse1);
+      }
+      gemm(f_o1);
+      layernorm(h1, a.l2w, a.l2b, n2.p, M, C);
+      gemm(f_q2);
+      if (!skip_attention())
+        attention(q2.p, C, kx + a.x_off, XT, vxt + (size_t)a.x_off * Tp, Tp, at2.p, C, heads, N, T, (long)XT * Tp, lse2);
+      gemm(f_o2);
+      layernorm(h2, a.l3w, a.l3b, n3.p, M, C);
+      gemm(f_ff1);
+      if (!geglu_fused) TR_OP(dfh::geglu_fwd_launch(ffpre.p, ff.p, M, 8 * C, s));
+      gemm(f_ff2);
+      if (!replay) gemm(f_pout);         // the output was kept: running again stops at h3, the last tensor the backward reads
+    }, [=] {
       const AttL& a = *ap;
       // out = proj_out(h3) + x
       wgrad(f_pout, out.g, C, a.pout.off, &a.poutb);
@@ -563,7 +611,7 @@ int dfh_unet::backward(const float* d_out, float* d_sample, float* const* master
   size_t lo, hi;
   for (;;) {
     const int rc = backward_next(&lo, &hi, s);
-    if (rc < 0) { tr->tape.clear(); tr->bucket = 0; return rc; }      // one backward per forward, also after an error
+    if (rc < 0) { tr->tape.clear(); tr->refwd.clear(); tr->bucket = 0; return rc; }      // one backward per forward, also after an error
     if (rc == 0) break;
   }
   return backward_finish(master_grads, count, s, overwrite);
@@ -601,6 +649,13 @@ int dfh_unet::backward_next(size_t* lo, size_t* hi, hipStream_t s) {
   r.s = s;
   while (r.ready.empty() && r.next_entry >= 0 && !r.rc) {
     const int i = r.next_entry--;
+    // Checkpointing: the layer's own forward closure makes its internal tensors again, into the recompute region, on the caller's stream.
+    // The region's previous readers are the launches of entry i + 1: those on this stream are ahead of the recompute in stream order,
+    // and those on the side stream (weight gradients reading recomputed operands) are behind the join() that closed entry i + 1 below --
+    // every entry ends in one, in the monolithic backward and in the segmented one alike, since both come through here.  The readers
+    // of what is written now are this entry's launches: stream order again, the side stream forking from this stream after them
+    // (wgrad() records ev_fork).  So no further event is needed.
+    if (i < (int)r.refwd.size() && r.refwd[i]) { r.replay = true; r.refwd[i](); r.replay = false; }
     r.tape[i]();
     r.join();                                   // side-stream weight gradients of this entry: done before its ranges are handed out
     // buckets whose last writer just ran; neighbours that finish together are handed out as one range
@@ -623,7 +678,7 @@ int dfh_unet::backward_finish(float* const* master_grads, int count, hipStream_t
   DFH_REQUIRE(tr->next_entry < 0 && tr->ready.empty(), "dfh_unet_backward_next has not reached the end of the tape");
   DFH_REQUIRE(count == (int)params.size(), "parameter count mismatch");
   TrainRun& r = *tr;
-  r.tape.clear(); r.bucket = 0;
+  r.tape.clear(); r.refwd.clear(); r.bucket = 0;
   if (r.rc) return r.rc;
   tab_unpack.clear();
   for (const PackOp& op : packs) {
@@ -665,6 +720,28 @@ size_t dfh_unet_train_workspace_bytes(dfh_unet* u, int batch) {
   if (batch <= 0) return 0;
   return u->plan_train(batch).total() + 256;
 }
+
+int dfh_unet_train_workspace_regions(dfh_unet* u, int batch, size_t* regions) {
+  DFH_BF16_ONLY_TRAINING;
+  DFH_REQUIRE(u && regions && batch > 0, "null argument or batch <= 0");
+  const WorkspacePlan p = u->plan_train(batch);
+  regions[0] = p.head(); regions[1] = p.persist; regions[2] = p.temp; regions[3] = p.recomp;
+  return 0;
+}
+
+int dfh_unet_set_checkpointing(dfh_unet* u, int mode) {
+  DFH_BF16_ONLY_TRAINING;
+  DFH_REQUIRE(u, "null argument");
+  DFH_REQUIRE(mode >= 0 && mode <= 2, "checkpointing mode must be 0 (off), 1 (recompute) or 2 (recompute, attention outputs kept)");
+  if (mode == u->ckpt) return 0;
+  // the tape of a step holds addresses of the layout its forward planned
+  DFH_REQUIRE(!(u->tr && !u->tr->tape.empty()), "the checkpointing mode cannot change between dfh_unet_forward_train and its backward");
+  u->ckpt = mode;
+  // the bound workspace was sized for the other mode: bind again with dfh_unet_train_workspace_bytes of this one
+  u->tws = nullptr; u->tws_bytes = 0; u->train_max_batch = 0;
+  return 0;
+}
+int dfh_unet_checkpointing(const dfh_unet* u) { return u ? u->ckpt : 0; }
 
 int dfh_unet_bind_train(dfh_unet* u, void* arena16t, void* grad16, void* grad32, void* workspace, size_t workspace_bytes,
                         int max_batch) {

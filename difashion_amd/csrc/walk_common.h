@@ -175,25 +175,29 @@ struct WorkspaceHead {
 };
 
 // What a planning (dry) walk found a workspace needs behind its head: the two allocator regions and the split-K slab bytes (each rounded
-// to 256), for which batch, and how many slab regions the head holds (2: the training walk's side stream has its own).
+// to 256), for which batch, and how many slab regions the head holds (2: the training walk's side stream has its own).  recomp: the
+// recompute region of a checkpointing training walk (unet_train.hip), behind the other two; 0 everywhere else, which leaves the layout
+// of head | persist | temp what it is without it.
 struct WorkspacePlan {
-  size_t persist = 0, temp = 0, slab = 0; int batch = 0, nslab = 1;
-  size_t total() const { return batch ? WorkspaceHead(nullptr, batch, slab, nslab).bytes + persist + temp : 0; }
+  size_t persist = 0, temp = 0, slab = 0; int batch = 0, nslab = 1; size_t recomp = 0;
+  size_t head() const { return WorkspaceHead(nullptr, batch, slab, nslab).bytes; }
+  size_t total() const { return batch ? head() + persist + temp + recomp : 0; }
 };
 
 // Launch context of one walk over a model: the batch, the stream, dry (planning: allocate and size, launch nothing), the first error, the
-// two bump allocators, and the split-K slab region with the size the dry run found it needs.
+// two bump allocators (and the recompute region only a checkpointing training walk allocates from), and the split-K slab region with the
+// size the dry run found it needs.
 struct WalkBase {
   const ParamTable& pt; int groups;            // groups: GroupNorm groups of the model
   int B; hipStream_t s; bool dry;
-  Bump persist, temp; size_t partial_need = 0;
+  Bump persist, temp, recomp; size_t partial_need = 0;
   float* partial = nullptr; size_t partial_cap = 0;
   float* partial2 = nullptr;                   // the second slab region of a two-slab head (else null)
   float* gn_partial = nullptr; bf16_t* zero = nullptr;
   int rc = 0;
   WalkBase(const ParamTable& pt_, int groups_, int B_, hipStream_t s_, bool dry_) : pt(pt_), groups(groups_), B(B_), s(s_), dry(dry_) {
     // a planning walk hands out addresses that are never dereferenced: from a made-up base, so that offsets from them are defined
-    if (dry) persist.base = temp.base = (char*)(uintptr_t)(1 << 20);
+    if (dry) persist.base = temp.base = recomp.base = (char*)(uintptr_t)(1 << 20);
   }
   WalkBase(const WalkBase&) = delete;          // the allocators of a bound walk point at its rc
 
@@ -201,9 +205,10 @@ struct WalkBase {
   WorkspacePlan plan(int nslab = 1) const {
     auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
     WorkspacePlan p; p.persist = up(persist.peak); p.temp = up(temp.peak); p.slab = up(partial_need); p.batch = B; p.nslab = nslab;
+    p.recomp = up(recomp.peak);
     return p;
   }
-  // A real walk over [base, base + bytes): head | persist | temp as planned, both allocators bounded by their planned sizes, the zero
+  // A real walk over [base, base + bytes): head | persist | temp | recomp as planned, the allocators bounded by their planned sizes, the zero
   // page cleared on the stream.  Refuses (rc, false) a plan for another batch and a workspace smaller than the plan.
   bool bind(char* base, size_t bytes, const WorkspacePlan& p) {
     if (B != p.batch) { dfh::set_error("walk batch differs from the planned batch"); rc = -1; return false; }
@@ -212,6 +217,7 @@ struct WalkBase {
     zero = h.zero; gn_partial = h.gn_partial; partial = h.slab[0]; partial2 = h.slab[1]; partial_cap = h.slab_bytes;
     persist = Bump{base + h.bytes, p.persist, 0, 0, "persist", &rc};
     temp = Bump{base + h.bytes + p.persist, p.temp, 0, 0, "temp", &rc};
+    recomp = Bump{base + h.bytes + p.persist + p.temp, p.recomp, 0, 0, "recompute", &rc};
     if (hipMemsetAsync(zero, 0, 256, s) != hipSuccess) { dfh::set_error("hipMemsetAsync failed (zero page)"); rc = -2; }
     return rc == 0;
   }

@@ -7,8 +7,10 @@ Mirrors what the reference glue requires of ``self.unet``:
   * a replaceable ``.conv_in`` nn.Conv2d with ``out_channels/kernel_size/stride/padding/weight`` (:84-93);
   * ``parameters()/state_dict()/load_state_dict()`` with diffusers key names (train.py:508,545-547,586);
   * ``save_pretrained(dir)`` / ``from_pretrained(dir, subfolder=)`` (train.py:524,545; difashion.py:77-79);
-  * ``enable_gradient_checkpointing()`` / ``enable_xformers_memory_efficient_attention()`` (train.py:560,
-    difashion.py:118) -- accepted; attention here is always the fused flash-style HIP kernel.
+  * ``enable_gradient_checkpointing()`` (train.py:560): the training walk keeps only layer outputs and recomputes the rest
+    in the backward, bit-identical gradients (``disable_gradient_checkpointing()``, ``is_gradient_checkpointing``);
+  * ``enable_xformers_memory_efficient_attention()`` (difashion.py:118) -- accepted; attention here is always the fused
+    flash-style HIP kernel.
 
 Training (train.py:691-716): with grad enabled and parameters that require grad, ``forward`` runs the
 saving forward of the native library and hooks one autograd node onto the result; ``loss.backward()``
@@ -135,8 +137,34 @@ class UNet2DConditionModel(NativeModule):
         self._build_parameters(self.param_table(), lambda name: ".norm" in name or name.startswith("conv_norm_out"), init_seed, init_std)
 
     # ------------------------------------------------------------------ config plumbing
-    def enable_gradient_checkpointing(self):
-        return None
+    _ckpt_mode = 0                        # 0 off, 1 recompute, 2 recompute but keep the attention outputs (dfh_unet_set_checkpointing)
+
+    def enable_gradient_checkpointing(self, keep_attention: bool = False):
+        """train.py:559-560.  The training walk then keeps only the OUTPUT of every resnet / transformer layer and runs the layer's
+        forward launches again in the backward, right before the layer's own backward launches; the gradients are those of the
+        default walk (same kernels, same operands).  ``keep_attention=True`` also keeps the two attention outputs of every transformer
+        layer, so that the attention kernels -- the most expensive forward launches per byte they leave behind -- do not run twice.
+        What this saves and costs: DESIGN.md "Gradient checkpointing".  Only recorded here: it reaches the library when the training
+        arenas are bound, and a change drops the bound training workspace, so the next training forward allocates the smaller (or
+        larger) one.  Refused (DfhError) between a training forward and its backward.  Returns None, like diffusers'."""
+        self._set_checkpointing(2 if keep_attention else 1)
+
+    def disable_gradient_checkpointing(self):
+        self._set_checkpointing(0)
+
+    @property
+    def is_gradient_checkpointing(self) -> bool:
+        return self._ckpt_mode != 0
+
+    def _set_checkpointing(self, mode: int):
+        if mode == self._ckpt_mode:
+            return
+        if self._ctx is not None and self._train_buffers is not None:
+            # a workspace of the other mode is bound: the library unbinds it, or refuses while a step is between its forward and backward
+            _lib.call("dfh_unet_set_checkpointing", self._ctx, mode)
+        self._ckpt_mode = mode
+        self._train_buffers = None
+        self._train_batch = 0
 
     fp8_attention = False
 
@@ -231,6 +259,9 @@ class UNet2DConditionModel(NativeModule):
         lib = _lib.raw()
         dev = self.device
         ctx = self._ctx
+        # the checkpointing mode first: the workspace size below answers for it (an older library loaded for an A/B probe knows mode 0 only)
+        if self._ckpt_mode or "dfh_unet_set_checkpointing" not in _lib._UNBOUND:
+            _lib.call("dfh_unet_set_checkpointing", ctx, self._ckpt_mode)
         a16t = torch.zeros(lib.dfh_unet_arena16t_bytes(ctx), dtype=torch.uint8, device=dev)
         g16 = torch.zeros(lib.dfh_unet_grad16_bytes(ctx), dtype=torch.uint8, device=dev)     # padding between the packed
         g32 = torch.zeros(lib.dfh_unet_grad32_bytes(ctx), dtype=torch.uint8, device=dev)     # matrices travels through the all-reduce
@@ -356,6 +387,9 @@ class UNet2DConditionModel(NativeModule):
         return plist
 
     def _native_backward(self, d_out, need_dsample: bool):
+        if self._train_buffers is None:
+            raise _lib.DfhError("the training workspace of this step's forward is no longer bound (context rebuilt or checkpointing mode "
+                                "changed since): run the training forward again")
         d_out = d_out.contiguous().float()
         plist = self.grad_views()
         for p in plist:

@@ -146,7 +146,7 @@ int dfh_unet_forward_cached(dfh_unet* u, const void* sample, int sample_bf16, co
  * (dfh_unet_bind + dfh_unet_pack first) and adds
  *   arena16t  : bf16 transposed/flipped weight packs for the data-gradient GEMMs   (dfh_unet_arena16t_bytes)
  *   grad16/32 : fp32 gradient arenas in the PACKED layouts of arena16 / arena32      (dfh_unet_grad16/32_bytes)
- *   workspace : every activation of one step + gradient buffers                      (dfh_unet_train_workspace_bytes)
+ *   workspace : the activations one step keeps + gradient buffers                    (dfh_unet_train_workspace_bytes)
  * All pointers 256-byte aligned device memory; arena16t must be zero-filled before the first pack. */
 size_t dfh_unet_arena16t_bytes(dfh_unet* u);
 size_t dfh_unet_grad16_bytes(const dfh_unet* u);
@@ -154,6 +154,21 @@ size_t dfh_unet_grad32_bytes(const dfh_unet* u);
 size_t dfh_unet_train_workspace_bytes(dfh_unet* u, int batch);
 int dfh_unet_bind_train(dfh_unet* u, void* arena16t, void* grad16, void* grad32, void* workspace, size_t workspace_bytes,
                         int max_batch);
+/* Gradient checkpointing of the training walk (train.py:559-560, unet.enable_gradient_checkpointing()); a property of the context.
+ *   0 : off (default) -- the workspace holds every activation of the step;
+ *   1 : every resnet / transformer layer keeps only its output; the backward runs the layer's forward launches again, into one
+ *       recompute region shared by all layers, right before the layer's backward launches;
+ *   2 : as 1, but the two attention outputs of a transformer layer (and their log-sum-exp rows) are kept and the attention kernels
+ *       do not run again.
+ * The gradients are those of mode 0: the same kernels run on the same operands.  dfh_unet_train_workspace_bytes answers for the
+ * current mode, so set it BEFORE dfh_unet_bind_train: a change of mode unbinds the training workspace.  Refused for a mode outside
+ * 0..2 and between a dfh_unet_forward_train and its backward.
+ * dfh_unet_train_workspace_regions: the parts of dfh_unet_train_workspace_bytes (their sum + 256) in bytes --
+ * regions[0] head (zero page, GroupNorm partials, split-K slabs), [1] persistent activations, [2] layer-internal gradient stack,
+ * [3] recompute region (0 in mode 0). */
+int dfh_unet_set_checkpointing(dfh_unet* u, int mode);
+int dfh_unet_checkpointing(const dfh_unet* u);
+int dfh_unet_train_workspace_regions(dfh_unet* u, int batch, size_t* regions);
 /* master parameters -> arena16t; call together with dfh_unet_pack after every weight update */
 int dfh_unet_pack_train(dfh_unet* u, const float* const* master_params, int count, void* stream);
 /* dfh_unet_pack + dfh_unet_pack_train in one pass over the master parameters (each weight is read once and written to both arenas);
